@@ -16,10 +16,20 @@ N > 1   STRONG scaling of that cube: rank r owns rows [r*2048/N, (r+1)*2048/N) (
         kept), every step = the rank's kernel + the RCCL all-gather stitching the maps on every
         rank (one call at a time; the chunked form hides the stitch inside the call).
 
-Rank 0 prints ONE compact JSON line (< 6 KB, asserted: the round-5 line had grown to 31 KB and the
-driver could not parse it).  Everything else - every record with its statistics, strip terms,
-oracle windows - goes to bench_records.json beside this script and, one line per record, to stderr.
-N = 1 also times a CPU baseline: the numpy restatement of the reference's arithmetic (oracle),
+A plain run does only what `value` needs: it sets the cube up, warms up, times the K steps and prints
+ONE JSON line with the contract's keys (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`,
+`dtype`, ...) and the workload.  Everything else the benchmark measures or checks runs with --full:
+the kernel alone by HIP events (`roofline`), the oracle check of the first rows, the rank-strip
+terms, configs[1..4], the SURVEY 8(f) and float64 records, the CPU baseline and, at N > 1, the RCCL
+self-check, the pipelined form, the parts alone and the oracle / digest checks of the stitched maps.
+--dump-outputs DIR writes the three float64 maps of the timed path's last step to DIR/m0.npy, m1.npy,
+m2.npy at the spaxels where all three are finite, and that pattern to DIR/finite.npy (a fixed seeded
+sample of the spaxels, the same for all maps, when they exceed 48 MiB; see dump_outputs).
+
+With --full, rank 0 prints ONE compact JSON line (< 6 KB, asserted: the round-5 line had grown to
+31 KB and the driver could not parse it).  Everything else - every record with its statistics, strip
+terms, oracle windows - goes to bench_records.json beside this script and, one line per record, to
+stderr.  N = 1 also times a CPU baseline: the numpy restatement of the reference's arithmetic (oracle),
 threads over spaxel chunks like dask's `threads` scheduler, bounded sample of the same workload.
 No torch: with WORLD_SIZE unset and --gpus N > 1 this script starts its N ranks itself (one process
 per GPU, RANK / LOCAL_RANK / WORLD_SIZE in their environment, rank 0's JSON relayed as the last line
@@ -63,7 +73,16 @@ def parse(argv=None):
                     help="only the named config records (kernel work: before / after numbers)")
     ap.add_argument("--configs-scale", type=int, default=1, help="divide the config cubes' longest axis (smoke runs)")
     ap.add_argument("--records-file", default=os.path.join(REPO, "bench_records.json"))
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement and check (roofline, oracle, configs, CPU baseline, records file); "
+                         "the --no-* / --configs* / --cpu-seconds / --records-file options apply to it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the maps the timed path computed in its last step to DIR/<name>.npy (float64, the finite values) "
+                         "and their finite pattern to DIR/finite.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---- synthetic inputs (never timed) ------------------------------------------------------------
@@ -195,6 +214,29 @@ class Ms(float):
 
 def ms_stats(ms):
     return getattr(ms, "stats", {"median": float(ms), "min": float(ms), "max": float(ms), "mean": float(ms), "n": 1})
+
+
+DUMP_BUDGET = 48 << 20    # bytes of all dumped arrays together
+DUMP_SEED = 20260        # the sample of spaxels a dump keeps when the maps are larger than the budget
+
+
+def dump_outputs(dirname, maps):
+    """{name: host map} -> dirname/<name>.npy (float64) + dirname/finite.npy (float32).  The positions are ALL spaxels or,
+    when the maps would exceed DUMP_BUDGET, one seeded sample of them (sorted flat indices: the same for every map and every
+    run of the same shape, whatever the results).  finite.npy holds 1.0 where every map is finite at a position, else 0.0;
+    <name>.npy holds the map's values at the positions where finite.npy is 1.0, in order.  Spaxels without a valid sample
+    have NaN maps (as in the reference): they are recorded by their pattern, never by a fill value.  Two builds compare
+    output for output at any size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    maps = {k: np.asarray(v, dtype=np.float64).reshape(-1) for k, v in maps.items()}
+    n = next(iter(maps.values())).size
+    keep = min(n, DUMP_BUDGET // (8 * len(maps) + 4))
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+    finite = np.logical_and.reduce([np.isfinite(v[idx]) for v in maps.values()])
+    np.save(os.path.join(dirname, "finite.npy"), finite.astype(np.float32))
+    for k, v in maps.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v[idx][finite]))
 
 
 class Workload:
@@ -361,6 +403,25 @@ def iter_records(detail):
                 yield r
 
 
+def contract_keys(detail):
+    """the keys every result line starts with: the headline figure, how it was timed and the workload"""
+    h = detail["headline"]
+    return {"metric": METRIC, "value": sig(h["value"], 7), "unit": "Mvoxel/s", "n_gpus": detail["n_gpus"], "steps": detail["steps"],
+            "warmup": detail["warmup"], "ms_per_step": sig(h["ms_per_step"]), "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": h["config"]}
+
+
+def plain_line(detail):
+    """the line of a run without --full: the contract's keys, the workload and, at N > 1, the per-call latencies of the two
+    call forms `value` is picked from"""
+    line = contract_keys(detail)
+    keep = ("latency_ms", "latency_unoverlapped_ms", "latency_chunked_ms", "chunks")
+    if detail.get("per_call"):
+        line["per_call"] = {k: sig(v) for k, v in detail["per_call"].items() if k in keep}
+    line["full"] = False
+    return line
+
+
 def compact_line(detail):
     """The ONE stdout line from the full record: the contract's keys, `roofline` of the headline kernel, `cpu_baseline`,
     the configs[1] scalars and one [kernel_ms, frac, traffic / algorithmic] row per record under its short key.  Never
@@ -385,12 +446,9 @@ def compact_line(detail):
                             "max_scaled_err": sig(max(c1["verify"]["max_scaled_err_m0_m1_m2"]), 3)}
     elif isinstance(c1, dict):
         roof["configs1"] = c1
-    line = {"metric": METRIC, "value": sig(h["value"], 7), "unit": "Mvoxel/s", "n_gpus": detail["n_gpus"], "steps": detail["steps"],
-            "warmup": detail["warmup"], "ms_per_step": sig(h["ms_per_step"]), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": h["config"], "roofline": roof,
-            "cpu_baseline": detail.get("cpu_baseline"),
-            "verify": h.get("verify_compact"), "records_file": detail.get("records_file"),
-            "records_columns": ["kernel_ms", "frac_of_8TBps", "traffic_over_algorithmic"]}
+    line = dict(contract_keys(detail), roofline=roof, cpu_baseline=detail.get("cpu_baseline"),
+                verify=h.get("verify_compact"), records_file=detail.get("records_file"),
+                records_columns=["kernel_ms", "frac_of_8TBps", "traffic_over_algorithmic"])
     if detail.get("per_call"):
         line["per_call"] = {k: sig(v) for k, v in detail["per_call"].items()}
     rows = {}
@@ -443,6 +501,30 @@ def fit_shape(shape, device):
     return (nz, ny, nx)
 
 
+def single_config(shape, want, mask_valid_fraction, device):
+    from spectral_cube_amd.device import device_info
+    fitted = "" if shape == want else " (the %dx%dx%d cube does not fit this device's free HBM)" % want
+    return {"workload": "north star: %dx%dx%d fp32 cube + uint8 boolean mask resident on ONE GPU%s, fused moment0+moment1+moment2 "
+                        "(one kernel launch, three float64 maps)" % (shape + (fitted,)),
+            "input_dtype": "f32 cube + u8 mask, sums carried in f64, f64 maps out", "arithmetic": ARITH_MOMENTS,
+            "mask_valid_fraction": sig(mask_valid_fraction, 4), "stitch": "none", "sharding": "none",
+            "data_note": "device-tiled synthetic data: one seeded 16-row host tile repeated along y",
+            "device": device_info(device)["name"] or device_info(device)["arch"]}
+
+
+def run_plain(args, device):
+    """N = 1 without --full: the headline's timed steps and nothing else"""
+    import numpy as np
+    want = tuple(args.shape)
+    shape = fit_shape(want, device)
+    wl, out, tile, tmask, elapsed = timed_headline(shape, device, args)
+    nz, ny, nx = shape
+    frac = float(np.count_nonzero(tmask)) / tmask.size
+    h = {"value": nz * ny * nx * args.steps / elapsed / 1e6, "unit": "Mvoxel/s", "ms_per_step": elapsed / args.steps * 1e3,
+         "config": single_config(shape, want, frac, device)}
+    return {"n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "headline": h}
+
+
 def run_single(args, device):
     import gc
     import numpy as np
@@ -453,13 +535,7 @@ def run_single(args, device):
     detail = {"n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "records_file": os.path.basename(args.records_file)}
     # ---- headline: the north-star cube on this one GPU --------------------------------------------
     h = headline_record(shape, device, args)
-    fitted = "" if shape == want else " (the %dx%dx%d cube does not fit this device's free HBM)" % want
-    h["config"] = {"workload": "north star: %dx%dx%d fp32 cube + uint8 boolean mask resident on ONE GPU%s, fused moment0+moment1+moment2 "
-                               "(one kernel launch, three float64 maps)" % (shape + (fitted,)),
-                   "input_dtype": "f32 cube + u8 mask, sums carried in f64, f64 maps out", "arithmetic": ARITH_MOMENTS,
-                   "mask_valid_fraction": sig(h["mask_valid_fraction"], 4), "stitch": "none", "sharding": "none",
-                   "data_note": "device-tiled synthetic data: one seeded 16-row host tile repeated along y",
-                   "device": device_info(device)["name"] or device_info(device)["arch"]}
+    h["config"] = single_config(shape, want, h["mask_valid_fraction"], device)
     detail["headline"] = h
     # ---- BASELINE.json configs[1] + the SURVEY 8(f) rows on the same resident cube ---------------------
     if not args.no_configs1:
@@ -495,13 +571,11 @@ def run_single(args, device):
     return detail
 
 
-def headline_record(shape, device, args):
+def timed_headline(shape, device, args):
     """the fixed cube on one GPU: K launches between barriers (wall clock) = `value`, the same measurement the N > 1 lines
-    make; the kernel alone by HIP events on its stream = `roofline`; the first rows against the oracle"""
-    import gc
+    make; the maps of the last step to --dump-outputs.  Returns (workload, its maps, host tile, tile mask, seconds)."""
     from spectral_cube_amd import synth
-    from spectral_cube_amd.device import pool_trim, synchronize
-    import numpy as np
+    from spectral_cube_amd.device import synchronize
     cube, maskd, tile, tmask = tiled_strip_on_device(shape, synth.SEEDS["C4"], device)
     wl = Workload(cube, maskd, device)
     out = wl.outputs()
@@ -517,6 +591,18 @@ def headline_record(shape, device, args):
         wl.launch(out)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: out[k].get() for k in ("m0", "m1", "m2")})
+    return wl, out, tile, tmask, elapsed
+
+
+def headline_record(shape, device, args):
+    """the timed steps (timed_headline); the kernel alone by HIP events on its stream = `roofline`; the first rows against
+    the oracle"""
+    import gc
+    from spectral_cube_amd.device import pool_trim
+    import numpy as np
+    wl, out, tile, tmask, elapsed = timed_headline(shape, device, args)
     k_ms = wl.kernel_ms(out, min(20, max(10, args.steps)))
     verify = wl.verify([out[k].get() for k in ("m0", "m1", "m2")], tile, tmask, 4)
     nz, ny, nx = shape
@@ -528,7 +614,7 @@ def headline_record(shape, device, args):
                               "max_scaled_err": sig(max(verify["max_scaled_err_m0_m1_m2"]), 3), "tolerance": 1e-5,
                               "nan_pattern": verify["nan_pattern"]},
            "target_frac": 0.60}
-    del wl, out, cube, maskd
+    del wl, out
     gc.collect()
     pool_trim(device)
     if not getattr(args, "no_strip_terms", False):
@@ -1252,6 +1338,24 @@ def rccl_self_check(comm, device, rdv, init_ms, stitch_bytes):
     return {"init_ms": init_ms, "checksum_ok": True, "allgather_ms_at_stitch_size": float(ms), "stitch_bytes_per_rank": int(stitch_bytes)}
 
 
+def sharded_config(shape, world, rows, nchunks, stitch, mask_valid_fraction, device):
+    """the workload of the N > 1 line; nchunks = 0: the call form that set `value` is kernel then stitch"""
+    from spectral_cube_amd.device import device_info
+    NZ, NY, NX = tuple(shape)
+    return {"workload": "north star: fixed %dx%dx%d fp32 cube + uint8 mask sharded by row strips over %d GPUs "
+                        "(%d rows each), fused moment0+1+2 per strip + the all-gather stitching the three "
+                        "float64 maps on every rank; ONE call at a time%s" % (
+                            NZ, NY, NX, world, rows,
+                            (" - the rank's rows in %d blocks (block-cyclic ownership), the all-gather of a block's maps "
+                             "under the kernel of the next block, nothing carried across calls" % nchunks) if nchunks
+                            else ", kernel then stitch, nothing overlapped"),
+            "input_dtype": "f32 cube + u8 mask, sums carried in f64, f64 maps out", "arithmetic": ARITH_MOMENTS,
+            "mask_valid_fraction": sig(mask_valid_fraction, 4), "stitch": stitch,
+            "sharding": "row strips (nz, %d, nx) of a %dx%dx%d cube" % (rows, NZ, NY, NX),
+            "allgather_bytes_per_rank": 3 * rows * NX * 8,
+            "device": device_info(device)["name"] or device_info(device)["arch"]}
+
+
 def run_sharded(args, device, rdv):
     import numpy as np
     from spectral_cube_amd import synth
@@ -1283,7 +1387,7 @@ def run_sharded(args, device, rdv):
     from spectral_cube_amd import _lib as _spclib
     require_device_stitch(stitch, int(os.environ.get("LOCAL_WORLD_SIZE", world)), _spclib.device_count(), rank)
     self_check = None
-    if stitch == "rccl":
+    if stitch == "rccl" and args.full:
         self_check = rccl_self_check(comm, device, rdv, (time.perf_counter() - t_init) * 1e3, 3 * rows * NX * 8)
 
     # send buffer = the rank's three map strips back to back; receive buffer (world, 3, rows, NX):
@@ -1326,14 +1430,35 @@ def run_sharded(args, device, rdv):
     # (1b) the same ONE call with the stitch hidden inside it (distributed.ChunkedMoments): the rank's rows in 2 - 4 blocks,
     # the all-gather of a block's three maps on a second stream under the kernel of the next block.  Nothing is carried
     # across calls: a call starts when the previous one has completed.  Needs the device all-gather.
-    chunked, elapsed_chunked = None, None
+    chunked, elapsed_chunked, chunked_maps = None, None, [None]
     from spectral_cube_amd.distributed import ChunkedMoments
     if stitch == "rccl" and ChunkedMoments.pick_chunks(rows) > 1:
         chunked = ChunkedMoments(cube, maskd, wl.d_cen, 500.0, wl.cref + wl.v[0], comm, workspace=wl.ws)   # blocks of >= 128 rows
 
         def step_chunked(i):
-            chunked(wl.stream, comm_stream)
+            chunked_maps[0] = chunked(wl.stream, comm_stream)
         elapsed_chunked = timed(step_chunked)
+
+    # the contract's value: ONE call at a time; with the device all-gather the call hides its stitch under its own
+    # kernel (chunked), otherwise kernel then stitch
+    best = elapsed if elapsed_chunked is None else min(elapsed, elapsed_chunked)
+    if args.dump_outputs and rank == 0:                     # the stitched maps of the last step of the form that set `value`
+        if best != elapsed:
+            dump_outputs(args.dump_outputs, {k: chunked_maps[0][k].get() for k in ("m0", "m1", "m2")})
+        else:
+            stitched = recvs[0].get()                       # (world, 3, rows, NX): map k = [:, k] read along y
+            dump_outputs(args.dump_outputs, {k: stitched[:, i].reshape(NY, NX) for i, k in enumerate(("m0", "m1", "m2"))})
+    if not args.full:
+        vfrac = rdv.allgather_object(float(np.count_nonzero(tmask)) / tmask.size)
+        if comm is not None and stitch == "rccl":
+            comm.close()
+        nchunks = chunked.chunks if chunked is not None else 0
+        head = {"value": NZ * NY * NX * args.steps / best / 1e6, "unit": "Mvoxel/s", "ms_per_step": best / args.steps * 1e3,
+                "config": sharded_config(args.shape, world, rows, nchunks if best != elapsed else 0, stitch, float(np.mean(vfrac)), device)}
+        return {"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "headline": head,
+                "per_call": {"latency_ms": best / args.steps * 1e3, "latency_unoverlapped_ms": elapsed / args.steps * 1e3,
+                             "latency_chunked_ms": None if elapsed_chunked is None else elapsed_chunked / args.steps * 1e3,
+                             "chunks": nchunks}}
 
     # (2) pipelined: the stitch of step k on its own stream under the kernel of step k+1
     ev_kernel, ev_comm = [Event(device), Event(device)], [Event(device), Event(device)]
@@ -1402,9 +1527,6 @@ def run_sharded(args, device, rdv):
         comm.close()
 
     total = NZ * NY * NX
-    # the contract's value: ONE call at a time; with the device all-gather the call hides its stitch under its own
-    # kernel (chunked), otherwise kernel then stitch
-    best = elapsed if elapsed_chunked is None else min(elapsed, elapsed_chunked)
     nchunks = chunked.chunks if chunked is not None else 0
     call_form = ("rows in %d blocks, all-gather of a block under the kernel of the next" % nchunks) if best != elapsed else "one launch, then one all-gather"
     head = {"value": total * args.steps / best / 1e6, "unit": "Mvoxel/s", "ms_per_step": best / args.steps * 1e3,
@@ -1412,18 +1534,7 @@ def run_sharded(args, device, rdv):
             "verify_compact": {"vs": "oracle, every rank its own rows", "rows_checked": 4 * world,
                                "max_scaled_err": sig(max(max(v["max_scaled_err_m0_m1_m2"]) for v in verifies), 3), "tolerance": 1e-5,
                                "stitched_maps_identical_on_all_ranks": True},
-            "config": {"workload": "north star: fixed %dx%dx%d fp32 cube + uint8 mask sharded by row strips over %d GPUs "
-                                   "(%d rows each), fused moment0+1+2 per strip + the all-gather stitching the three "
-                                   "float64 maps on every rank; ONE call at a time%s" % (
-                                       NZ, NY, NX, world, rows,
-                                       (" - the rank's rows in %d blocks (block-cyclic ownership), the all-gather of a block's maps "
-                                        "under the kernel of the next block, nothing carried across calls" % nchunks) if best != elapsed
-                                       else ", kernel then stitch, nothing overlapped"),
-                       "input_dtype": "f32 cube + u8 mask, sums carried in f64, f64 maps out", "arithmetic": ARITH_MOMENTS,
-                       "mask_valid_fraction": sig(float(np.mean(vfrac)), 4), "stitch": stitch,
-                       "sharding": "row strips (nz, %d, nx) of a %dx%dx%d cube" % (rows, NZ, NY, NX),
-                       "allgather_bytes_per_rank": 3 * rows * NX * 8,
-                       "device": device_info(device)["name"] or device_info(device)["arch"]}}
+            "config": sharded_config(args.shape, world, rows, nchunks if best != elapsed else 0, stitch, float(np.mean(vfrac)), device)}
     detail = {"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "records_file": os.path.basename(args.records_file),
               "headline": head,
               "per_call": {"kernel_ms": k_ms_max, "allgather_ms": g_ms, "latency_ms": best / args.steps * 1e3,
@@ -1512,7 +1623,7 @@ def dry_run(args):
         print("noise before the record")
         # the line a real run of this world size prints, from canned records (the CPU test of the line's size and shape)
         detail = canned_detail(world, args)
-        line = emit(detail, os.environ.get("SPC_BENCH_DRYRUN_RECORDS", os.devnull))
+        line = emit(detail, os.environ.get("SPC_BENCH_DRYRUN_RECORDS", os.devnull)) if args.full else plain_line(detail)
         line["dryrun"] = {"gpus_arg": args.gpus, "ranks": ranks, "bcast": token.decode()}
         print(json.dumps(line), flush=True)
 
@@ -1595,10 +1706,12 @@ def main():
             detail = run_sharded(args, device, rdv)
         finally:
             rdv.close()                                     # also after a failure: no stale files for a restarted launch
-    else:
+    elif args.full:
         detail = run_single(args, device)
         detail["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(tuple(args.shape), args.cpu_seconds)
-    line = emit(detail, args.records_file) if rank == 0 else None
+    else:
+        detail = run_plain(args, device)
+    line = None if rank != 0 else emit(detail, args.records_file) if args.full else plain_line(detail)
     # whatever the native libraries still hold in the C stdio buffer (RCCL prints a version banner at init) goes out first:
     # the JSON line is the last line of stdout
     try:

@@ -211,7 +211,7 @@ def test_bench_launches_its_own_ranks():
     WORLD_SIZE in their environment), the ranks meet through the file rendezvous, rank 0's JSON record is the LAST
     line of the parent's stdout, exit status 0.  (SPC_BENCH_DRYRUN=1: everything but the GPU work.)"""
     import json
-    p = _bench(["--gpus", "4", "--steps", "3"], SPC_BENCH_DRYRUN="1")
+    p = _bench(["--gpus", "4", "--steps", "3", "--full"], SPC_BENCH_DRYRUN="1")
     assert p.returncode == 0, p.stderr
     last = p.stdout.strip().splitlines()[-1]
     rec = json.loads(last)
@@ -273,12 +273,78 @@ def test_bench_line_is_small_and_round_trips(tmp_path):
 def test_bench_eight_rank_dry_run_line():
     """an 8-rank launch of the spawner (no GPU work): rank 0's last stdout line satisfies the same size bound"""
     import json
-    p = _bench(["--gpus", "8", "--steps", "2"], SPC_BENCH_DRYRUN="1")
+    p = _bench(["--gpus", "8", "--steps", "2", "--full"], SPC_BENCH_DRYRUN="1")
     assert p.returncode == 0, p.stderr
     last = p.stdout.strip().splitlines()[-1]
     rec = json.loads(last)
     assert rec["n_gpus"] == 8 and len(rec["dryrun"]["ranks"]) == 8 and "per_call" in rec
     _check_line(rec, last)
+
+
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config")
+
+
+@pytest.mark.parametrize("gpus", [1, 4])
+def test_bench_plain_line_holds_the_contract_keys_and_nothing_measured_besides(gpus):
+    """a run without --full prints the contract's keys with the meaning of the --full line (the same metric, unit, dtype,
+    ms_per_step of the timed steps) and none of the secondary measurements or checks"""
+    import json
+    sys.path.insert(0, REPO)
+    import bench
+    p = _bench(["--gpus", str(gpus), "--steps", "7", "--warmup", "2"], SPC_BENCH_DRYRUN="1")
+    assert p.returncode == 0, p.stderr
+    rec = json.loads(p.stdout.strip().splitlines()[-1])
+    full = bench.compact_line(bench.canned_detail(gpus, bench.parse(["--steps", "7", "--warmup", "2", "--full"])))
+    for k in PLAIN_KEYS:
+        assert rec[k] == full[k], k
+    assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["full"] is False and rec["higher_is_better"] is True
+    for k in ("roofline", "cpu_baseline", "verify", "records", "records_file"):
+        assert k not in rec, k
+    assert (gpus > 1) == ("per_call" in rec) and "pipelined_ms_per_step" not in rec.get("per_call", {})
+
+
+def test_bench_steps_must_be_positive():
+    p = _bench(["--gpus", "1", "--steps", "0"])
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: every file finite; finite.npy = where all maps are finite at the dumped positions (all spaxels, or
+    ONE seeded sample of them when the maps exceed the budget: the same positions whatever the results), <name>.npy (float64)
+    = the map's values there; the same files from run to run, within 64 MB"""
+    sys.path.insert(0, REPO)
+    import bench
+    names = ("m0", "m1", "m2")
+
+    def load(d):
+        return {k: np.load(str(tmp_path / d / (k + ".npy"))) for k in names + ("finite",)}
+    rng = np.random.default_rng(3)
+    small = {k: rng.standard_normal((5, 7)).astype(np.float32) for k in names}
+    small["m0"][1, 2], small["m2"][4, 6], small["m1"][0, 0] = np.nan, np.inf, np.nan
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    got = load("s")
+    ok = np.isfinite(small["m0"]) & np.isfinite(small["m1"]) & np.isfinite(small["m2"])
+    assert got["finite"].dtype == np.float32 and np.array_equal(got["finite"], ok.reshape(-1).astype(np.float32))
+    for k in names:
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], small[k][ok].astype(np.float64))
+    ny = nx = 2048
+    big = {k: np.arange(ny * nx, dtype=np.float64).reshape(ny, nx) * (i + 1) for i, k in enumerate(names)}
+    holes = np.random.default_rng(5).choice(ny * nx, size=ny * nx // 10, replace=False)
+    big["m1"].reshape(-1)[holes] = np.nan
+    for d, maps in (("a", big), ("b", big), ("c", {k: np.zeros((ny, nx)) for k in names})):
+        bench.dump_outputs(str(tmp_path / d), maps)
+    a, b, c = load("a"), load("b"), load("c")
+    total = sum((tmp_path / "a" / (k + ".npy")).stat().st_size for k in names + ("finite",))
+    assert total <= 64 * 10**6 and a["finite"].size == bench.DUMP_BUDGET // 28
+    assert 0.85 < a["finite"].mean() < 0.95 and c["finite"].min() == 1.0
+    for k in names + ("finite",):
+        assert np.all(np.isfinite(a[k])) and np.array_equal(a[k], b[k]), k
+    pos = a["m0"]                                            # m0 = the flat index: the sampled positions, sorted
+    assert np.all(np.diff(pos) > 0) and pos[-1] < ny * nx and np.isnan(big["m1"].reshape(-1)[pos.astype(np.int64)]).sum() == 0
+    for i, k in enumerate(names):
+        assert np.array_equal(a[k], pos * (i + 1)), "the same spaxels in every map"
+    assert c["m0"].size == a["finite"].size and int(a["finite"].sum()) == pos.size
 
 
 def test_chunked_moments_picks_blocks_from_the_strip_height():
@@ -297,7 +363,8 @@ def test_bench_launch_fails_when_a_rank_fails():
 
 
 def test_bench_without_gpu_fails_loudly_not_silently():
-    p = _bench(["--gpus", "1", "--steps", "1", "--no-configs1", "--no-cpu-baseline"])
+    # the benchmark's process sees no device on any machine, a GPU machine included
+    p = _bench(["--gpus", "1", "--steps", "1", "--no-configs1", "--no-cpu-baseline"], HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     assert p.returncode != 0 and "no HIP device" in p.stderr and not p.stdout.strip()
 
 

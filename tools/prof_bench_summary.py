@@ -33,7 +33,7 @@ for f in glob.glob(os.path.join(O, "stats", "*", "*kernel_trace.csv")):
         groups[(norm(r["Kernel_Name"]), grid_of(r))].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 rows = sorted(((sum(v), k, v) for k, v in groups.items()), reverse=True)
 with open(os.path.join(O, "bench_kernel_stats_by_workload.csv"), "w") as fh:
-    fh.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline: durations from the\n"
+    fh.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline: durations from the\n"
              "# kernel trace, grouped by (kernel, grid threads) = by workload; warm-up and verification launches included\n")
     fh.write("kernel,grid_threads,calls,median_ns,average_ns,min_ns,max_ns,total_ms\n")
     for tot, (name, grid), v in rows:
@@ -185,8 +185,8 @@ try:
 except OSError:
     head = None
 json.dump({"library_sha256": lib_sha, "git_head_when_summarised": head,
-           "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-strip-terms; "
-                      "records matched to (kernel, grid) groups of `rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline`",
+           "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-strip-terms; "
+                      "records matched to (kernel, grid) groups of `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline`",
            "note": "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B); WRITE_SIZE used as reported",
            "records": out}, open(os.path.join(O, "pmc_traffic_by_record.json"), "w"), indent=1)
 print("%d of %d records have PMC traffic" % (len(out), len(records)))
