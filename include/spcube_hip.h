@@ -300,6 +300,35 @@ int spc_narrow_f64_to_f32(int device, void* stream, const spc_cube_f64* cube, fl
 int spc_mask_include_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask,
                          int nan_excluded, uint8_t* d_out);
 
+/* ---- block downsampling along one axis (SpectralCube.downsample_axis, spectral_cube.py:3421-3557) ----
+ * The in-memory form (use_memmap=False, :3466-3497) in one pass: along `axis` (0 = spectral, 1 = y, 2 = x) every run of
+ * `factor` samples of the FILLED data (masked voxels -> fill) becomes one output sample, estimator(run), and one mask
+ * byte, any(include) over the run's real voxels (:3491-3495).  A last run shorter than `factor` is dropped when
+ * truncate != 0 (:3468-3473), otherwise it is padded with NaN as the reference pads it (:3474-3480): the nan-estimators
+ * skip the padding, SPC_DS_MEAN / SUM / MAX / MIN give NaN for that run.  Output length ceil(n / factor), or
+ * floor(n / factor) when truncating (at least one, else SPC_ERR_INVALID).
+ * Sums are carried in float64 with an integer count and rounded once to the sample type (nanmean = sum / count, NaN
+ * when the count is 0; nansum of nothing = 0); extrema are compared in the sample type; the non-nan estimators return
+ * NaN when any sample of the run is NaN.
+ * nan_excluded != 0: a NaN sample counts as excluded whatever the mask terms say - what a ~isnan mask of the cube's own
+ * data means (NotNaNMask, the mask spectral_interpolate attaches, lowers to no term: a reduction skips NaN anyway, but
+ * here excluded voxels become `fill` and drop out of the include map).
+ * d_out: the output view, strides in elements (0 = C-contiguous), so that strips of a larger output are written in
+ * place; d_out_mask (uint8, 1 = included; may be NULL) has the same strides.  Every input byte is read once, with 16-byte
+ * loads (4-byte for the mask array) when every input row and plane starts 16-byte aligned - for axes 0 / 1 the outputs'
+ * rows and planes as well, for axis 2 with factor > 512 a factor that is a multiple of 4 samples - and with one load
+ * per sample otherwise (e.g. float32 rows with nx % 4 != 0).  No workspace. */
+typedef enum {
+    SPC_DS_NANMEAN = 0, SPC_DS_NANSUM = 1, SPC_DS_NANMAX = 2, SPC_DS_NANMIN = 3,
+    SPC_DS_MEAN = 4, SPC_DS_SUM = 5, SPC_DS_MAX = 6, SPC_DS_MIN = 7
+} spc_ds_estimator;
+int spc_downsample_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
+                       float fill, int axis, int64_t factor, int truncate, int estimator,
+                       float* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask);
+int spc_downsample_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
+                       double fill, int axis, int64_t factor, int truncate, int estimator,
+                       double* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

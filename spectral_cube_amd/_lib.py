@@ -28,6 +28,8 @@ MAP_MUL, MAP_SECOND_MOMENT_SUM, MAP_DIV_ADD, MAP_DIV_SUB_SQ = 0, 1, 2, 3
 (WS_MOMENTS, WS_SPECTRAL_CONV, WS_SPECTRAL_CONV_MOMENTS, WS_SPATIAL_CONV_SEP, WS_SPATIAL_CONV2D, WS_RESAMPLE_BILINEAR,
  WS_STATS_GLOBAL, WS_STATS_PLANES, WS_MAP_CONV2D, WS_CLIP_OUTSIDE, WS_PERCENTILE_GLOBAL, WS_SPATIAL_CONV_MFMA, WS_SIGMA_CLIP,
  WS_RESAMPLE_BILINEAR_LERP, WS_STATS_GLOBAL_F64, WS_SPECTRAL_CONV_F64, WS_SPATIAL_CONV_F64) = range(17)
+# spc_ds_estimator (spc_downsample_f32 / _f64)
+DS_NANMEAN, DS_NANSUM, DS_NANMAX, DS_NANMIN, DS_MEAN, DS_SUM, DS_MAX, DS_MIN = range(8)
 
 
 class HipLibraryError(RuntimeError):
@@ -158,6 +160,8 @@ SIGNATURES = {
     "spc_sigma_clip_axis0_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _d, _d, _i, _i, _i, _vp]),
     "spc_narrow_f64_to_f32": (_i, [_i, _vp, _P(SpcCube), _vp, _i64, _i64]),
     "spc_mask_include_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
+    "spc_downsample_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i64, _i, _i, _vp, _i64, _i64, _vp]),
+    "spc_downsample_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i64, _i, _i, _vp, _i64, _i64, _vp]),
     "spc_moments_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _d, _vp, _vp, _vp]),
     "spc_moment_order_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i, _vp, _vp]),
     "spc_spectral_conv_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _i, _vp, _i64, _i64, _vp, _sz]),

@@ -190,6 +190,71 @@ def _unit_pow(a, n):
     return "(%s)%d" % (a, n) if " " in a or "/" in a else "%s%d" % (a, n)
 
 
+# downsample_axis estimators, recognised by identity (np.max is np.amax, np.min is np.amin)
+_DS_ESTIMATORS = ((np.nanmean, _lib.DS_NANMEAN), (np.nansum, _lib.DS_NANSUM), (np.nanmax, _lib.DS_NANMAX),
+                  (np.nanmin, _lib.DS_NANMIN), (np.mean, _lib.DS_MEAN), (np.sum, _lib.DS_SUM), (np.max, _lib.DS_MAX),
+                  (np.amax, _lib.DS_MAX), (np.min, _lib.DS_MIN), (np.amin, _lib.DS_MIN))
+
+
+def _ds_estimator(estimator):
+    for fn, code in _DS_ESTIMATORS:
+        if estimator is fn:
+            return code
+    raise NotImplementedError("downsample_axis estimator %r is not built: np.nanmean, np.nansum, np.nanmax, np.nanmin, "
+                              "np.mean, np.sum, np.max (np.amax), np.min (np.amin)" % (getattr(estimator, "__name__", estimator),))
+
+
+def _nan_term_dropped(cube, view):
+    """True when the cube's mask goes to the kernels as device terms (``_device_terms(view)``, *view* what it is lowered
+    against) and names ~isnan of the cube's own data.  That term lowers to nothing (NotNaNMask: a reduction skips NaN
+    anyway), so an operator that fills excluded voxels or reports the include map must exclude NaN samples itself - as
+    reproject and streaming.original_include do"""
+    m = cube._mask
+    return (m is not None and not isinstance(m, M.DeviceBooleanMask) and M.contains(m, M.NotNaNMask)
+            and m._device_terms(view) is not None)
+
+
+def _check_downsample_fits(cube, shape):
+    """the downsampled result of a streamed cube is made resident: its data + mask must fit the HBM budget"""
+    from . import streaming
+    need = 5 * int(np.prod(shape, dtype=np.int64))
+    budget = streaming.hbm_budget(cube.device)
+    if need > budget:
+        raise streaming.HugeCubeError(
+            "downsample_axis of an out-of-core cube keeps its result in HBM: the result (data + mask) takes %d bytes "
+            "(%.2f GiB) against a budget of %d bytes (%.2f GiB, SPC_HBM_BUDGET); use a larger factor"
+            % (need, need / 2**30, budget, budget / 2**30))
+    return need, budget
+
+
+def _downsample_streamed(cube, axis, factor, truncate, est, fill, shape):
+    """ops.downsample of a cube larger than the HBM budget into a resident result: along the spectral axis strip by strip
+    (every spaxel whole), along y or x slab by slab (every image plane whole); the kernel writes each part in place"""
+    from . import streaming
+    from .device import Stream
+    need, budget = _check_downsample_fits(cube, shape)
+    data = DeviceArray(shape, np.float32, cube.device)
+    inc = DeviceArray(shape, np.uint8, cube.device)
+    src = cube._stream_source()
+    terms = streaming._mask_terms(cube)
+    has_arr = terms is not None and terms[3] is not None
+    nan_ex = _nan_term_dropped(cube, cube)
+    left = max(budget - need, 1)
+    compute = Stream(cube.device)
+    if axis == 0:
+        rows = streaming.plan_rows(src.shape, left, mask_array=has_arr, max_strip_mb=getattr(src, "max_strip_mb", 0))
+        for y0, y1, dev, mspec in streaming.Strips(cube, compute, rows):
+            ops.downsample(dev, 0, factor, truncate, est, fill, mask=mspec, out=data.rows(y0, y1), out_mask=inc.rows(y0, y1),
+                           stream=compute, nan_excluded=nan_ex)
+    else:
+        planes = streaming.plan_planes(src.shape, left, mask_array=has_arr, out_factor=0.0)
+        for z0, z1, dev, mspec in streaming.Strips(cube, compute, planes, axis=0):
+            ops.downsample(dev, axis, factor, truncate, est, fill, mask=mspec, out=data.planes(z0, z1), out_mask=inc.planes(z0, z1),
+                           stream=compute, nan_excluded=nan_ex)
+    compute.synchronize()
+    return data, inc
+
+
 class Projection(np.ndarray):
     """2-D result map (stands in for lower_dimensional_structures.Projection
     :246-292): an ndarray carrying unit, wcs and meta."""
@@ -694,7 +759,9 @@ class SpectralCube:
         """the mask lowered for the float64 kernels: thresholds in float64, host-evaluated terms on the float64 samples"""
         if self._mask64_cache is None:
             owner = M.foreign_owner(self._mask) if self._mask is not None else None
-            if (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
+            if isinstance(self._mask, M.DeviceBooleanMask) and tuple(self._mask.shape) == tuple(self._shape):
+                self._mask64_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, self._mask.device_array())
+            elif (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
                     and getattr(owner, "_wide_resident", lambda: False)() and self._mask._device_terms(_WideView(owner)) is not None):
                 # every lazy term belongs to ANOTHER float64 cube's data (a smoothed cube keeps its parent's mask):
                 # evaluated there, on the device, on the float64 samples (as _mask_spec does for float32 cubes)
@@ -740,7 +807,10 @@ class SpectralCube:
         """lower the mask tree once and keep the uint8 array resident in HBM."""
         if self._mask_cache is None:
             owner = M.foreign_owner(self._mask) if self._mask is not None else None
-            if (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
+            if isinstance(self._mask, M.DeviceBooleanMask) and tuple(self._mask.shape) == tuple(self._shape):
+                # computed on the device (downsample_axis): the kernels read its uint8 array where it is
+                self._mask_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, self._mask.device_array())
+            elif (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
                     and self._mask._device_terms(owner) is not None):
                 # every lazy term belongs to ANOTHER cube's data (a smoothed cube keeps its parent's mask):
                 # evaluate it there, on the device - no host copy of either cube
@@ -1304,6 +1374,65 @@ class SpectralCube:
             st["rms"] = float(np.sqrt(st["sumsq"] / n)) if n else np.nan
         return st
 
+    # ---- downsampling ------------------------------------------------------------------------
+    def downsample_axis(self, factor, axis, estimator=np.nanmean, truncate=False, use_memmap=True, progressbar=True):
+        """Block-downsample the cube by an integer *factor* along *axis* (spectral_cube.py:3421-3557, the in-memory form
+        ``use_memmap=False``; ``use_memmap`` / ``progressbar`` are accepted and ignored).  Every run of *factor* samples of
+        the FILLED data (masked voxels -> fill_value, NaN by default: ``with_fill_value(0)`` counts them as zeros)
+        becomes ``estimator(run)``; the new mask is a boolean array, True where any voxel of the run is included.  A
+        last run shorter than *factor* is dropped when *truncate*, otherwise padded with NaN like the reference pads it:
+        the nan-estimators skip the padding, ``np.mean`` / ``np.sum`` / ``np.max`` / ``np.min`` give NaN there.
+        The WCS follows ``wcs_utils.slice_wcs`` with a step (``SimpleWCS.downsampled``): output pixel k is the centre of
+        its parent block.
+
+        Estimators (by identity): np.nanmean (default), np.nansum, np.nanmax, np.nanmin, np.mean, np.sum, np.max /
+        np.amax, np.min / np.amin; any other raises NotImplementedError (there is no CPU path).
+
+        dtype, by design: a float32 cube gives float32 (sums and means are carried in float64 and rounded once), a
+        float64 cube float64 throughout - the reference's dtype depends on its code path (float32 unpadded, float64
+        padded or memory-mapped).
+
+        The result is pending like ``spectral_smooth``: shape, wcs and header need no device; data and mask come from
+        one kernel pass on first use, and stay in HBM.  A parent larger than the HBM budget streams through the device
+        (row strips along the spectral axis, slabs of planes along y / x) into a resident result, which must fit."""
+        if isinstance(factor, (bool, np.bool_)) or not isinstance(factor, (int, np.integer)) or factor < 1:
+            raise ValueError("factor must be an integer >= 1 (got %r)" % (factor,))
+        factor = int(factor)
+        if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)) or axis not in (0, 1, 2):
+            raise ValueError("axis must be 0, 1 or 2 (got %r)" % (axis,))
+        axis = int(axis)
+        est = _ds_estimator(estimator)
+        shape = ops.downsample_shape(self._shape, axis, factor, truncate)
+        if shape[axis] < 1:
+            raise ValueError("downsampling %d samples along axis %d by %d with truncate=True leaves an empty cube"
+                             % (self._shape[axis], axis, factor))
+        newwcs = self._wcs.downsampled(axis, factor, shape) if self._wcs is not None else None
+        parent, fill, wide = self, self._fill_value, self._runs_wide()
+        if not wide:
+            try:
+                streamed = self._stream_source() is not None
+            except _lib.HipLibraryError:
+                streamed = False
+            if streamed:
+                _check_downsample_fits(self, shape)
+
+        def run():
+            # (a ~isnan mask of the parent's own data lowers to no term: the kernel is told to exclude NaN samples, which the
+            # reference fills with fill_value and leaves out of the new mask)
+            if wide:
+                return ops.downsample_f64(parent._device_data64(), axis, factor, truncate, est, fill, mask=parent._mask_spec64(),
+                                          nan_excluded=_nan_term_dropped(parent, _WideView(parent)))
+            if parent._stream_source() is not None:
+                return _downsample_streamed(parent, axis, factor, truncate, est, fill, shape)
+            return ops.downsample(parent._device_data(), axis, factor, truncate, est, fill, mask=parent._mask_spec(),
+                                  nan_excluded=_nan_term_dropped(parent, parent))
+
+        result = _Once(run)
+        mask = M.DeviceBooleanMask(lambda: result()[1], wcs=newwcs, shape=shape)
+        if wide:
+            return self._new_wide_cube(lambda: result()[0], shape=shape, wcs=newwcs, mask=mask)
+        return self._new_cube_with(lazy=_Thunk(lambda: result()[0]), shape=shape, wcs=newwcs, mask=mask)
+
     # ---- smoothing ---------------------------------------------------------------------------
     def spectral_smooth(self, kernel, convolve=None, **kwargs):
         """Smooth along the spectral axis; the mask is left unchanged
@@ -1798,6 +1927,14 @@ class VaryingResolutionSpectralCube(SpectralCube):
             new._goodbeams_mask = np.asarray(goodbeams_mask, dtype=bool)
         return new
 
+    def downsample_axis(self, factor, axis, estimator=np.nanmean, truncate=False, use_memmap=True, progressbar=True):
+        """spatial axes as SpectralCube.downsample_axis (the beams table is kept); along the spectral axis the beams of a
+        run cannot be averaged: NotImplementedError"""
+        if not isinstance(axis, (bool, np.bool_)) and isinstance(axis, (int, np.integer)) and axis == 0:
+            raise NotImplementedError("downsampling the spectral axis of a VaryingResolutionSpectralCube would have to average "
+                                      "the channels' beams: bring the cube to one beam with convolve_to() first")
+        return SpectralCube.downsample_axis(self, factor, axis, estimator=estimator, truncate=truncate)
+
     def _new_cube_with(self, **kw):
         new = SpectralCube._new_cube_with(self, **kw)
         if new._shape[0] == len(self._beams):
@@ -1928,3 +2065,17 @@ class _Thunk:
 
     def __call__(self):
         return self._fn()
+
+
+class _Once:
+    """fn() run once, its result kept (the one kernel pass behind a downsampled cube's data AND mask)"""
+
+    def __init__(self, fn):
+        self._fn, self._res = fn, None
+
+    def __call__(self):
+        if self._fn is not None:
+            _lib.require_gpu()
+            self._res = self._fn()
+            self._fn = None
+        return self._res

@@ -128,6 +128,31 @@ class BooleanArrayMask(MaskBase):
         return (0, -np.inf, np.inf, m)
 
 
+class DeviceBooleanMask(BooleanArrayMask):
+    """A BooleanArrayMask whose array lives in HBM as uint8 (1 = include): the mask of a cube computed on the device
+    (downsample_axis).  *source* is the DeviceArray, or a callable that produces it on first use.  Kernels take the
+    device array as it is (cube._mask_spec); the host copy is made only when ``include()`` / ``exclude()`` or a host
+    composition asks for it."""
+
+    def __init__(self, source, wcs=None, shape=None):
+        self._source = source
+        self._host = None
+        self._wcs = wcs
+        self._include_flag = True
+        self._shape = tuple(shape) if shape is not None else tuple(source.shape)
+
+    def device_array(self):
+        if callable(self._source):
+            self._source = self._source()
+        return self._source
+
+    @property
+    def _mask(self):
+        if self._host is None:
+            self._host = self.device_array().get().view(bool)
+        return self._host
+
+
 class LazyMask(MaskBase):
     """mask = function(data), evaluated lazily on the data it was created for
     (masks.py:586-668).  ``np.isfinite`` lowers to SPC_MASK_FINITE."""

@@ -464,6 +464,58 @@ def spectral_conv(cube, kernel1d, mask=None, out=None, stream=None):
     return out
 
 
+def downsample_shape(shape, axis, factor, truncate):
+    """shape of the downsampled cube: ceil(n / factor) along *axis*, floor(n / factor) when truncating
+    (spectral_cube.py:3511-3513)"""
+    out = list(shape)
+    n = int(shape[axis])
+    out[axis] = n // factor if truncate else -(-n // factor)
+    return tuple(out)
+
+
+def _strides(arr):
+    return getattr(arr, "row_stride", 0), getattr(arr, "plane_stride", 0)
+
+
+def _downsample_outputs(cube, axis, factor, truncate, dtype, out, out_mask):
+    shape = downsample_shape(cube.shape, axis, factor, truncate)
+    if out is None:
+        out = DeviceArray(shape, dtype, cube.device)
+    if out_mask is None:
+        out_mask = DeviceArray(shape, np.uint8, cube.device)
+    if tuple(out.shape) != shape or out.dtype != np.dtype(dtype) or tuple(out_mask.shape) != shape or out_mask.dtype != np.uint8:
+        raise ValueError("preallocated outputs must be %s %s and %s uint8" % (shape, np.dtype(dtype), shape))
+    if _strides(out) != _strides(out_mask):
+        raise ValueError("out and out_mask must have the same strides")
+    return out, out_mask
+
+
+def downsample(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fill=np.nan, mask=None, out=None, out_mask=None,
+               stream=None, nan_excluded=False):
+    """(data, include) of the cube block-downsampled along *axis* = SpectralCube.downsample_axis's in-memory form
+    (spectral_cube.py:3466-3497): estimator (an SPC_DS_* code) over every run of *factor* filled samples, and any(include)
+    over the run's voxels, as a float32 and a uint8 DeviceArray.  *out* / *out_mask* may be strided views (rows() /
+    planes()) of larger outputs: a strip is written in place.  *nan_excluded*: NaN samples count as excluded (the
+    ~isnan mask of the cube's own data, which lowers to no MaskSpec term)."""
+    out, out_mask = _downsample_outputs(cube, axis, factor, truncate, np.float32, out, out_mask)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    ors, ops_ = _strides(out)
+    _lib.call("spc_downsample_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+              int(axis), int(factor), 1 if truncate else 0, int(estimator), C.c_void_p(out.ptr), ors, ops_, C.c_void_p(out_mask.ptr))
+    return out, out_mask
+
+
+def downsample_f64(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fill=np.nan, mask=None, out=None, out_mask=None,
+                   stream=None, nan_excluded=False):
+    """downsample of a float64 cube: float64 in, float64 out"""
+    out, out_mask = _downsample_outputs(cube, axis, factor, truncate, np.float64, out, out_mask)
+    c, m = _cube_c64(cube), _mask_c64(mask, cube)
+    ors, ops_ = _strides(out)
+    _lib.call("spc_downsample_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+              int(axis), int(factor), 1 if truncate else 0, int(estimator), C.c_void_p(out.ptr), ors, ops_, C.c_void_p(out_mask.ptr))
+    return out, out_mask
+
+
 def spectral_conv_moments(cube, kernel1d, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL,
                           stream=None, out=None, cen_host=None):
     """fused spectral_smooth -> moment (smoothed cube never written).

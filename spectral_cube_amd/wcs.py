@@ -563,6 +563,40 @@ class SimpleWCS:
             out.header["CUNIT3"] = cunit
         return out
 
+    def downsampled(self, axis, factor, shape=None):
+        """The WCS of a cube block-downsampled by *factor* along numpy *axis* (0 = spectral): the step branch of
+        ``wcs_utils.slice_wcs`` (wcs_utils.py:309-332), crpix' = (crpix - 0.5) / factor + 0.5 and the pixel axis
+        ``factor`` times longer, so that output pixel k sits at the centre of its parent block, parent pixel
+        k * factor + (factor - 1) / 2.  The longer pixel axis is CDELT * factor where the axis has a column of its own (as
+        the reference does); a CD matrix, or a PC matrix that mixes the axis into others, gets that column scaled instead
+        (CDELT would scale a world row, which moves the block centres).  *shape* (numpy order) sets NAXISn.  SIP
+        distortion on a downsampled celestial axis: NotImplementedError."""
+        n = self.naxis
+        i = n - 1 - int(axis)                   # 0-based FITS axis
+        if i < 2 and self.sip_a is not None:
+            raise NotImplementedError("downsampling a celestial axis of a WCS with SIP distortion is not built (the "
+                                      "polynomial coefficients would have to be rescaled)")
+        h, k = dict(self.header), i + 1
+        f = float(factor)
+        h["CRPIX%d" % k] = (float(h.get("CRPIX%d" % k, 0.0)) - 0.5) / f + 0.5
+        has_pc = any(("PC%d_%d" % (a + 1, b + 1)) in h or ("PC%03d%03d" % (a + 1, b + 1)) in h for a in range(n) for b in range(n))
+        has_cd = any(("CD%d_%d" % (a + 1, b + 1)) in h for a in range(n) for b in range(n))
+        if has_cd and not has_pc:
+            for a in range(n):
+                key = "CD%d_%d" % (a + 1, k)
+                if key in h:
+                    h[key] = float(h[key]) * f
+        elif has_pc and any(self.pc[a, i] != 0.0 for a in range(n) if a != i):
+            for a in range(n):
+                h.pop("PC%03d%03d" % (a + 1, k), None)
+                h["PC%d_%d" % (a + 1, k)] = float(self.pc[a, i]) * f
+        else:
+            h["CDELT%d" % k] = float(h.get("CDELT%d" % k, 1.0)) * f
+        if shape is not None:
+            for a in range(n):
+                h["NAXIS%d" % (n - a)] = int(shape[a])
+        return SimpleWCS(h, naxis=n, strict=False)
+
     def to_header(self):
         h = {"WCSAXES": self.naxis}
         for i in range(self.naxis):
