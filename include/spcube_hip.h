@@ -20,6 +20,11 @@
  *   - cubes are C-contiguous (nz, ny, nx) float32, spectral axis first, x
  *     fastest; row/plane strides are given in ELEMENTS so that a (y) row strip
  *     of a larger cube can be processed in place;
+ *   - an axis may be longer than 65535 (the largest launch-grid y / z dimension): the
+ *     entry points split such a call into launches of their own, so shapes are limited
+ *     by memory and by the int64_t fields, not by the grid.  Known exceptions:
+ *     spc_wcs_pixel_map_f64 and spc_resample_spline_f32 take at most 262140 output
+ *     rows, and the spline form at most 65535 channels per call;
  *   - every launch takes a device index and a stream handle (hipStream_t as
  *     void*, NULL = default stream); there is no global mutable state, so dask
  *     `threads` workers and one-process-per-GPU drivers may call concurrently;

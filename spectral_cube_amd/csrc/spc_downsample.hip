@@ -348,7 +348,6 @@ int ds_setup(DsArgs<T>& A, int axis, int64_t factor, int truncate, int estimator
     A.ops = ops ? ops : A.nyo * A.ors;
     SPC_REQUIRE(A.ors >= A.nxo && A.ops >= A.ors * (A.nyo - 1) + A.nxo, "output strides too small for (%lld, %lld, %lld)",
                 (long long)A.nzo, (long long)A.nyo, (long long)A.nxo);
-    SPC_REQUIRE((axis == 1 ? A.nyo : A.ny) <= 65535, "more than 65535 rows per call not supported (split the call)");
     A.out = d_out;
     A.omask = d_out_mask;
     A.nan_skip = estimator < SPC_DS_MEAN;
@@ -377,9 +376,26 @@ int ds_run(int device, void* stream, const DsArgs<T>& A, int axis, int estimator
     SPC_DEVICE(device);
     const int kind = (estimator & 3) < 2 ? K_SUM : ((estimator & 3) == 2 ? K_MAX : K_MIN);
     hipStream_t st = (hipStream_t)stream;
-    if (ds_vec_ok(A, axis)) ds_launch_vec<T, true>(A, axis, kind, st);
-    else ds_launch_vec<T, false>(A, axis, kind, st);
-    SPC_LAUNCH_CHECK();
+    const bool vec = ds_vec_ok(A, axis);             // (row offsets below keep every alignment it checks)
+    const int64_t rows = axis == 1 ? A.nyo : A.ny;   // blockIdx.y: output rows along y, input rows otherwise
+    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {   // slabs of at most 65535 rows (gridDim.y)
+        DsArgs<T> S = A;
+        const int64_t n = ds_min(65535, rows - r0), in_r0 = axis == 1 ? r0 * A.f : r0;
+        S.in = A.in + in_r0 * A.rs;
+        if (S.marr) S.marr = A.marr + in_r0 * A.mrs;
+        S.out = A.out + r0 * A.ors;
+        if (S.omask) S.omask = A.omask + r0 * A.ors;
+        if (axis == 1) {
+            S.n_ax = A.n_ax - in_r0;
+            S.nyo = n;
+            S.ny = ds_min(S.n_ax, n * A.f);
+        } else {
+            S.ny = S.nyo = n;
+        }
+        if (vec) ds_launch_vec<T, true>(S, axis, kind, st);
+        else ds_launch_vec<T, false>(S, axis, kind, st);
+        SPC_LAUNCH_CHECK();
+    }
     return SPC_OK;
 }
 

@@ -180,19 +180,32 @@ template <bool ORD>
 static int launch_spatial(const SpMomArgs& A, const spc_cube_f32* cube, int axis, const double* d_cen, hipStream_t st) {
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     if (axis == 1) {
-        SPC_REQUIRE(cube->nz <= 65535, "nz > 65535 not supported for axis-1 moments");
         const bool v4 = (cube->nx % 4 == 0) && (cube->row_stride % 4 == 0) && (cube->plane_stride % 4 == 0) &&
                         ((((uintptr_t)cube->d_data) & 15) == 0) && ((((uintptr_t)d_cen) & 15) == 0) &&
                         (!arr || ((A.mask.row_stride % 4 == 0) && (A.mask.plane_stride % 4 == 0) && ((((uintptr_t)A.mask.arr) & 3) == 0)));
-        if (v4) {
-            dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)cube->nz);
-            if (arr) hipLaunchKernelGGL((moments_axis1_kernel<4, true, ORD>), grid, dim3(256), 0, st, A);
-            else hipLaunchKernelGGL((moments_axis1_kernel<4, false, ORD>), grid, dim3(256), 0, st, A);
-        } else {
-            dim3 grid((unsigned)((cube->nx + 63) / 64), (unsigned)cube->nz);
-            if (arr) hipLaunchKernelGGL((moments_axis1_kernel<1, true, ORD>), grid, dim3(256), 0, st, A);
-            else hipLaunchKernelGGL((moments_axis1_kernel<1, false, ORD>), grid, dim3(256), 0, st, A);
+        for (int64_t z0 = 0; z0 < cube->nz; z0 += 65535) {       // slabs of at most 65535 channels (gridDim.y)
+            SpMomArgs S = A;
+            S.cube = A.cube + z0 * A.plane_stride;
+            if (arr) S.mask.arr = A.mask.arr + z0 * A.mask.plane_stride;
+            const int64_t off = z0 * A.nx;                       // the maps are (nz, nx)
+            if (S.m0) S.m0 += off;
+            if (S.m1) S.m1 += off;
+            if (S.m2) S.m2 += off;
+            if (S.mu) S.mu += off;
+            if (S.mN) S.mN += off;
+            const unsigned gy = (unsigned)std::min<int64_t>(65535, cube->nz - z0);
+            if (v4) {
+                dim3 grid((unsigned)((cube->nx + 255) / 256), gy);
+                if (arr) hipLaunchKernelGGL((moments_axis1_kernel<4, true, ORD>), grid, dim3(256), 0, st, S);
+                else hipLaunchKernelGGL((moments_axis1_kernel<4, false, ORD>), grid, dim3(256), 0, st, S);
+            } else {
+                dim3 grid((unsigned)((cube->nx + 63) / 64), gy);
+                if (arr) hipLaunchKernelGGL((moments_axis1_kernel<1, true, ORD>), grid, dim3(256), 0, st, S);
+                else hipLaunchKernelGGL((moments_axis1_kernel<1, false, ORD>), grid, dim3(256), 0, st, S);
+            }
+            SPC_LAUNCH_CHECK();
         }
+        return SPC_OK;
     } else {
         const int64_t rows = cube->nz * cube->ny;
         if (arr) hipLaunchKernelGGL((moments_axis2_kernel<true, ORD>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, A);

@@ -391,6 +391,28 @@ int64_t wide_chunk_planes(int64_t nz, int64_t plane) {
     return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nz, 65535), (int64_t)(1ll << 28) / (plane * 8)));
 }
 
+// more than 65535 planes: the kernels hold the channel in gridDim.y / gridDim.z, and every plane is convolved on its own, so
+// the entry point runs once per slab of at most 65535 planes (stream-ordered: the slabs share the workspace)
+template <class F>
+int over_plane_slabs(const spc_cube_f32* cube, const spc_mask* mask, float* d_out, int64_t out_row_stride,
+                     int64_t out_plane_stride, F call) {
+    const int64_t ors = out_row_stride ? out_row_stride : cube->nx;
+    const int64_t ops = out_plane_stride ? out_plane_stride : cube->ny * ors;
+    for (int64_t z0 = 0; z0 < cube->nz; z0 += 65535) {
+        spc_cube_f32 c = *cube;
+        c.d_data = cube->d_data + z0 * cube->plane_stride;
+        c.nz = std::min<int64_t>(65535, cube->nz - z0);
+        spc_mask m{};
+        if (mask) {
+            m = *mask;
+            if (m.d_array) m.d_array += z0 * (m.plane_stride ? m.plane_stride : cube->plane_stride);
+        }
+        const int rc = call(&c, mask ? &m : nullptr, d_out + z0 * ops, ors, ops);
+        if (rc) return rc;
+    }
+    return SPC_OK;
+}
+
 }  // namespace
 
 size_t spc_ws_spatial_conv_sep(int64_t nz, int64_t ny, int64_t nx, int64_t nky, int64_t nkx) {
@@ -417,6 +439,12 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
     int rc = spc_check_cube(cube);
     if (rc) return rc;
     if ((rc = check_kernel(h_kernel, nky, "y")) || (rc = check_kernel(h_kernel, nkx, "x"))) return rc;
+    if (cube->nz > 65535 && d_out)
+        return over_plane_slabs(cube, mask, d_out, out_row_stride, out_plane_stride,
+                                [&](const spc_cube_f32* c, const spc_mask* m, float* o, int64_t ors, int64_t ops) {
+                                    return spc_spatial_conv2d_f32(device, stream, c, m, h_kernel, nky, nkx, o, ors, ops,
+                                                                  d_workspace, workspace_bytes);
+                                });
     double sum = 0.0;
     for (int i = 0; i < nky * nkx; ++i) sum += h_kernel[i];
     SPC_REQUIRE(!(sum < 1e-8 && sum > -1e-8) && sum >= 1e-8,
@@ -424,7 +452,6 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
     SpArgs A{};
     rc = fill_args(A, cube, mask, d_out, out_row_stride, out_plane_stride);
     if (rc) return rc;
-    SPC_REQUIRE(cube->nz <= 65535, "nz > 65535 planes per call not supported by the 2-D kernel grid");
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const char* env = getenv("SPC_CONV2D_TILED");
@@ -491,6 +518,12 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     int rc = spc_check_cube(cube);
     if (rc) return rc;
     if ((rc = check_kernel(h_ky, nky, "y")) || (rc = check_kernel(h_kx, nkx, "x"))) return rc;
+    if (cube->nz > 65535 && d_out)
+        return over_plane_slabs(cube, mask, d_out, out_row_stride, out_plane_stride,
+                                [&](const spc_cube_f32* c, const spc_mask* m, float* o, int64_t ors, int64_t ops) {
+                                    return spc_spatial_conv_sep_f32(device, stream, c, m, h_ky, nky, h_kx, nkx, o, ors, ops,
+                                                                    d_workspace, workspace_bytes);
+                                });
     double sy = 0.0, sx = 0.0;
     for (int i = 0; i < nky; ++i) sy += h_ky[i];
     for (int i = 0; i < nkx; ++i) sx += h_kx[i];
@@ -512,7 +545,6 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
         SpArgs A{};
         rc = fill_args(A, cube, mask, d_out, out_row_stride, out_plane_stride);
         if (rc) return rc;
-        SPC_REQUIRE(cube->ny <= 65535, "more than 65535 rows per call not supported (split the call)");
         SPC_DEVICE(device);
         canonical_pred(A);
         hipStream_t st = (hipStream_t)stream;
@@ -534,16 +566,22 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
         for (int64_t z0 = 0; z0 < cube->nz; z0 += nzc_max) {
             const int64_t nzc = std::min<int64_t>(nzc_max, cube->nz - z0);
             dim3 gy((unsigned)((nzc * cube->nx + 255) / 256), nys);
-            dim3 gx((unsigned)((cube->nx + 255) / 256), (unsigned)cube->ny, (unsigned)nzc);
             const size_t lds = sizeof(float2v) * (size_t)(256 + nkx - 1);
-            if (arr) {
-                hipLaunchKernelGGL(spatial_wide_ypass_kernel<true>, gy, dim3(256), 0, st, A, d_k, nyp, d_inter, z0, nzc);
-                hipLaunchKernelGGL(spatial_wide_xpass_kernel<true>, gx, dim3(256), lds, st, A, d_k + (nyp + 30), nkx, d_inter, z0, (float)sy);
-            } else {
-                hipLaunchKernelGGL(spatial_wide_ypass_kernel<false>, gy, dim3(256), 0, st, A, d_k, nyp, d_inter, z0, nzc);
-                hipLaunchKernelGGL(spatial_wide_xpass_kernel<false>, gx, dim3(256), lds, st, A, d_k + (nyp + 30), nkx, d_inter, z0, (float)sy);
-            }
+            if (arr) hipLaunchKernelGGL(spatial_wide_ypass_kernel<true>, gy, dim3(256), 0, st, A, d_k, nyp, d_inter, z0, nzc);
+            else hipLaunchKernelGGL(spatial_wide_ypass_kernel<false>, gy, dim3(256), 0, st, A, d_k, nyp, d_inter, z0, nzc);
             SPC_LAUNCH_CHECK();
+            // the x pass reads finished (num, den) rows of the y pass: slabs of at most 65535 rows (gridDim.y), row y0 of
+            // every plane moved to the slab's origin (S.ny stays the row count of a d_inter plane)
+            for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {
+                SpArgs S = A;
+                S.cube = A.cube + y0 * A.row_stride;
+                if (arr) S.mask.arr = A.mask.arr + y0 * A.mask.row_stride;
+                S.out = A.out + y0 * A.out_row_stride;
+                dim3 gx((unsigned)((cube->nx + 255) / 256), (unsigned)std::min<int64_t>(65535, cube->ny - y0), (unsigned)nzc);
+                if (arr) hipLaunchKernelGGL(spatial_wide_xpass_kernel<true>, gx, dim3(256), lds, st, S, d_k + (nyp + 30), nkx, d_inter + y0 * cube->nx, z0, (float)sy);
+                else hipLaunchKernelGGL(spatial_wide_xpass_kernel<false>, gx, dim3(256), lds, st, S, d_k + (nyp + 30), nkx, d_inter + y0 * cube->nx, z0, (float)sy);
+                SPC_LAUNCH_CHECK();
+            }
         }
         return SPC_OK;
     }
@@ -552,7 +590,6 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     if (rc) return rc;
     pad_taps(A.ky, h_ky, nky, R);
     pad_taps(A.kx, h_kx, nkx, R);
-    SPC_REQUIRE(cube->nz <= 65535, "nz > 65535 planes per call not supported (split the call)");
     SPC_DEVICE(device);
     const int HX = R / 2;
     A.txo = ((kThreads - 2 * HX) / kRun) * kRun;

@@ -784,7 +784,6 @@ int spc_stats_planes_f32(int device, void* stream, const spc_cube_f32* cube, con
     StatArgs A{};
     int rc = fill_common(A, cube, mask);
     if (rc) return rc;
-    SPC_REQUIRE(A.nz <= 65535, "more than 65535 channels per call not supported (split the call)");
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
@@ -795,11 +794,17 @@ int spc_stats_planes_f32(int device, void* stream, const spc_cube_f32* cube, con
     const size_t nrec = (size_t)A.nz * nseg;
     SpcWorkspace ws(d_workspace, workspace_bytes);
     SPC_WS_TAKE(d_partial, ws, double, 5 * nrec);
-    A.partial = d_partial;
-    dim3 grid((unsigned)nseg, (unsigned)A.nz);
-    if (arr) hipLaunchKernelGGL(stats_planes_kernel<true>, grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(stats_planes_kernel<false>, grid, dim3(256), 0, st, A);
-    hipError_t e = hipGetLastError();
+    hipError_t e = hipSuccess;
+    for (int64_t z0 = 0; z0 < A.nz && e == hipSuccess; z0 += 65535) {       // slabs of at most 65535 channels (gridDim.y)
+        StatArgs S = A;
+        S.cube = A.cube + z0 * A.plane_stride;
+        if (arr) S.mask.arr = A.mask.arr + z0 * A.mask.plane_stride;
+        S.partial = d_partial + (size_t)z0 * nseg * 5;
+        dim3 grid((unsigned)nseg, (unsigned)std::min<int64_t>(65535, A.nz - z0));
+        if (arr) hipLaunchKernelGGL(stats_planes_kernel<true>, grid, dim3(256), 0, st, S);
+        else hipLaunchKernelGGL(stats_planes_kernel<false>, grid, dim3(256), 0, st, S);
+        e = hipGetLastError();
+    }
     std::vector<double> h(5 * nrec);
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_partial, sizeof(double) * 5 * nrec, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -845,20 +850,31 @@ int spc_stats_axis_f32(int device, void* stream, const spc_cube_f32* cube, const
         A.n_outer = A.nz; A.outer_stride = A.plane_stride; A.n_march = A.ny; A.march_stride = A.row_stride;
         A.m_outer_stride = A.mask.plane_stride; A.m_march_stride = A.mask.row_stride;
     }
-    SPC_REQUIRE(A.n_outer <= 65535, "more than 65535 output rows per call not supported (split the call)");
     const bool v4 = (A.nx % 4 == 0) && (A.row_stride % 4 == 0) && (A.plane_stride % 4 == 0) &&
                     ((((uintptr_t)A.cube) & 15) == 0) &&
                     (!arr || ((A.mask.row_stride % 4 == 0) && (A.mask.plane_stride % 4 == 0) && ((((uintptr_t)A.mask.arr) & 3) == 0)));
-    if (v4) {
-        dim3 grid((unsigned)((A.nx + 255) / 256), (unsigned)A.n_outer);
-        if (arr) hipLaunchKernelGGL((stats_march_kernel<4, true>), grid, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((stats_march_kernel<4, false>), grid, dim3(256), 0, st, A);
-    } else {
-        dim3 grid((unsigned)((A.nx + 63) / 64), (unsigned)A.n_outer);
-        if (arr) hipLaunchKernelGGL((stats_march_kernel<1, true>), grid, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((stats_march_kernel<1, false>), grid, dim3(256), 0, st, A);
+    for (int64_t o0 = 0; o0 < A.n_outer; o0 += 65535) {          // slabs of at most 65535 output rows (gridDim.y)
+        StatArgs S = A;
+        S.cube = A.cube + o0 * A.outer_stride;
+        if (arr) S.mask.arr = A.mask.arr + o0 * A.m_outer_stride;
+        const int64_t off = o0 * A.nx;
+        if (S.o_cnt) S.o_cnt += off;
+        if (S.o_min) S.o_min += off;
+        if (S.o_max) S.o_max += off;
+        if (S.o_sum) S.o_sum += off;
+        if (S.o_ssq) S.o_ssq += off;
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, A.n_outer - o0);
+        if (v4) {
+            dim3 grid((unsigned)((A.nx + 255) / 256), gy);
+            if (arr) hipLaunchKernelGGL((stats_march_kernel<4, true>), grid, dim3(256), 0, st, S);
+            else hipLaunchKernelGGL((stats_march_kernel<4, false>), grid, dim3(256), 0, st, S);
+        } else {
+            dim3 grid((unsigned)((A.nx + 63) / 64), gy);
+            if (arr) hipLaunchKernelGGL((stats_march_kernel<1, true>), grid, dim3(256), 0, st, S);
+            else hipLaunchKernelGGL((stats_march_kernel<1, false>), grid, dim3(256), 0, st, S);
+        }
+        SPC_LAUNCH_CHECK();
     }
-    SPC_LAUNCH_CHECK();
     return SPC_OK;
 }
 
@@ -886,20 +902,27 @@ int spc_argextrema_axis_f32(int device, void* stream, const spc_cube_f32* cube, 
     }
     A.n_outer = A.nz; A.outer_stride = A.plane_stride; A.n_march = A.ny; A.march_stride = A.row_stride;
     A.m_outer_stride = A.mask.plane_stride; A.m_march_stride = A.mask.row_stride;
-    SPC_REQUIRE(A.n_outer <= 65535, "more than 65535 output rows per call not supported (split the call)");
     const bool v4 = (A.nx % 4 == 0) && (A.row_stride % 4 == 0) && (A.plane_stride % 4 == 0) &&
                     ((((uintptr_t)A.cube) & 15) == 0) &&
                     (!arr || ((A.mask.row_stride % 4 == 0) && (A.mask.plane_stride % 4 == 0) && ((((uintptr_t)A.mask.arr) & 3) == 0)));
-    if (v4) {
-        dim3 grid((unsigned)((A.nx + 255) / 256), (unsigned)A.n_outer);
-        if (arr) hipLaunchKernelGGL((arg_march_kernel<4, true>), grid, dim3(256), 0, st, B);
-        else hipLaunchKernelGGL((arg_march_kernel<4, false>), grid, dim3(256), 0, st, B);
-    } else {
-        dim3 grid((unsigned)((A.nx + 63) / 64), (unsigned)A.n_outer);
-        if (arr) hipLaunchKernelGGL((arg_march_kernel<1, true>), grid, dim3(256), 0, st, B);
-        else hipLaunchKernelGGL((arg_march_kernel<1, false>), grid, dim3(256), 0, st, B);
+    for (int64_t o0 = 0; o0 < A.n_outer; o0 += 65535) {          // slabs of at most 65535 output rows (gridDim.y)
+        ArgArgs S = B;
+        S.s.cube = A.cube + o0 * A.outer_stride;
+        if (arr) S.s.mask.arr = A.mask.arr + o0 * A.m_outer_stride;
+        if (S.o_argmin) S.o_argmin += o0 * A.nx;
+        if (S.o_argmax) S.o_argmax += o0 * A.nx;
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, A.n_outer - o0);
+        if (v4) {
+            dim3 grid((unsigned)((A.nx + 255) / 256), gy);
+            if (arr) hipLaunchKernelGGL((arg_march_kernel<4, true>), grid, dim3(256), 0, st, S);
+            else hipLaunchKernelGGL((arg_march_kernel<4, false>), grid, dim3(256), 0, st, S);
+        } else {
+            dim3 grid((unsigned)((A.nx + 63) / 64), gy);
+            if (arr) hipLaunchKernelGGL((arg_march_kernel<1, true>), grid, dim3(256), 0, st, S);
+            else hipLaunchKernelGGL((arg_march_kernel<1, false>), grid, dim3(256), 0, st, S);
+        }
+        SPC_LAUNCH_CHECK();
     }
-    SPC_LAUNCH_CHECK();
     return SPC_OK;
 }
 
@@ -1008,17 +1031,23 @@ int spc_fill_masked_f32(int device, void* stream, const spc_cube_f32* cube, cons
     ClipArgs A{};
     rc = spc_mask_to_dev(mask, cube, &A.mask);
     if (rc) return rc;
-    SPC_REQUIRE(cube->ny <= 65535, "more than 65535 rows per call not supported (split the call)");
     SPC_DEVICE(device);
     A.in = cube->d_data; A.out = d_out; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
     A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
     A.out_row_stride = out_row_stride ? out_row_stride : cube->nx;
     A.out_plane_stride = out_plane_stride ? out_plane_stride : cube->ny * A.out_row_stride;
     A.fill = fill;
-    dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)cube->ny, (unsigned)std::min<int64_t>(cube->nz, 64));
-    if (A.mask.flags & SPC_MASK_ARRAY) hipLaunchKernelGGL(fill_masked_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(fill_masked_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    SPC_LAUNCH_CHECK();
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {           // slabs of at most 65535 rows (gridDim.y)
+        ClipArgs S = A;
+        S.in = A.in + y0 * A.row_stride;
+        S.out = A.out + y0 * A.out_row_stride;
+        if (arr) S.mask.arr = A.mask.arr + y0 * A.mask.row_stride;
+        dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)std::min<int64_t>(65535, cube->ny - y0), (unsigned)std::min<int64_t>(cube->nz, 64));
+        if (arr) hipLaunchKernelGGL(fill_masked_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, S);
+        else hipLaunchKernelGGL(fill_masked_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, S);
+        SPC_LAUNCH_CHECK();
+    }
     return SPC_OK;
 }
 
@@ -1030,14 +1059,21 @@ int spc_mask_include_u8(int device, void* stream, const spc_cube_f32* cube, cons
     ClipArgs A{};
     rc = spc_mask_to_dev(mask, cube, &A.mask);
     if (rc) return rc;
-    SPC_REQUIRE(cube->ny <= 65535, "too many rows for one launch");
     SPC_DEVICE(device);
     A.in = cube->d_data; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
     A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
-    dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)cube->ny, (unsigned)std::min<int64_t>(cube->nz, 64));
-    if (A.mask.flags & SPC_MASK_ARRAY) hipLaunchKernelGGL(mask_include_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, A, d_out, nan_excluded);
-    else hipLaunchKernelGGL(mask_include_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, A, d_out, nan_excluded);
-    SPC_LAUNCH_CHECK();
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {
+        // slabs of at most 65535 rows (gridDim.y); the kernel's output plane stays ny * nx (S.ny is the whole count)
+        ClipArgs S = A;
+        S.in = A.in + y0 * A.row_stride;
+        if (arr) S.mask.arr = A.mask.arr + y0 * A.mask.row_stride;
+        uint8_t* out = d_out + y0 * cube->nx;
+        dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)std::min<int64_t>(65535, cube->ny - y0), (unsigned)std::min<int64_t>(cube->nz, 64));
+        if (arr) hipLaunchKernelGGL(mask_include_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, S, out, nan_excluded);
+        else hipLaunchKernelGGL(mask_include_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, S, out, nan_excluded);
+        SPC_LAUNCH_CHECK();
+    }
     return SPC_OK;
 }
 
@@ -1049,17 +1085,25 @@ int spc_fill_masked_transpose_f32(int device, void* stream, const spc_cube_f32* 
     ClipArgs A{};
     rc = spc_mask_to_dev(mask, cube, &A.mask);
     if (rc) return rc;
-    SPC_REQUIRE((cube->ny + 63) / 64 <= 65535, "too many rows for one launch");
     SPC_DEVICE(device);
     A.in = cube->d_data; A.out = d_out; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
     A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
     A.out_row_stride = cube->ny;                      // out is (nz, nx, ny), C-contiguous
     A.out_plane_stride = cube->nx * cube->ny;
     A.fill = fill;
-    dim3 grid((unsigned)((cube->nx + 63) / 64), (unsigned)((cube->ny + 63) / 64), (unsigned)std::min<int64_t>(cube->nz, 1024));
-    if (A.mask.flags & SPC_MASK_ARRAY) hipLaunchKernelGGL(fill_masked_transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(fill_masked_transpose_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    SPC_LAUNCH_CHECK();
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    const int64_t slab = 65535 * 64;                  // rows per launch: at most 65535 tiles of 64 rows (gridDim.y)
+    for (int64_t y0 = 0; y0 < cube->ny; y0 += slab) {
+        ClipArgs S = A;
+        S.ny = std::min<int64_t>(slab, cube->ny - y0);
+        S.in = A.in + y0 * A.row_stride;
+        S.out = A.out + y0;                           // column y0 of every (nx, ny) output plane
+        if (arr) S.mask.arr = A.mask.arr + y0 * A.mask.row_stride;
+        dim3 grid((unsigned)((cube->nx + 63) / 64), (unsigned)((S.ny + 63) / 64), (unsigned)std::min<int64_t>(cube->nz, 1024));
+        if (arr) hipLaunchKernelGGL(fill_masked_transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, S);
+        else hipLaunchKernelGGL(fill_masked_transpose_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, S);
+        SPC_LAUNCH_CHECK();
+    }
     return SPC_OK;
 }
 
@@ -1079,7 +1123,7 @@ int spc_clip_bounds_f32(int device, void* stream, int64_t n, const int32_t* d_co
 int spc_clip_outside_f32(int device, void* stream, float* d_cube, int64_t nz, int64_t ny, int64_t nx,
                          const float* d_lo, const float* d_hi, uint64_t* h_nchanged, void* d_workspace, size_t workspace_bytes) {
     SPC_REQUIRE(d_cube && d_lo && d_hi && h_nchanged, "NULL pointer argument");
-    SPC_REQUIRE(nz > 0 && ny > 0 && nx > 0 && ny <= 65535, "bad shape");
+    SPC_REQUIRE(nz > 0 && ny > 0 && nx > 0, "bad shape");
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     SpcWorkspace ws(d_workspace, workspace_bytes);
@@ -1089,14 +1133,20 @@ int spc_clip_outside_f32(int device, void* stream, float* d_cube, int64_t nz, in
         ClipArgs A{};
         A.out = d_cube; A.nz = nz; A.ny = ny; A.nx = nx; A.out_row_stride = nx; A.out_plane_stride = ny * nx;
         A.lo = d_lo; A.hi = d_hi; A.nchanged = d_n;
-        if (nx % 4 == 0 && ((((uintptr_t)d_cube) & 15) == 0)) {
-            dim3 grid((unsigned)((nx / 4 + 255) / 256), (unsigned)ny, (unsigned)std::min<int64_t>(nz, 64));
-            hipLaunchKernelGGL(clip_outside_kernel<4>, grid, dim3(256), 0, st, A);
-        } else {
-            dim3 grid((unsigned)((nx + 255) / 256), (unsigned)ny, (unsigned)std::min<int64_t>(nz, 64));
-            hipLaunchKernelGGL(clip_outside_kernel<1>, grid, dim3(256), 0, st, A);
+        const bool v4 = nx % 4 == 0 && ((((uintptr_t)d_cube) & 15) == 0);
+        for (int64_t y0 = 0; y0 < ny && e == hipSuccess; y0 += 65535) {     // slabs of at most 65535 rows (gridDim.y)
+            ClipArgs S = A;
+            S.out = d_cube + y0 * nx; S.lo = d_lo + y0 * nx; S.hi = d_hi + y0 * nx;
+            const unsigned gy = (unsigned)std::min<int64_t>(65535, ny - y0);
+            if (v4) {
+                dim3 grid((unsigned)((nx / 4 + 255) / 256), gy, (unsigned)std::min<int64_t>(nz, 64));
+                hipLaunchKernelGGL(clip_outside_kernel<4>, grid, dim3(256), 0, st, S);
+            } else {
+                dim3 grid((unsigned)((nx + 255) / 256), gy, (unsigned)std::min<int64_t>(nz, 64));
+                hipLaunchKernelGGL(clip_outside_kernel<1>, grid, dim3(256), 0, st, S);
+            }
+            e = hipGetLastError();
         }
-        e = hipGetLastError();
     }
     unsigned long long h = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d_n, sizeof h, hipMemcpyDeviceToHost, st);

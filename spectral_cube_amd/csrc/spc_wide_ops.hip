@@ -183,13 +183,9 @@ struct Conv64Args {
     int ntaps;
     const unsigned* gate;    // != nullptr: run only when the word is set (the ring kernel met an infinite valid sample)
 };
-__global__ __launch_bounds__(256) void spectral_conv64_kernel(const Conv64Args A) {
-    if (A.gate && *A.gate == 0u) return;
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= A.c.ny * A.c.nx) return;
-    const int64_t y = g / A.c.nx, x = g - y * A.c.nx;
+// the 16 outputs o0 .. o0 + 15 of spaxel (y, x)
+__device__ __forceinline__ void spectral_conv64_run(const Conv64Args& A, int64_t y, int64_t x, int64_t o0) {
     const int H = A.ntaps / 2;
-    const int64_t o0 = (int64_t)blockIdx.y * kRun;
     double num[kRun], den[kRun];
 #pragma unroll
     for (int u = 0; u < kRun; ++u) { num[u] = 0.0; den[u] = 0.0; }
@@ -262,6 +258,15 @@ emit:
         else { double cv; res = inc64(A.c, A.m, o, y, x, cv) ? cv : NAN; }
         A.out[o * A.out_plane_stride + y * A.out_row_stride + x] = res;
     }
+}
+
+__global__ __launch_bounds__(256) void spectral_conv64_kernel(const Conv64Args A) {
+    if (A.gate && *A.gate == 0u) return;
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= A.c.ny * A.c.nx) return;
+    const int64_t y = g / A.c.nx, x = g - y * A.c.nx;
+    // blockIdx.y = run of 16 channels; more than 65535 runs (gridDim.y) stride over the rest
+    for (int64_t o0 = (int64_t)blockIdx.y * kRun; o0 < A.c.nz; o0 += (int64_t)gridDim.y * kRun) spectral_conv64_run(A, y, x, o0);
 }
 
 // Second form (round 6): ring streaming, the float32 stencil's layout with float64 places.  A lane owns one spaxel and marches
@@ -362,11 +367,12 @@ struct Sp64Args {
     double* tmp;                            // (planes, ny, nx, 2) of the slab
     int64_t z0;                             // first plane of the slab
     const unsigned* gate;                   // != nullptr: run only when the word is set (the ring kernel met an infinite valid sample)
+    int64_t y0;                             // first row of the launch: row y = y0 + blockIdx.y (slabs of at most 65535 rows)
 };
 __global__ __launch_bounds__(256) void spatial64_xpass_kernel(const Sp64Args A) {
     if (A.gate && *A.gate == 0u) return;
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t y = blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
+    const int64_t y = A.y0 + blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
     if (x >= A.c.nx) return;
     const int H = A.nkx / 2;
     double num = 0.0, den = 0.0;
@@ -402,7 +408,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_kernel(const Sp64Args A) 
 __global__ __launch_bounds__(256) void spatial64_ypass_kernel(const Sp64Args A) {
     if (A.gate && *A.gate == 0u) return;
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t y = blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
+    const int64_t y = A.y0 + blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
     if (x >= A.c.nx) return;
     const int H = A.nky / 2;
     // a row outside the image is a row of valid zeros: its x-pass denominator is the whole x kernel
@@ -446,7 +452,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds_kernel(const Sp64Args
     __shared__ double sk[2 * kSpHaloMax + 1];                   // the flipped taps (a scalar load per tap waited out its latency in every lane's loop)
     const int t = threadIdx.x, H = A.nkx / 2;
     for (int j = t; j < A.nkx; j += 256) sk[j] = A.kx[A.nkx - 1 - j];
-    const int64_t x0 = (int64_t)blockIdx.x * 256, y = blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
+    const int64_t x0 = (int64_t)blockIdx.x * 256, y = A.y0 + blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
     const bool arr = (A.m.flags & SPC_MASK_ARRAY) != 0;
     const double* pd = A.c.p + z * A.c.plane_stride + y * A.c.row_stride;
     const uint8_t* pmk = arr ? A.m.arr + z * A.m.plane_stride + y * A.m.row_stride : nullptr;
@@ -526,7 +532,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds4_kernel(const Sp64Arg
     __shared__ double sk[2 * kSpX4Halo + 1];
     const int t = threadIdx.x, H = A.nkx / 2;
     for (int j = t; j < A.nkx; j += 256) sk[j] = A.kx[A.nkx - 1 - j];
-    const int64_t x0 = (int64_t)blockIdx.x * kSpX4Out, y = blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
+    const int64_t x0 = (int64_t)blockIdx.x * kSpX4Out, y = A.y0 + blockIdx.y, zl = blockIdx.z, z = A.z0 + zl;
     const bool arr = (A.m.flags & SPC_MASK_ARRAY) != 0;
     const double* pd = A.c.p + z * A.c.plane_stride + y * A.c.row_stride;
     const uint8_t* pmk = arr ? A.m.arr + z * A.m.plane_stride + y * A.m.row_stride : nullptr;
@@ -772,7 +778,7 @@ __global__ __launch_bounds__(256, 2) void spatial64_ring_kernel(const Ring64Args
 
 __global__ __launch_bounds__(256) void spatial64_direct_kernel(const Sp64Args A) {
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t y = blockIdx.y, z = A.z0 + blockIdx.z;
+    const int64_t y = A.y0 + blockIdx.y, z = A.z0 + blockIdx.z;
     if (x >= A.c.nx) return;
     const int Hy = A.nky / 2, Hx = A.nkx / 2;
     double num = 0.0, den = 0.0;
@@ -1733,8 +1739,8 @@ int spc_spectral_conv_f64(int device, void* stream, const spc_cube_f64* cube, co
         A.gate = d_flag;                                        // the kernel below runs only if the ring kernel raised the flag
     }
     const int64_t nb = (cube->ny * cube->nx + 255) / 256, runs = (cube->nz + kRun - 1) / kRun;
-    SPC_REQUIRE(nb < (1LL << 31) && runs <= 65535, "cube too large for one launch (convolve a slab of channels / rows)");
-    hipLaunchKernelGGL(spectral_conv64_kernel, dim3((unsigned)nb, (unsigned)runs), dim3(256), 0, st, A);
+    SPC_REQUIRE(nb < (1LL << 31), "more than 2^39 spaxels in one call");
+    hipLaunchKernelGGL(spectral_conv64_kernel, dim3((unsigned)nb, (unsigned)std::min<int64_t>(runs, 65535)), dim3(256), 0, st, A);
     SPC_LAUNCH_CHECK();
     return SPC_OK;
 }
@@ -1748,7 +1754,6 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
     SPC_REQUIRE(h_ky && d_out && (!separable || h_kx), "NULL pointer argument");
     SPC_REQUIRE(nky >= 1 && (nky & 1) && nkx >= 1 && (nkx & 1) && nky <= 1023 && nkx <= 1023,
                 "kernel axes must be odd and at most 1023 (got %d x %d)", nky, nkx);
-    SPC_REQUIRE(cube->ny <= 65535, "too many rows for one launch");
     if (separable) {                                            // (the sum of an outer product is the product of the sums)
         double sy = 0.0, sx = 0.0;
         for (int i = 0; i < nky; ++i) sy += h_ky[i];
@@ -1776,12 +1781,23 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
     A.out_row_stride = out_row_stride ? out_row_stride : cube->nx;
     A.out_plane_stride = out_plane_stride ? out_plane_stride : cube->ny * A.out_row_stride;
     const unsigned gx = (unsigned)((cube->nx + 255) / 256);
+    // kernels with one row per blockIdx.y: slabs of at most 65535 rows (gridDim.y), the rows addressed from A.y0 (the stencils
+    // read their halo rows from the whole image)
+    auto over_rows = [&](auto launch) -> int {
+        for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {
+            A.y0 = y0;
+            launch((unsigned)std::min<int64_t>(65535, cube->ny - y0));
+            SPC_LAUNCH_CHECK();
+        }
+        A.y0 = 0;
+        return SPC_OK;
+    };
     if (!separable) {
         for (int64_t z0 = 0; z0 < cube->nz; z0 += 65535) {
             A.z0 = z0;
             const unsigned gz = (unsigned)std::min<int64_t>(65535, cube->nz - z0);
-            hipLaunchKernelGGL(spatial64_direct_kernel, dim3(gx, (unsigned)cube->ny, gz), dim3(256), 0, st, A);
-            SPC_LAUNCH_CHECK();
+            rc = over_rows([&](unsigned gy) { hipLaunchKernelGGL(spatial64_direct_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A); });
+            if (rc) return rc;
         }
         return SPC_OK;
     }
@@ -1816,13 +1832,15 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
         const unsigned gz = (unsigned)std::min<int64_t>(planes, cube->nz - z0);
         static const int tiled = [] { const char* e = getenv("SPC_SPATIAL64_LDS"); return e ? atoi(e) : 2; }();
         // (SPC_SPATIAL64_LDS: 0 = the untiled passes, 1 = LDS tiles with one output per thread (round 5), 2 = four outputs per thread)
-        if (tiled == 2 && nkx / 2 <= kSpX4Halo)
-            hipLaunchKernelGGL(spatial64_xpass_lds4_kernel, dim3((unsigned)((cube->nx + kSpX4Out - 1) / kSpX4Out), (unsigned)cube->ny, gz), dim3(256), 0, st, A);
-        else if (tiled && nkx / 2 <= kSpHaloMax)
-            hipLaunchKernelGGL(spatial64_xpass_lds_kernel, dim3(gx, (unsigned)cube->ny, gz), dim3(256), 0, st, A);
-        else
-            hipLaunchKernelGGL(spatial64_xpass_kernel, dim3(gx, (unsigned)cube->ny, gz), dim3(256), 0, st, A);
-        SPC_LAUNCH_CHECK();
+        rc = over_rows([&](unsigned gy) {
+            if (tiled == 2 && nkx / 2 <= kSpX4Halo)
+                hipLaunchKernelGGL(spatial64_xpass_lds4_kernel, dim3((unsigned)((cube->nx + kSpX4Out - 1) / kSpX4Out), gy, gz), dim3(256), 0, st, A);
+            else if (tiled && nkx / 2 <= kSpHaloMax)
+                hipLaunchKernelGGL(spatial64_xpass_lds_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A);
+            else
+                hipLaunchKernelGGL(spatial64_xpass_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A);
+        });
+        if (rc) return rc;
         if (tiled == 2 && nky / 2 <= kSpYHalo && (cube->ny + kSpYRows - 1) / kSpYRows <= 65535)
             hipLaunchKernelGGL(spatial64_ypass_lds4_kernel, dim3((unsigned)((cube->nx + 63) / 64), (unsigned)((cube->ny + kSpYRows - 1) / kSpYRows), gz),
                                dim3(256), (size_t)(kSpYRows + 2 * (nky / 2)) * 64 * 16, st, A);
@@ -1830,8 +1848,9 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
             hipLaunchKernelGGL(spatial64_ypass_lds_kernel, dim3((unsigned)((cube->nx + 63) / 64), (unsigned)((cube->ny + kSpYRows - 1) / kSpYRows), gz),
                                dim3(256), (size_t)(kSpYRows + 2 * (nky / 2)) * 64 * 16, st, A);
         else
-            hipLaunchKernelGGL(spatial64_ypass_kernel, dim3(gx, (unsigned)cube->ny, gz), dim3(256), 0, st, A);
+            rc = over_rows([&](unsigned gy) { hipLaunchKernelGGL(spatial64_ypass_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A); });
         SPC_LAUNCH_CHECK();
+        if (rc) return rc;
     }
     return SPC_OK;
 }
@@ -1926,12 +1945,18 @@ int spc_narrow_f64_to_f32(int device, void* stream, const spc_cube_f64* cube, fl
     int rc = cube64_args(cube, nullptr, &C, &M);
     if (rc) return rc;
     SPC_REQUIRE(d_out != nullptr, "d_out is NULL");
-    SPC_REQUIRE(cube->ny <= 65535 && cube->nz <= 65535, "too many rows / channels for one launch");
     SPC_DEVICE(device);
     const int64_t rs = out_row_stride ? out_row_stride : cube->nx, ps = out_plane_stride ? out_plane_stride : cube->ny * rs;
-    hipLaunchKernelGGL(narrow64_kernel, dim3((unsigned)((cube->nx + 255) / 256), (unsigned)cube->ny, (unsigned)cube->nz), dim3(256), 0,
-                       (hipStream_t)stream, C, d_out, rs, ps);
-    SPC_LAUNCH_CHECK();
+    for (int64_t z0 = 0; z0 < cube->nz; z0 += 65535) {         // blocks of at most 65535 planes x 65535 rows (gridDim.z / .y)
+        for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {
+            Cube64 S = C;
+            S.p = C.p + z0 * C.plane_stride + y0 * C.row_stride;
+            const dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)std::min<int64_t>(65535, cube->ny - y0),
+                            (unsigned)std::min<int64_t>(65535, cube->nz - z0));
+            hipLaunchKernelGGL(narrow64_kernel, grid, dim3(256), 0, (hipStream_t)stream, S, d_out + z0 * ps + y0 * rs, rs, ps);
+            SPC_LAUNCH_CHECK();
+        }
+    }
     return SPC_OK;
 }
 
@@ -1941,11 +1966,21 @@ int spc_mask_include_f64(int device, void* stream, const spc_cube_f64* cube, con
     int rc = cube64_args(cube, mask, &C, &M);
     if (rc) return rc;
     SPC_REQUIRE(d_out != nullptr, "d_out is NULL");
-    SPC_REQUIRE(cube->ny <= 65535 && cube->nz <= 65535, "too many rows / channels for one launch");
     SPC_DEVICE(device);
-    hipLaunchKernelGGL(include64_kernel, dim3((unsigned)((cube->nx + 255) / 256), (unsigned)cube->ny, (unsigned)cube->nz), dim3(256), 0,
-                       (hipStream_t)stream, C, M, nan_excluded, d_out);
-    SPC_LAUNCH_CHECK();
+    const bool arr = (M.flags & SPC_MASK_ARRAY) != 0;
+    for (int64_t z0 = 0; z0 < cube->nz; z0 += 65535) {         // blocks of at most 65535 planes x 65535 rows (gridDim.z / .y)
+        for (int64_t y0 = 0; y0 < cube->ny; y0 += 65535) {
+            Cube64 S = C;                                      // (S.ny stays the row count of an output plane)
+            S.p = C.p + z0 * C.plane_stride + y0 * C.row_stride;
+            MaskDev64 SM = M;
+            if (arr) SM.arr = M.arr + z0 * M.plane_stride + y0 * M.row_stride;
+            const dim3 grid((unsigned)((cube->nx + 255) / 256), (unsigned)std::min<int64_t>(65535, cube->ny - y0),
+                            (unsigned)std::min<int64_t>(65535, cube->nz - z0));
+            hipLaunchKernelGGL(include64_kernel, grid, dim3(256), 0, (hipStream_t)stream, S, SM, nan_excluded,
+                               d_out + (z0 * cube->ny + y0) * cube->nx);
+            SPC_LAUNCH_CHECK();
+        }
+    }
     return SPC_OK;
 }
 

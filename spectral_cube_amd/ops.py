@@ -369,12 +369,8 @@ def sigma_clip_axis0_f64(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, ma
 def narrow_f64(cube, stream=None):
     """float32 copy of a float64 DeviceArray (for the operators without a float64 form)"""
     out = DeviceArray(cube.shape, np.float32, cube.device)
-    nz = cube.shape[0]
-    for z0 in range(0, nz, 65535):
-        z1 = min(nz, z0 + 65535)
-        c = _cube_c64(cube.planes(z0, z1) if (z0, z1) != (0, nz) else cube)
-        _lib.call("spc_narrow_f64_to_f32", cube.device, _sh(stream), C.byref(c),
-                  C.c_void_p(out.ptr + z0 * cube.shape[1] * cube.shape[2] * 4), 0, 0)
+    c = _cube_c64(cube)
+    _lib.call("spc_narrow_f64_to_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(out.ptr), 0, 0)
     return out
 
 
