@@ -334,6 +334,40 @@ int spc_downsample_f64(int device, void* stream, const spc_cube_f64* cube, const
                        double fill, int axis, int64_t factor, int truncate, int estimator,
                        double* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask);
 
+/* ---- cutting a cube (SpectralCube.__getitem__, spectral_cube.py:1308-1381; spectral_slab :1823-1879; subcube :1947-2036) ----
+ * Gathers a view of the parent into a compact cube, data and mask in one pass: output sample (k, j, i) is parent sample
+ * (start[0] + k * step[0], start[1] + j * step[1], start[2] + i * step[2]).  start / step are HOST arrays of 3 int64 in
+ * numpy axis order (spectral, y, x); step != 0, a negative step walks downwards from start; every selected sample must
+ * lie inside the parent and every output length be >= 1 (there is no zero-size form), else SPC_ERR_INVALID.
+ * filled == 0: the samples are copied bit for bit (the new cube's unmasked data, NaN payloads included); filled != 0:
+ * `fill` is written where the voxel is excluded (the FILLED 2-D / 1-D results of integer indices, :1362-1370).
+ * d_out_mask (uint8, may be NULL): include of the parent's lowered mask at the source voxel, with the nan_excluded rule
+ * of spc_downsample_*.  d_out / d_out_mask share the output strides (elements, 0 = C-contiguous), so that strips of a
+ * larger result are written in place.  Only selected rows are addressed: skipped planes and rows are never read.
+ * Along x a step of 1 uses 16-byte loads and stores (4-byte for the mask bytes) when the selected source rows, start[2]
+ * and the output rows are 16-byte aligned, one load per sample otherwise; any other x step one load per selected sample.
+ * Launches are split inside: no limit on any axis.  No workspace. */
+int spc_subcube_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
+                    const int64_t* start, const int64_t* step, int64_t nz_out, int64_t ny_out, int64_t nx_out,
+                    float* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask,
+                    int filled, float fill);
+int spc_subcube_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
+                    const int64_t* start, const int64_t* step, int64_t nz_out, int64_t ny_out, int64_t nx_out,
+                    double* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask,
+                    int filled, double fill);
+
+/* ---- bounding box of a mask (subcube_slices_from_mask / minimal_subcube, spectral_cube.py:1881-1945) ----
+ * What ndimage.find_objects(include.astype(int))[0] returns at :1925-1938: d_box (6 int64 in device memory, 8-byte
+ * aligned) receives {zmin, zmax, ymin, ymax, xmin, xmax} of the included voxels, bounds inclusive.  The entry point
+ * initialises it on the stream; a mask that includes nothing leaves min > max (INT64_MAX, -1).  The samples are read
+ * only when a predicate term or nan_excluded needs them: a pure array mask costs one byte per voxel.  Bounds are reduced
+ * per wave and per block before one atomicMin / atomicMax per block and bound.  The caller reads d_box after the stream
+ * has drained.  No workspace. */
+int spc_mask_bbox_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
+                      int64_t* d_box);
+int spc_mask_bbox_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
+                      int64_t* d_box);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

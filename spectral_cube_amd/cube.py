@@ -119,6 +119,10 @@ _ALL_NAN = ("All values in reprojected cube are nan.  This can be caused"
             "and world->pixel coordinates in each axis.")
 
 
+class SliceWarning(UserWarning):
+    """a spectral slab whose two limits fall on the same channel (utils.py:86)"""
+
+
 class SmoothingWarning(UserWarning):
     pass
 
@@ -255,14 +259,88 @@ def _downsample_streamed(cube, axis, factor, truncate, est, fill, shape):
     return data, inc
 
 
+def _check_cut_fits(cube, shape, has_mask):
+    """the cut of a streamed cube is made resident: its data (+ mask) must fit the HBM budget"""
+    from . import streaming
+    need = (5 if has_mask else 4) * int(np.prod(shape, dtype=np.int64))
+    budget = streaming.hbm_budget(cube.device)
+    if need > budget:
+        raise streaming.HugeCubeError(
+            "a cut of an out-of-core cube keeps its result in HBM: the result %s (data%s) takes %d bytes (%.2f GiB) against a "
+            "budget of %d bytes (%.2f GiB, SPC_HBM_BUDGET); cut a smaller range"
+            % (tuple(shape), " + mask" if has_mask else "", need, need / 2**30, budget, budget / 2**30))
+    return need, budget
+
+
+def _cut_window(spec):
+    """(z0, z1, y0, y1): the channel and row range of the parent that the view *spec* ((start, step, length) per axis)
+    touches - what a streamed cut stages; channels and rows outside it never leave the host"""
+    lo, hi = [], []
+    for (start, step, n) in spec[:2]:
+        last = start + (n - 1) * step
+        lo.append(min(start, last))
+        hi.append(max(start, last) + 1)
+    return lo[0], hi[0], lo[1], hi[1]
+
+
+def _subcube_streamed(cube, spec, shape, has_mask):
+    """ops.subcube of a cube larger than the HBM budget into a resident result: slabs of planes of the window the view
+    touches go through the strip pipeline, and the kernel writes each slab's selected channels in place"""
+    from . import streaming
+    from .device import Stream
+    need, budget = _check_cut_fits(cube, shape, has_mask)
+    data = DeviceArray(shape, np.float32, cube.device)
+    inc = DeviceArray(shape, np.uint8, cube.device) if has_mask else None
+    z0, z1, y0, y1 = window = _cut_window(spec)
+    terms = streaming._mask_terms(cube)
+    has_arr = terms is not None and terms[3] is not None
+    nan_ex = _nan_term_dropped(cube, cube)
+    compute = Stream(cube.device)
+    wshape = (z1 - z0, y1 - y0, cube._shape[2])
+    planes = streaming.plan_planes(wshape, max(budget - need, 1), mask_array=has_arr, out_factor=0.0)
+    (zs, zstep, nzo), (ys, ystep, _), (xs, xstep, _) = spec
+    chan = zs + zstep * np.arange(nzo, dtype=np.int64)           # parent channel of every output plane
+    for a, b, dev, mspec in streaming.Strips(cube, compute, planes, axis=0, window=window):
+        sel = np.nonzero((chan >= z0 + a) & (chan < z0 + b))[0]
+        if sel.size == 0:
+            continue
+        k0, k1 = int(sel[0]), int(sel[-1]) + 1
+        ops.subcube(dev, (int(chan[k0]) - z0 - a, ys - y0, xs), (zstep, ystep, xstep), (k1 - k0,) + tuple(shape[1:]), mask=mspec,
+                    out=data.planes(k0, k1), out_mask=inc.planes(k0, k1) if inc is not None else None, want_mask=has_mask,
+                    stream=compute, nan_excluded=nan_ex)
+    compute.synchronize()
+    return data, inc
+
+
+def _bbox_streamed(cube):
+    """ops.mask_bbox of a streamed cube: one box per row strip, merged on the host"""
+    from . import streaming
+    from .device import Stream
+    compute = Stream(cube.device)
+    nan_ex = _nan_term_dropped(cube, cube)
+    box = None
+    for y0, y1, dev, mspec in streaming.Strips(cube, compute):
+        b = ops.mask_bbox(dev, mask=mspec, stream=compute, nan_excluded=nan_ex)
+        if b is None:
+            continue
+        b = (b[0], (b[1][0] + y0, b[1][1] + y0), b[2])
+        box = b if box is None else tuple((min(p[0], q[0]), max(p[1], q[1])) for p, q in zip(box, b))
+    compute.synchronize()
+    return box
+
+
+_AXIS_NAMES = ("spectral axis (0)", "y axis (1)", "x axis (2)")
+
+
 class Projection(np.ndarray):
     """2-D result map (stands in for lower_dimensional_structures.Projection
     :246-292): an ndarray carrying unit, wcs and meta."""
 
-    def __new__(cls, value, unit="", wcs=None, meta=None, beam=None, device=0):
+    def __new__(cls, value, unit="", wcs=None, meta=None, beam=None, device=0, header=None):
         obj = np.asarray(value).view(cls)
         obj.unit = unit
         obj.wcs = wcs
+        obj.header = dict(header) if header is not None else dict(getattr(wcs, "header", None) or {})
         obj.meta = dict(meta or {})
         obj.beam = beam if beam is not None else obj.meta.get("beam")
         obj._spc_device = device
@@ -273,6 +351,7 @@ class Projection(np.ndarray):
             return
         self.unit = getattr(obj, "unit", "")
         self.wcs = getattr(obj, "wcs", None)
+        self.header = getattr(obj, "header", {})
         self.meta = getattr(obj, "meta", {})
         self.beam = getattr(obj, "beam", None)
         self._spc_device = getattr(obj, "_spc_device", 0)
@@ -1433,6 +1512,277 @@ class SpectralCube:
             return self._new_wide_cube(lambda: result()[0], shape=shape, wcs=newwcs, mask=mask)
         return self._new_cube_with(lazy=_Thunk(lambda: result()[0]), shape=shape, wcs=newwcs, mask=mask)
 
+    # ---- cutting: slicing, spectral_slab, subcube, minimal_subcube ---------------------------------
+    def _normalize_view(self, view):
+        """*view* as a tuple of three entries, slices kept, integers normalised to 0 .. n - 1 (spectral_cube.py:1310-1316)"""
+        if not isinstance(view, tuple):
+            view = (view,)
+        if len(view) > 3:
+            raise IndexError("Too many indices")
+        view = view + (slice(None),) * (3 - len(view))
+        out = []
+        for axis, (s, n) in enumerate(zip(view, self._shape)):
+            if isinstance(s, slice):
+                out.append(s)
+            elif isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)):
+                k = int(s)
+                if not -n <= k < n:
+                    raise IndexError("index %d is out of bounds for the %s with size %d" % (k, _AXIS_NAMES[axis], n))
+                out.append(k + n if k < 0 else k)
+            else:
+                raise IndexError("a cube is indexed with integers and slices (got %r)" % (s,))
+        return tuple(out)
+
+    def __getitem__(self, view):
+        """``cube[view]`` (spectral_cube.py:1308-1381): an integer or slice, or a tuple of up to three.
+
+        Slices only: a new cube that owns compact memory (never a view of the parent's), its unmasked data equal to
+        ``parent_data[view]`` bit for bit, its mask to ``parent.mask.include()[view]``, the WCS from ``SimpleWCS.sliced``;
+        ``meta['slice']`` records the view.  The result is pending like ``downsample_axis``: one gather pass makes data and
+        mask on first use, and the mask stays in HBM.  A parent larger than the HBM budget streams only the channel and
+        row range the view touches; the cut itself must fit the budget (HugeCubeError).
+        An empty selection (``cube[5:5]``) raises ValueError - the reference returns a (0, ...) cube.
+
+        ``cube[k]`` / ``cube[k, ys, xs]``: the FILLED channel as a 2-D Projection with the celestial WCS, its header
+        carrying CRVAL3 / CDELT3 / CUNIT3 of that channel.  ``cube[zs, j, i]``: the filled spectrum as a 1-D Projection
+        whose wcs is the spectral axis alone.  Integers that include the spectral axis and another:
+        NotImplementedError as the reference; one integer on y or x (a position-velocity slice): NotImplementedError."""
+        view = self._normalize_view(view)
+        meta = dict(self._meta)
+        slice_data = [(s.start, s.stop, s.step) if isinstance(s, slice) else s for s in view]
+        meta["slice"] = list(meta.get("slice", [])) + [slice_data]
+        ints = [axis for axis, s in enumerate(view) if not isinstance(s, slice)]
+        if not ints:
+            return self._cut(view, meta)
+        if len(ints) > 1:
+            if 0 in ints:
+                raise NotImplementedError("1D slices along non-spectral axes are not yet implemented.")
+            return self._spectrum(view, meta)
+        if ints[0] != 0:
+            raise NotImplementedError("a single integer index on a spatial axis (a position-velocity slice) is not built")
+        return self._channel(view, meta)
+
+    def _view_spec(self, view):
+        """(start, step, length) per axis of three slices; an empty selection raises (the kernels have no zero-size form)"""
+        spec = ops.normalize_view(view, self._shape)
+        for axis, (start, step, n) in enumerate(spec):
+            if n < 1:
+                raise ValueError("the view %r selects nothing along the %s of a cube of shape %s"
+                                 % (view[axis], _AXIS_NAMES[axis], self._shape))
+        return spec
+
+    def _gather(self, spec, shape, filled=False):
+        """(data, include or None) of the view on the device, in the cube's dtype path"""
+        starts, steps = [a[0] for a in spec], [a[1] for a in spec]
+        has_mask = self._mask is not None
+        if self._runs_wide():
+            return ops.subcube_f64(self._device_data64(), starts, steps, shape, mask=self._mask_spec64() if has_mask else None,
+                                   want_mask=has_mask, filled=filled, fill=self._fill_value,
+                                   nan_excluded=_nan_term_dropped(self, _WideView(self)))
+        if self._stream_source() is not None:
+            data, inc = _subcube_streamed(self, spec, shape, has_mask)
+            if filled and has_mask:
+                data = ops.fill_masked(data, ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc), self._fill_value)
+            return data, inc
+        return ops.subcube(self._device_data(), starts, steps, shape, mask=self._mask_spec() if has_mask else None,
+                           want_mask=has_mask, filled=filled, fill=self._fill_value, nan_excluded=_nan_term_dropped(self, self))
+
+    def _cut_finish(self, new, view):
+        return new
+
+    def _cut(self, view, meta):
+        spec = self._view_spec(view)
+        shape = tuple(a[2] for a in spec)
+        newwcs = self._wcs.sliced(view, self._shape) if self._wcs is not None else None
+        if newwcs is None:
+            for axis, (start, step, n) in enumerate(spec):
+                if step < 0 and (axis != 0 or step != -1):
+                    raise NotImplementedError("Haven't dealt with resampling & reversing.")
+        parent, wide, has_mask = self, self._runs_wide(), self._mask is not None
+        if not wide:
+            try:
+                streamed = self._stream_source() is not None
+            except _lib.HipLibraryError:
+                streamed = False
+            if streamed:
+                _check_cut_fits(self, shape, has_mask)
+        result = _Once(lambda: parent._gather(spec, shape))
+        mask = M.DeviceBooleanMask(lambda: result()[1], wcs=newwcs, shape=shape) if has_mask else None
+        if wide:
+            new = self._new_wide_cube(lambda: result()[0], shape=shape, wcs=newwcs, mask=mask, plain=True)
+        else:
+            new = SpectralCube._new_cube_with(self, lazy=_Thunk(lambda: result()[0]), shape=shape, wcs=newwcs, mask=mask)
+        new._meta = meta
+        return self._cut_finish(new, view)
+
+    def _channel_beam(self, k):
+        return self.beam
+
+    def _spectrum_meta(self, meta, view):
+        return meta
+
+    def _channel(self, view, meta):
+        """cube[k, ys, xs]: the filled channel as a 2-D Projection (spectral_cube.py:1351-1370)"""
+        k = view[0]
+        full = (slice(k, k + 1),) + tuple(view[1:])
+        spec = self._view_spec(full)
+        shape = tuple(a[2] for a in spec)
+        w2, header = None, {}
+        if self._wcs is not None:
+            w2 = self._wcs.sliced(full, self._shape).drop_spectral()
+            header = dict(w2.header)
+            header["CRVAL3"] = float(self._wcs.spectral_pix2world(k))
+            header["CDELT3"] = float(self._wcs.cdelt[2] * self._wcs.pc[2, 2])
+            header["CUNIT3"] = self.spectral_unit
+        data, _ = self._gather(spec, shape, filled=True)
+        beam = self._channel_beam(k)
+        if beam is not None:
+            meta = dict(meta, beam=beam)
+        return Projection(data.get()[0], unit=self._unit, wcs=w2, meta=meta, beam=beam, device=self.device, header=header)
+
+    def _spectrum(self, view, meta):
+        """cube[zs, j, i]: the filled spectrum as a 1-D Projection whose wcs is the spectral axis alone (:1331-1349)"""
+        j, i = view[1], view[2]
+        full = (view[0], slice(j, j + 1), slice(i, i + 1))
+        spec = self._view_spec(full)
+        shape = tuple(a[2] for a in spec)
+        w1 = self._wcs.sliced(full, self._shape).spectral_only() if self._wcs is not None else None
+        data, _ = self._gather(spec, shape, filled=True)
+        meta = self._spectrum_meta(meta, view)
+        return Projection(data.get()[:, 0, 0], unit=self._unit, wcs=w1, meta=meta, device=self.device)
+
+    def _spectral_value(self, value):
+        """a spectral coordinate in the cube's spectral unit: plain numbers are taken to be in it, an object with
+        ``.value`` and ``.unit`` is converted (same kind of unit only, spectral_cube.py:1794-1819)"""
+        if not hasattr(value, "unit"):
+            return float(value)
+        unit = value.unit
+        unit = str(getattr(unit, "to_string", lambda: unit)()).replace(" ", "")
+        try:
+            return float(value.value) * spectral_unit_scale(unit, self.spectral_unit)
+        except ValueError:
+            from .wcs import _SPECTRAL_SI
+            mine = _SPECTRAL_SI.get(self.spectral_unit, (None,))[0]
+            theirs = _SPECTRAL_SI.get(unit, (None,))[0]
+            if theirs in ("freq", "length") and mine == "speed":
+                raise UnitsError("Spectral axis is in velocity units and 'value' is in frequency-equivalent units - use "
+                                 "SpectralCube.with_spectral_unit first to convert the cube to frequency-equivalent units, or "
+                                 "search for a velocity instead")
+            if theirs == "speed" and mine in ("freq", "length"):
+                raise UnitsError("Spectral axis is in frequency-equivalent units and 'value' is in velocity units - use "
+                                 "SpectralCube.with_spectral_unit first to convert the cube to frequency-equivalent units, or "
+                                 "search for a velocity instead")
+            if theirs in ("freq", "length") and mine in ("freq", "length"):
+                raise NotImplementedError("converting between frequency and wavelength is a change of spectral representation: "
+                                          "not built, give the value in %s" % self.spectral_unit)
+            if theirs is not None:
+                raise UnitsError("Unexpected spectral axis units: {0}".format(self.spectral_unit))
+            raise UnitsError("'value' should be in frequency equivalent or velocity units (got {0})".format(unit))
+
+    def closest_spectral_channel(self, value):
+        """index of the channel closest to the spectral coordinate *value* (spectral_cube.py:1780-1821)"""
+        return int(np.argmin(np.abs(self.spectral_axis - self._spectral_value(value))))
+
+    def spectral_slab(self, lo, hi):
+        """the cube between two spectral coordinates, both ends included (spectral_cube.py:1823-1879); limits in either
+        order, plain numbers in the cube's spectral unit"""
+        ilo, ihi = self.closest_spectral_channel(lo), self.closest_spectral_channel(hi)
+        if ilo == ihi:
+            warnings.warn("The maxmimum and minimum spectral channel in the spectral"
+                          "slab are identical; this indicates that one or both are "
+                          "likely incorrect and/or out of range.", SliceWarning)
+        if ilo > ihi:
+            ilo, ihi = ihi, ilo
+        return self[ilo:ihi + 1]
+
+    def subcube(self, xlo="min", xhi="max", ylo="min", yhi="max", zlo="min", zhi="max", rest_value=None):
+        """Extract a sub-cube spatially and spectrally (spectral_cube.py:1947-2036).  Limits are 'min' / 'max', pixel
+        integers, or - *zlo* / *zhi* only - spectral coordinates (objects with ``.unit``; the upper one is end-inclusive).
+        Spatial limits as world coordinates (the reference's joint corner solve): NotImplementedError."""
+        nz, ny, nx = self._shape
+        given = {"xlo": xlo, "xhi": xhi, "ylo": ylo, "yhi": yhi, "zlo": zlo, "zhi": zhi}
+        ends = {"xlo": 0, "xhi": nx, "ylo": 0, "yhi": ny, "zlo": 0, "zhi": nz}
+        lim, united = {}, []
+        for key, v in given.items():
+            if isinstance(v, str):
+                if v != ("min" if key.endswith("lo") else "max"):
+                    raise ValueError("%s must be %r, a pixel index or a quantity (got %r)" % (key, "min" if key.endswith("lo") else "max", v))
+                lim[key] = ends[key]
+            elif hasattr(v, "unit"):
+                if key[0] != "z":
+                    raise NotImplementedError("spatial limits given as world coordinates are not built: give %s in pixels" % key)
+                try:
+                    lim[key] = self.closest_spectral_channel(v)
+                except UnitsError:
+                    raise UnitsError("Spectral units are not equivalent to the spectral slice.  Use `.with_spectral_unit` to "
+                                     "convert to equivalent units first")
+                united.append(key)
+            elif isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+                lim[key] = int(v)
+            else:
+                raise ValueError("%s must be 'min' / 'max', a pixel index or (spectral limits) a quantity (got %r)" % (key, v))
+        if lim["zhi"] < lim["zlo"]:
+            lim["zlo"], lim["zhi"] = lim["zhi"], lim["zlo"]
+        if "zhi" in united:
+            lim["zhi"] += 1
+        for xx in "zyx":
+            if lim[xx + "hi"] == lim[xx + "lo"]:
+                raise ValueError("The slice in the {0} direction will remove "
+                                 "all elements.  If you want a single-channel "
+                                 "slice, you need a different approach.".format(xx))
+        return self[tuple(slice(lim[xx + "lo"], lim[xx + "hi"]) for xx in "zyx")]
+
+    def subcube_slices_from_mask(self, region_mask, spatial_only=False):
+        """the slices of the smallest subcube that holds every voxel *region_mask* includes (spectral_cube.py:1901-1945):
+        a boolean ndarray broadcastable to the cube, or a mask object, lowered against this cube's data and reduced to
+        its bounding box on the device.  ``(slice(0),) * 3`` when nothing is included."""
+        if isinstance(region_mask, np.ndarray):
+            ok = region_mask.ndim <= 3 and all(a in (1, b) for a, b in zip(region_mask.shape[::-1], self._shape[::-1]))
+            if not ok:
+                raise ValueError("Mask shape does not match cube shape.")
+            region_mask = M.BooleanArrayMask(region_mask, self._wcs, shape=self._shape)
+        if region_mask is self._mask:
+            probe = self
+        else:
+            if self._lazy is not None and not self._runs_wide():
+                self._device_data()                     # a pending cube is materialised once and shared with the probe
+            probe = SpectralCube._new_cube_with(self, data=self._data, dev=self._dev, mask=region_mask, lazy=self._lazy,
+                                                shape=self._shape, same_data=True)
+        if probe._runs_wide():
+            box = ops.mask_bbox_f64(probe._device_data64(), mask=probe._mask_spec64(),
+                                    nan_excluded=_nan_term_dropped(probe, _WideView(probe)))
+        elif probe._stream_source() is not None:
+            box = _bbox_streamed(probe)
+        else:
+            box = ops.mask_bbox(probe._device_data(), mask=probe._mask_spec(), nan_excluded=_nan_term_dropped(probe, probe))
+        if box is None:
+            return (slice(0),) * 3
+        slices = tuple(slice(lo, hi + 1) for lo, hi in box)
+        if spatial_only:
+            slices = (slice(None),) + slices[1:]
+        return slices
+
+    def subcube_from_mask(self, region_mask):
+        """the minimal subcube that encloses *region_mask* (spectral_cube.py:1890-1899)"""
+        return self[self.subcube_slices_from_mask(region_mask)]
+
+    def minimal_subcube(self, spatial_only=False):
+        """the minimum enclosing subcube where the mask is valid (spectral_cube.py:1881-1888); a cube without a mask: a
+        copy of itself.  With nothing included the empty selection raises ValueError."""
+        if self._mask is None:
+            return self[:]
+        return self[self.subcube_slices_from_mask(self._mask, spatial_only=spatial_only)]
+
+    def mask_channels(self, goodchannels):
+        """mask out whole channels: *goodchannels* a 1-D boolean array with one entry per channel (spectral_cube.py:3394)"""
+        goodchannels = np.asarray(goodchannels, dtype="bool")
+        if goodchannels.ndim != 1:
+            raise ValueError("goodchannels mask must be one-dimensional")
+        if goodchannels.size != self._shape[0]:
+            raise ValueError("goodchannels must have a length equal to the "
+                             "cube's spectral dimension.")
+        return self.with_mask(goodchannels[:, None, None])
+
     # ---- smoothing ---------------------------------------------------------------------------
     def spectral_smooth(self, kernel, convolve=None, **kwargs):
         """Smooth along the spectral axis; the mask is left unchanged
@@ -1934,6 +2284,20 @@ class VaryingResolutionSpectralCube(SpectralCube):
             raise NotImplementedError("downsampling the spectral axis of a VaryingResolutionSpectralCube would have to average "
                                       "the channels' beams: bring the cube to one beam with convolve_to() first")
         return SpectralCube.downsample_axis(self, factor, axis, estimator=estimator, truncate=truncate)
+
+    def _cut_finish(self, new, view):
+        """a cut along the spectral axis cuts the beams table with the same slice (spectral_cube.py:3873-3967)"""
+        new.__class__ = VaryingResolutionSpectralCube
+        new._beams = list(self._beams[view[0]])
+        new._goodbeams_mask = self._goodbeams_mask[view[0]].copy()
+        new.beam_threshold = self.beam_threshold
+        return new
+
+    def _channel_beam(self, k):
+        return self._beams[k]
+
+    def _spectrum_meta(self, meta, view):
+        return dict(meta, beams=list(self._beams[view[0]]))
 
     def _new_cube_with(self, **kw):
         new = SpectralCube._new_cube_with(self, **kw)

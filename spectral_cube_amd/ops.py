@@ -512,6 +512,81 @@ def downsample_f64(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN
     return out, out_mask
 
 
+def normalize_view(view, shape):
+    """(start, step, length) per axis of a tuple of three slices applied to *shape* (``slice.indices``, as numpy indexes)"""
+    out = []
+    for sl, n in zip(view, shape):
+        start, stop, step = sl.indices(int(n))
+        out.append((start, step, len(range(start, stop, step))))
+    return out
+
+
+def _subcube_call(name, cube, c, m, start, step, shape, dtype, out, out_mask, want_mask, filled, fill, nan_excluded, stream):
+    shape = tuple(int(n) for n in shape)
+    if out is None:
+        out = DeviceArray(shape, dtype, cube.device)
+    if out_mask is None and want_mask:
+        out_mask = DeviceArray(shape, np.uint8, cube.device)
+    if tuple(out.shape) != shape or out.dtype != np.dtype(dtype):
+        raise ValueError("preallocated output must be %s %s" % (shape, np.dtype(dtype)))
+    if out_mask is not None:
+        if tuple(out_mask.shape) != shape or out_mask.dtype != np.uint8:
+            raise ValueError("preallocated mask output must be %s uint8" % (shape,))
+        if _strides(out) != _strides(out_mask):
+            raise ValueError("out and out_mask must have the same strides")
+    ors, ops_ = _strides(out)
+    st3, sp3 = (C.c_int64 * 3)(*[int(v) for v in start]), (C.c_int64 * 3)(*[int(v) for v in step])
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, st3, sp3,
+              shape[0], shape[1], shape[2], C.c_void_p(out.ptr), ors, ops_,
+              C.c_void_p(out_mask.ptr) if out_mask is not None else None, 1 if filled else 0, float(fill))
+    return out, out_mask
+
+
+def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_mask=True, filled=False, fill=np.nan,
+            stream=None, nan_excluded=False):
+    """(data, include) of ``cube[start[a] :: step[a]]`` cut to *shape* = SpectralCube.__getitem__ with three slices
+    (spectral_cube.py:1308-1381): output sample (k, j, i) is parent sample (start + (k, j, i) * step), copied bit for bit
+    (*filled*: excluded voxels become *fill*), and the include byte of the parent's mask there.  ``want_mask=False``
+    (a parent without a mask) skips the mask output and returns None for it.  *out* / *out_mask* may be strided views
+    of larger outputs."""
+    return _subcube_call("spc_subcube_f32", cube, _cube_c(cube), _mask_c(mask, cube), start, step, shape, np.float32, out,
+                         out_mask, want_mask, filled, fill, nan_excluded, stream)
+
+
+def subcube_f64(cube, start, step, shape, mask=None, out=None, out_mask=None, want_mask=True, filled=False, fill=np.nan,
+                stream=None, nan_excluded=False):
+    """subcube of a float64 cube: float64 in, float64 out"""
+    return _subcube_call("spc_subcube_f64", cube, _cube_c64(cube), _mask_c64(mask, cube), start, step, shape, np.float64, out,
+                         out_mask, want_mask, filled, fill, nan_excluded, stream)
+
+
+def _bbox_result(box, device, stream):
+    if stream is not None:
+        _lib.call("spc_stream_sync", device, _sh(stream))
+    b = [int(v) for v in box.get()]
+    if b[0] > b[1]:
+        return None
+    return ((b[0], b[1]), (b[2], b[3]), (b[4], b[5]))
+
+
+def mask_bbox(cube, mask=None, stream=None, nan_excluded=False):
+    """bounding box of the included voxels, ((zmin, zmax), (ymin, ymax), (xmin, xmax)) with inclusive bounds, or None
+    when nothing is included: ``ndimage.find_objects(include.astype(int))[0]`` of subcube_slices_from_mask
+    (spectral_cube.py:1925-1938) in one pass over the mask terms."""
+    box = DeviceArray((6,), np.int64, cube.device)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    _lib.call("spc_mask_bbox_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(box.ptr))
+    return _bbox_result(box, cube.device, stream)
+
+
+def mask_bbox_f64(cube, mask=None, stream=None, nan_excluded=False):
+    """mask_bbox of a float64 cube (thresholds compared in float64)"""
+    box = DeviceArray((6,), np.int64, cube.device)
+    c, m = _cube_c64(cube), _mask_c64(mask, cube)
+    _lib.call("spc_mask_bbox_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(box.ptr))
+    return _bbox_result(box, cube.device, stream)
+
+
 def spectral_conv_moments(cube, kernel1d, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL,
                           stream=None, out=None, cen_host=None):
     """fused spectral_smooth -> moment (smoothed cube never written).

@@ -181,6 +181,28 @@ class FitsSource:
 
 
 # ---- the strip pipeline ------------------------------------------------------------------------------------
+class WindowSource:
+    """channels [z0, z1) and rows [y0, y1) of another source, as a source of shape (z1 - z0, y1 - y0, nx): what a cut of an
+    out-of-core cube stages.  Reads, decoding and the staging format are the parent's"""
+
+    def __init__(self, source, z0, z1, y0, y1):
+        nz, ny, nx = source.shape
+        if not (0 <= z0 < z1 <= nz and 0 <= y0 < y1 <= ny):
+            raise ValueError("window (%d:%d, %d:%d) outside a source of shape %s" % (z0, z1, y0, y1, (nz, ny, nx)))
+        self.source, self.z0, self.y0 = source, int(z0), int(y0)
+        self.shape = (int(z1 - z0), int(y1 - y0), nx)
+        self.out_dtype, self.sample_bytes, self.decode = source.out_dtype, source.sample_bytes, getattr(source, "decode", None)
+        for name in ("max_strip_mb", "preferred_chunk_mb"):
+            if hasattr(source, name):
+                setattr(self, name, getattr(source, name))
+
+    def read_into(self, view_u8, z0, z1, y0, y1):
+        return self.source.read_into(view_u8, z0 + self.z0, z1 + self.z0, y0 + self.y0, y1 + self.y0)
+
+    def release(self):
+        pass                               # the parent source stays open for the cube it belongs to
+
+
 def plan_rows(shape, budget, mask_array=False, align=8, max_strip_mb=0):
     """rows per strip: two strips in flight (one computing, one being staged) + their mask strips within
     half the budget, at least `align` rows, a multiple of `align` (16-byte aligned row starts for any nx % 4 == 0)"""
@@ -386,10 +408,12 @@ class Strips:
     """(y0, y1, data strip, MaskSpec or None) of a streamed cube on `stream`; data and the mask's array term come
     through two pipelines in lockstep"""
 
-    def __init__(self, cube, stream, rows=None, halo=0, axis=1, out_factor=1.0):
+    def __init__(self, cube, stream, rows=None, halo=0, axis=1, out_factor=1.0, window=None):
         from . import ops
         self.ops = ops
-        src = cube._stream_source()
+        src = whole = cube._stream_source()
+        if window is not None:             # (z0, z1, y0, y1): only that range of channels and rows is staged (a cut)
+            src = WindowSource(whole, *window)
         self.terms = _mask_terms(cube)
         has_arr = self.terms is not None and self.terms[3] is not None
         if rows is None:
@@ -399,7 +423,9 @@ class Strips:
         self.data = StripPipeline(src, cube.device, rows, stream, halo=halo, axis=axis)
         self.mask = None
         if has_arr:
-            m = np.broadcast_to(self.terms[3], src.shape)
+            m = np.broadcast_to(self.terms[3], whole.shape)
+            if window is not None:
+                m = m[window[0]:window[1], window[2]:window[3]]
             self.mask = StripPipeline(NdarraySource(m, np.uint8), cube.device, rows, stream,
                                       nbuffers=max(4, self.data.nbuf // 2), readers=max(2, self.data.readers // 2), halo=halo, axis=axis)
 

@@ -571,14 +571,33 @@ class SimpleWCS:
         the reference does); a CD matrix, or a PC matrix that mixes the axis into others, gets that column scaled instead
         (CDELT would scale a world row, which moves the block centres).  *shape* (numpy order) sets NAXISn.  SIP
         distortion on a downsampled celestial axis: NotImplementedError."""
+        h = dict(self.header)
+        if int(factor) == 1 and self.naxis - 1 - int(axis) < 2 and self.sip_a is not None:
+            self._step_axis(h, int(axis), 0, 2)                  # (raises: a factor of 1 is refused like any other)
+        self._step_axis(h, int(axis), 0, int(factor))
+        return self._with_naxis(h, shape)
+
+    def _step_axis(self, h, axis, start, step):
+        """header *h* (edited in place) for numpy *axis* cut as ``[start::step]``, step >= 1: the start and step branches of
+        ``wcs_utils.slice_wcs`` (wcs_utils.py:309-334)"""
         n = self.naxis
-        i = n - 1 - int(axis)                   # 0-based FITS axis
+        i = n - 1 - axis                        # 0-based FITS axis
+        k = i + 1
+        crpix = float(h.get("CRPIX%d" % k, 0.0))
+        if step == 1:
+            h["CRPIX%d" % k] = crpix - start
+            return
         if i < 2 and self.sip_a is not None:
             raise NotImplementedError("downsampling a celestial axis of a WCS with SIP distortion is not built (the "
                                       "polynomial coefficients would have to be rescaled)")
-        h, k = dict(self.header), i + 1
-        f = float(factor)
-        h["CRPIX%d" % k] = (float(h.get("CRPIX%d" % k, 0.0)) - 0.5) / f + 0.5
+        f = float(step)
+        h["CRPIX%d" % k] = (crpix - start - 0.5) / f + 0.5
+        self._scale_column(h, i, f)
+
+    def _scale_column(self, h, i, f):
+        """pixel axis *i* (0-based FITS) made *f* times longer: CDELT where the axis has a column of its own, else the
+        column of the CD / PC matrix"""
+        n, k = self.naxis, i + 1
         has_pc = any(("PC%d_%d" % (a + 1, b + 1)) in h or ("PC%03d%03d" % (a + 1, b + 1)) in h for a in range(n) for b in range(n))
         has_cd = any(("CD%d_%d" % (a + 1, b + 1)) in h for a in range(n) for b in range(n))
         if has_cd and not has_pc:
@@ -592,10 +611,67 @@ class SimpleWCS:
                 h["PC%d_%d" % (a + 1, k)] = float(self.pc[a, i]) * f
         else:
             h["CDELT%d" % k] = float(h.get("CDELT%d" % k, 1.0)) * f
+
+    def _with_naxis(self, h, shape):
+        n = self.naxis
         if shape is not None:
             for a in range(n):
                 h["NAXIS%d" % (n - a)] = int(shape[a])
         return SimpleWCS(h, naxis=n, strict=False)
+
+    def sliced(self, view, shape):
+        """The WCS of ``cube[view]``: *view* a tuple of three slices (numpy order), *shape* the PARENT's shape;
+        ``wcs_utils.slice_wcs`` (wcs_utils.py:212-337) restated.  With ``start, stop, step = slice.indices(n)``:
+
+        * step 1: ``crpix -= start`` - result pixel k has the world coordinates of parent pixel ``start + k``;
+        * step > 1: ``crpix' = (crpix - start - 0.5) / step + 0.5`` and the pixel axis ``step`` times longer (CDELT, or the
+          axis' column of a CD / mixing PC matrix): result pixel k is the CENTRE of the parent pixels
+          ``start + k * step ... + step - 1``, i.e. parent pixel ``start + k * step + (step - 1) / 2``, the reference's
+          convention for a stepped view; ``downsampled(axis, f)`` is exactly ``slice(0, None, f)`` on that axis;
+        * step -1, spectral axis only: ``crpix = 1``, ``crval = world(start)``, ``cdelt = -cdelt`` - result pixel k is
+          parent pixel ``start - k``.
+
+        NotImplementedError: a negative step on a celestial axis (the reference fails in wcslib, "Unmatched celestial
+        axes"), a negative step other than -1 (reference: "Haven't dealt with resampling & reversing."), step > 1 on a
+        celestial axis with SIP distortion.  NAXISn are set to the new shape.
+
+        Two deliberate deviations, where the reference contradicts the samples it returns: a negative start
+        (``cube[-5:-1]``: the reference computes ``crpix - (-5)``; here start is normalised first) and a reversed view
+        with a stop (``cube[8:2:-1]``: the reference takes the world value of channel ``stop - 1`` for the first sample,
+        which is channel 8).  Both follow the rules above."""
+        if len(view) != self.naxis or len(shape) != self.naxis:
+            raise ValueError("sliced() needs one slice and one length per WCS axis")
+        h = dict(self.header)
+        new_shape = []
+        for axis, (sl, n) in enumerate(zip(view, shape)):
+            start, stop, step = sl.indices(int(n))
+            new_shape.append(len(range(start, stop, step)))
+            if step > 0:
+                self._step_axis(h, axis, start, step)
+                continue
+            if step != -1:
+                raise NotImplementedError("Haven't dealt with resampling & reversing.")
+            if self.naxis - 1 - axis != 2:
+                raise NotImplementedError("a reversed celestial axis is not built (the reference fails there as well: "
+                                          "wcslib reports unmatched celestial axes)")
+            h["CRVAL3"] = float(self.spectral_pix2world(start))
+            h["CRPIX3"] = 1.0
+            self._scale_column(h, 2, -1.0)
+        return self._with_naxis(h, new_shape)
+
+    def spectral_only(self):
+        """the spectral axis alone, as a 1-axis WCS: ``wcs.sub([3])`` of the 1-D spectrum ``cube[:, j, i]``
+        (spectral_cube.py:1334-1336).  Carries ``spectral_pix2world`` / ``spectral_world2pix`` of the cube's axis."""
+        self._require_linear_spectral()
+        scale = self.cdelt[2] * self.pc[2, 2]
+        h = {"WCSAXES": 1, "CTYPE1": self.ctype[2], "CUNIT1": self.cunit[2], "CRVAL1": float(self.crval[2]),
+             "CRPIX1": float(self.crpix[2]), "CDELT1": float(scale)}
+        for key in ("RESTFRQ", "RESTFREQ", "RESTWAV", "SPECSYS", "VELREF"):
+            if key in self.header:
+                h[key] = self.header[key]
+        if self.shape_hint and self.shape_hint[0]:
+            h["NAXIS1"] = int(self.shape_hint[0])
+        return SpectralAxisWCS(h)
 
     def to_header(self):
         h = {"WCSAXES": self.naxis}
@@ -609,6 +685,32 @@ class SimpleWCS:
                 if self.pc[i, j] != (1.0 if i == j else 0.0):
                     h["PC%d_%d" % (i + 1, j + 1)] = float(self.pc[i, j])
         return h
+
+
+class SpectralAxisWCS:
+    """1-axis linear WCS of a spectrum (``SimpleWCS.spectral_only``): world = crval + cdelt * (pix + 1 - crpix)"""
+
+    def __init__(self, header):
+        self.header = dict(header)
+        self.naxis = 1
+        self.ctype = [str(header.get("CTYPE1", ""))]
+        self.cunit = [str(header.get("CUNIT1", "")).strip()]
+        self.crval = np.array([float(header.get("CRVAL1", 0.0))])
+        self.crpix = np.array([float(header.get("CRPIX1", 0.0))])
+        self.cdelt = np.array([float(header.get("CDELT1", 1.0))])
+
+    @property
+    def spectral_unit(self):
+        return self.cunit[0]
+
+    def spectral_pix2world(self, pz):
+        return self.crval[0] + self.cdelt[0] * (np.asarray(pz, dtype=np.float64) + 1.0 - self.crpix[0])
+
+    def spectral_world2pix(self, w):
+        return (np.asarray(w, dtype=np.float64) - self.crval[0]) / self.cdelt[0] + self.crpix[0] - 1.0
+
+    def to_header(self):
+        return dict(self.header)
 
 
 # ---- celestial reference frames ---------------------------------------------------------------------
