@@ -834,25 +834,38 @@ class SpectralCube:
                 tok.dev64 = DeviceArray.from_numpy(self._data, self.device, dtype=np.float64)
         return tok.dev64
 
+    def _lower_mask(self, wide):
+        """the mask tree lowered for the float32 kernels or (*wide*) the float64 ones: thresholds in float64, host-evaluated
+        terms on the float64 samples.  The uint8 array term stays resident in HBM."""
+        view = _WideView if wide else (lambda cube: cube)
+        owner = M.foreign_owner(self._mask) if self._mask is not None else None
+        if isinstance(self._mask, M.DeviceBooleanMask) and tuple(self._mask.shape) == tuple(self._shape):
+            # computed on the device (downsample_axis, a cut): the kernels read its uint8 array where it is
+            return ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, self._mask.device_array())
+        if (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
+                and (not wide or getattr(owner, "_wide_resident", lambda: False)())
+                and self._mask._device_terms(view(owner)) is not None):
+            # every lazy term belongs to ANOTHER cube's data (a smoothed cube keeps its parent's mask): evaluate it there,
+            # on the device, on the samples of this path - no host copy of either cube
+            flags, lo, hi, arr = M.lower_mask(self._mask, view(owner), self._shape)
+            darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
+            inc = ops.mask_include(owner._device_data64() if wide else owner._device_data(), ops.MaskSpec(flags, lo, hi, darr),
+                                   nan_excluded=M.contains(self._mask, M.NotNaNMask))
+            return ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
+        flags, lo, hi, arr = M.lower_mask(self._mask, view(self), self._shape)
+        darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
+        return ops.MaskSpec(flags, lo, hi, darr)
+
+    def _mask_spec(self):
+        """the mask lowered for the float32 kernels, once"""
+        if self._mask_cache is None:
+            self._mask_cache = self._lower_mask(False)
+        return self._mask_cache
+
     def _mask_spec64(self):
-        """the mask lowered for the float64 kernels: thresholds in float64, host-evaluated terms on the float64 samples"""
+        """the mask lowered for the float64 kernels, once (both lowerings of one mask may be live)"""
         if self._mask64_cache is None:
-            owner = M.foreign_owner(self._mask) if self._mask is not None else None
-            if isinstance(self._mask, M.DeviceBooleanMask) and tuple(self._mask.shape) == tuple(self._shape):
-                self._mask64_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, self._mask.device_array())
-            elif (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
-                    and getattr(owner, "_wide_resident", lambda: False)() and self._mask._device_terms(_WideView(owner)) is not None):
-                # every lazy term belongs to ANOTHER float64 cube's data (a smoothed cube keeps its parent's mask):
-                # evaluated there, on the device, on the float64 samples (as _mask_spec does for float32 cubes)
-                flags, lo, hi, arr = M.lower_mask(self._mask, _WideView(owner), self._shape)
-                darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
-                inc = ops.mask_include_f64(owner._device_data64(), ops.MaskSpec(flags, lo, hi, darr),
-                                           nan_excluded=M.contains(self._mask, M.NotNaNMask))
-                self._mask64_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
-            else:
-                flags, lo, hi, arr = M.lower_mask(self._mask, _WideView(self), self._shape)
-                darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
-                self._mask64_cache = ops.MaskSpec(flags, lo, hi, darr)
+            self._mask64_cache = self._lower_mask(True)
         return self._mask64_cache
 
     def _runs_wide(self):
@@ -865,6 +878,27 @@ class SpectralCube:
             return self._stream_source() is None and self._wide_resident()
         except _lib.HipLibraryError:
             return False
+
+    def _operand(self, wide=None):
+        """(device data, lowered mask, view) for the path this cube's operators run on (*wide*: a decision of
+        ``_runs_wide()`` taken earlier): the float64 samples, the float64 lowering and ``_WideView(self)``, or the float32
+        ones and the cube itself.  The view is what ``_nan_term_dropped`` and the mask lowering evaluate against."""
+        if self._runs_wide() if wide is None else wide:
+            return self._device_data64(), self._mask_spec64(), _WideView(self)
+        return self._device_data(), self._mask_spec(), self
+
+    def _result_cube(self, run, wide, shape=None, wcs=None, mask=None, plain=False):
+        """the result cube of a cube -> cube operator, pending until first used: run() gives its DeviceArray, a float64 one
+        when *wide*.  *plain*: a SpectralCube whatever the subclass (no beams)."""
+        if wide:
+            return self._new_wide_cube(run, shape=shape, wcs=wcs, mask=mask, plain=plain)
+        make = (lambda **kw: SpectralCube._new_cube_with(self, **kw)) if plain else self._new_cube_with
+        return make(lazy=_Thunk(run), shape=tuple(shape) if shape is not None else self._shape, wcs=wcs, mask=mask)
+
+    def _derived(self, fn, **kw):
+        """_result_cube of *fn*(data, mask, view) applied to ``_operand()``, on the path decided now"""
+        wide = self._runs_wide()
+        return self._result_cube(lambda: fn(*self._operand(wide)), wide, **kw)
 
     def _new_wide_cube(self, fn64, shape=None, wcs=None, mask=None, plain=False):
         """the result of a float64 operator on this (wide, resident) cube: a cube whose values exist as a float64 DeviceArray
@@ -881,28 +915,6 @@ class SpectralCube:
         out._data_id.derived64 = True
         tokens.append(out._data_id)
         return out
-
-    def _mask_spec(self):
-        """lower the mask tree once and keep the uint8 array resident in HBM."""
-        if self._mask_cache is None:
-            owner = M.foreign_owner(self._mask) if self._mask is not None else None
-            if isinstance(self._mask, M.DeviceBooleanMask) and tuple(self._mask.shape) == tuple(self._shape):
-                # computed on the device (downsample_axis): the kernels read its uint8 array where it is
-                self._mask_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, self._mask.device_array())
-            elif (owner is not None and not owner._is_same_data(self) and tuple(owner._shape) == tuple(self._shape)
-                    and self._mask._device_terms(owner) is not None):
-                # every lazy term belongs to ANOTHER cube's data (a smoothed cube keeps its parent's mask):
-                # evaluate it there, on the device - no host copy of either cube
-                flags, lo, hi, arr = M.lower_mask(self._mask, owner, self._shape)
-                darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
-                inc = ops.mask_include(owner._device_data(), ops.MaskSpec(flags, lo, hi, darr),
-                                       nan_excluded=M.contains(self._mask, M.NotNaNMask))
-                self._mask_cache = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
-            else:
-                flags, lo, hi, arr = M.lower_mask(self._mask, self, self._shape)
-                darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
-                self._mask_cache = ops.MaskSpec(flags, lo, hi, darr)
-        return self._mask_cache
 
     @property
     def filled_data(self):
@@ -1248,10 +1260,9 @@ class SpectralCube:
             if self._stream_source() is not None:
                 from . import streaming
                 st = streaming.statistics(self)
-            elif self._wide_resident():
-                st = ops.stats_global_f64(self._device_data64(), mask=self._mask_spec64())
             else:
-                st = ops.stats_global(self._device_data(), mask=self._mask_spec())
+                data, mask, _ = self._operand()
+                st = ops.stats_global(data, mask=mask)
             n = st["npts"]
             vals = {"count": np.float64(n), "sum": np.float64(st["sum"]), "sumsq": np.float64(st["sumsq"]),
                     "max": np.float64(st["max"]), "min": np.float64(st["min"])}
@@ -1299,9 +1310,8 @@ class SpectralCube:
         if self._stream_source() is not None:          # out of core: strips (axis 0) or slabs of planes (axis 1 / 2)
             from . import streaming
             return streaming.stats_axis(self, axis, need)
-        if self._wide_resident():
-            return ops.stats_axis_f64(self._device_data64(), axis, mask=self._mask_spec64(), want=need)
-        return ops.stats_axis(self._device_data(), axis, mask=self._mask_spec(), want=need)
+        data, mask, _ = self._operand()
+        return ops.stats_axis(data, axis, mask=mask, want=need)
 
     def _finish_reduce(self, op, vals, axis, ddof=0):
         n = vals["count"]
@@ -1345,10 +1355,11 @@ class SpectralCube:
             raise ValueError("axis must be None, 0, 1 or 2")
         if axis in (0, 1) and self._shape[axis] <= 4096 and self._runs_wide():
             # a float64 cube: sorted rays of float64 keys (spc_percentile_axis0_f64), a float64 map
-            d64, ms = self._device_data64(), self._mask_spec64()
+            # (longer rays have no float64 kernel: they go the float32 way below, with a PrecisionWarning)
+            d64, ms, _ = self._operand(True)
             if axis == 1:
                 d64, ms = d64.swap01(), ms.swap01()
-            return ops.percentile_axis0_f64(d64, q, mask=ms, center=center, scale=scale)
+            return ops.percentile_axis0(d64, q, mask=ms, center=center, scale=scale)
         if axis in (1, 2) and self._stream_source() is not None:
             # out of core: the rays along y / x are whole in a slab of channels; row z of the (nz, nx) / (nz, ny) map per slab row
             from . import streaming
@@ -1442,10 +1453,8 @@ class SpectralCube:
         if self._stream_source() is not None:
             from . import streaming
             return streaming.statistics(self)           # per-strip records, combined (same formulae)
-        if self._wide_resident():
-            st = ops.stats_global_f64(self._device_data64(), mask=self._mask_spec64())
-        else:
-            st = ops.stats_global(self._device_data(), mask=self._mask_spec())
+        data, mask, _ = self._operand()
+        st = ops.stats_global(data, mask=mask)
         n = st["npts"]
         with np.errstate(invalid="ignore", divide="ignore"):
             st["mean"] = st["sum"] / n if n else np.nan
@@ -1498,19 +1507,14 @@ class SpectralCube:
         def run():
             # (a ~isnan mask of the parent's own data lowers to no term: the kernel is told to exclude NaN samples, which the
             # reference fills with fill_value and leaves out of the new mask)
-            if wide:
-                return ops.downsample_f64(parent._device_data64(), axis, factor, truncate, est, fill, mask=parent._mask_spec64(),
-                                          nan_excluded=_nan_term_dropped(parent, _WideView(parent)))
-            if parent._stream_source() is not None:
+            if not wide and parent._stream_source() is not None:
                 return _downsample_streamed(parent, axis, factor, truncate, est, fill, shape)
-            return ops.downsample(parent._device_data(), axis, factor, truncate, est, fill, mask=parent._mask_spec(),
-                                  nan_excluded=_nan_term_dropped(parent, parent))
+            data, mask, view = parent._operand(wide)
+            return ops.downsample(data, axis, factor, truncate, est, fill, mask=mask, nan_excluded=_nan_term_dropped(parent, view))
 
         result = _Once(run)
         mask = M.DeviceBooleanMask(lambda: result()[1], wcs=newwcs, shape=shape)
-        if wide:
-            return self._new_wide_cube(lambda: result()[0], shape=shape, wcs=newwcs, mask=mask)
-        return self._new_cube_with(lazy=_Thunk(lambda: result()[0]), shape=shape, wcs=newwcs, mask=mask)
+        return self._result_cube(lambda: result()[0], wide, shape=shape, wcs=newwcs, mask=mask)
 
     # ---- cutting: slicing, spectral_slab, subcube, minimal_subcube ---------------------------------
     def _normalize_view(self, view):
@@ -1575,17 +1579,15 @@ class SpectralCube:
         """(data, include or None) of the view on the device, in the cube's dtype path"""
         starts, steps = [a[0] for a in spec], [a[1] for a in spec]
         has_mask = self._mask is not None
-        if self._runs_wide():
-            return ops.subcube_f64(self._device_data64(), starts, steps, shape, mask=self._mask_spec64() if has_mask else None,
-                                   want_mask=has_mask, filled=filled, fill=self._fill_value,
-                                   nan_excluded=_nan_term_dropped(self, _WideView(self)))
-        if self._stream_source() is not None:
+        wide = self._runs_wide()
+        if not wide and self._stream_source() is not None:
             data, inc = _subcube_streamed(self, spec, shape, has_mask)
             if filled and has_mask:
                 data = ops.fill_masked(data, ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc), self._fill_value)
             return data, inc
-        return ops.subcube(self._device_data(), starts, steps, shape, mask=self._mask_spec() if has_mask else None,
-                           want_mask=has_mask, filled=filled, fill=self._fill_value, nan_excluded=_nan_term_dropped(self, self))
+        data, mask, view = self._operand(wide)
+        return ops.subcube(data, starts, steps, shape, mask=mask if has_mask else None, want_mask=has_mask, filled=filled,
+                           fill=self._fill_value, nan_excluded=_nan_term_dropped(self, view))
 
     def _cut_finish(self, new, view):
         return new
@@ -1608,10 +1610,7 @@ class SpectralCube:
                 _check_cut_fits(self, shape, has_mask)
         result = _Once(lambda: parent._gather(spec, shape))
         mask = M.DeviceBooleanMask(lambda: result()[1], wcs=newwcs, shape=shape) if has_mask else None
-        if wide:
-            new = self._new_wide_cube(lambda: result()[0], shape=shape, wcs=newwcs, mask=mask, plain=True)
-        else:
-            new = SpectralCube._new_cube_with(self, lazy=_Thunk(lambda: result()[0]), shape=shape, wcs=newwcs, mask=mask)
+        new = self._result_cube(lambda: result()[0], wide, shape=shape, wcs=newwcs, mask=mask, plain=True)
         new._meta = meta
         return self._cut_finish(new, view)
 
@@ -1748,13 +1747,12 @@ class SpectralCube:
                 self._device_data()                     # a pending cube is materialised once and shared with the probe
             probe = SpectralCube._new_cube_with(self, data=self._data, dev=self._dev, mask=region_mask, lazy=self._lazy,
                                                 shape=self._shape, same_data=True)
-        if probe._runs_wide():
-            box = ops.mask_bbox_f64(probe._device_data64(), mask=probe._mask_spec64(),
-                                    nan_excluded=_nan_term_dropped(probe, _WideView(probe)))
-        elif probe._stream_source() is not None:
+        wide = probe._runs_wide()
+        if not wide and probe._stream_source() is not None:
             box = _bbox_streamed(probe)
         else:
-            box = ops.mask_bbox(probe._device_data(), mask=probe._mask_spec(), nan_excluded=_nan_term_dropped(probe, probe))
+            data, mask, view = probe._operand(wide)
+            box = ops.mask_bbox(data, mask=mask, nan_excluded=_nan_term_dropped(probe, view))
         if box is None:
             return (slice(0),) * 3
         slices = tuple(slice(lo, hi + 1) for lo, hi in box)
@@ -1792,8 +1790,9 @@ class SpectralCube:
         _check_convolve(convolve)
         parent = self
         if self._runs_wide():
-            # a float64 cube stays float64 (the Dask class keeps the chunk dtype, dask_spectral_cube.py:829)
-            return self._new_wide_cube(lambda: ops.spectral_conv_f64(parent._device_data64(), karr, mask=parent._mask_spec64()))
+            # a float64 cube stays float64 (the Dask class keeps the chunk dtype, dask_spectral_cube.py:829) and is resident:
+            # none of what the float32 class below carries for a following moment or an out-of-core parent applies
+            return self._derived(lambda data, mask, view: ops.spectral_conv(data, karr, mask=mask))
 
         class _Lazy:
             op = "spectral_smooth"
@@ -1823,8 +1822,8 @@ class SpectralCube:
         if arithmetic is not None and arithmetic not in ops.MASKED_SPATIAL_ARITHMETIC:
             raise ValueError("arithmetic must be one of %r, got %r" % (ops.MASKED_SPATIAL_ARITHMETIC, arithmetic))
         parent = self
-        if self._runs_wide():
-            return self._new_wide_cube(lambda: ops.spatial_conv_f64(parent._device_data64(), karr, mask=parent._mask_spec64()))
+        if self._runs_wide():        # (resident: no strip / slab form; the float64 stencils have one arithmetic)
+            return self._derived(lambda data, mask, view: ops.spatial_conv(data, karr, mask=mask))
 
         class _Lazy:
             op = "spatial_smooth"
@@ -1883,13 +1882,11 @@ class SpectralCube:
         karr = beam.deconvolve(self.beam).as_kernel(pixscale)
         is_jybm = str(self._unit).replace(" ", "").upper() in ("JY/BEAM", "JYBEAM-1", "JY/BM")
         ratio = beam.sr / self.beam.sr if is_jybm else 1.0
-        if self._runs_wide():
-            parent = self
-
-            def run64():
-                res = ops.spatial_conv_f64(parent._device_data64(), karr, mask=parent._mask_spec64())
-                return ops.scale_inplace_f64(res, ratio) if ratio != 1.0 else res
-            return self._new_wide_cube(run64).with_beam(beam, raise_error_jybm=False)
+        def run(data, mask, view=None):
+            res = ops.spatial_conv(data, karr, mask=mask)
+            return ops.scale_inplace(res, ratio) if ratio != 1.0 else res
+        if self._runs_wide():        # (pending, like every float64 result; the float32 result below is made at once)
+            return self._derived(run).with_beam(beam, raise_error_jybm=False)
         if self._stream_source() is not None:
             # out of core: one kernel for every channel, so slabs of whole planes; pending until write() / stream_into()
             parent = self
@@ -1902,10 +1899,7 @@ class SpectralCube:
             thunk = _Thunk(lambda: parent._device_data())           # (never resident: raises HugeCubeError with the budget)
             thunk.parent, thunk.slab_fn, thunk.keeps_mask = parent, slab, True
             return self._new_cube_with(lazy=thunk, shape=self._shape).with_beam(beam, raise_error_jybm=False)
-        dev = ops.spatial_conv(self._device_data(), karr, mask=self._mask_spec())
-        if ratio != 1.0:
-            ops.scale_inplace(dev, ratio)
-        new = self._new_cube_with(dev=dev)
+        new = self._new_cube_with(dev=run(self._device_data(), self._mask_spec()))
         return new.with_beam(beam, raise_error_jybm=False)
 
     def check_jybeam_smoothing(self, raise_error_jybm=True):
@@ -1954,11 +1948,11 @@ class SpectralCube:
         cdelt = outdiff if not rout else -outdiff
         newwcs = self._wcs.with_spectral(crval, cdelt, 1.0)
         if self._runs_wide():
-            out = self._new_wide_cube(lambda: ops.spectral_lerp_f64(parent._device_data64(), plan[0], plan[1], plan[2], fill,
-                                                                    mask=parent._mask_spec64()),
-                                      shape=(len(grid),) + self._shape[1:], wcs=newwcs, mask=False)
+            out = self._derived(lambda data, mask, view: ops.spectral_lerp(data, plan[0], plan[1], plan[2], fill, mask=mask),
+                                shape=(len(grid),) + self._shape[1:], wcs=newwcs, mask=False)
             out._mask = M.NotNaNMask(out)
             return out
+        # float32: the thunk also carries what a following reproject and an out-of-core parent need
         thunk = _Thunk(run)
         thunk.parent = parent
         thunk.lerp = (plan, fill)          # (a following reproject folds the interpolation into its resampling kernel)
@@ -2051,9 +2045,9 @@ class SpectralCube:
             fillv = float(self._fill_value)
             if filled and not np.isnan(fillv) and self._mask is not None and M.contains(self._mask, M.NotNaNMask) \
                     and not M.contains(self._mask, M.InvertedMask):
-                inc = ops.mask_include_f64(self._device_data64(), mask64, nan_excluded=True)
+                inc = ops.mask_include(self._device_data64(), mask64, nan_excluded=True)
                 mask64 = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
-            dev64, foot = ops.resample_bilinear_f64(self._device_data64(), xs, ys, fill=fillv, mask=mask64, order=order, any_valid=flag)
+            dev64, foot = ops.resample_bilinear(self._device_data64(), xs, ys, fill=fillv, mask=mask64, order=order, any_valid=flag)
             footprint = foot.get().astype(bool)
             valid3d = footprint[None]
             nothing = int(flag.get()[0]) == 0
@@ -2061,7 +2055,7 @@ class SpectralCube:
                 inside = (zs >= -0.5) & (zs <= nz - 0.5)
                 zc = np.clip(np.where(inside, zs, 0.0), 0.0, nz - 1.0)
                 z0 = np.minimum(np.floor(zc).astype(np.int64), nz - 2)
-                dev64 = ops.spectral_lerp_f64(dev64, np.where(inside, z0, -1).astype(np.int32), zc - z0, np.ones(len(zs)), np.nan)
+                dev64 = ops.spectral_lerp(dev64, np.where(inside, z0, -1).astype(np.int32), zc - z0, np.ones(len(zs)), np.nan)
                 if not inside.all():
                     valid3d = footprint[None] & inside[:, None, None]
                 nothing = nothing or not inside.any()
@@ -2350,19 +2344,21 @@ class VaryingResolutionSpectralCube(SpectralCube):
             else:
                 plans.append((bm, dk.as_kernel(pixscale), beam.sr / bm.sr if is_jybm else 1.0))
         def runs(src, spec, zbase, stream=None):
-            """channels zbase .. of the cube held in `src` (their mask in `spec`): runs of channels that share a plan, one launch each"""
+            """channels zbase .. of the cube held in `src` (their mask in `spec`): runs of channels that share a plan, one launch
+            each, in the dtype of `src`"""
             n = src.shape[0]
-            out = DeviceArray(src.shape, np.float32, self.device)
+            out = DeviceArray(src.shape, src.dtype, self.device)
             a = 0
             while a < n:
                 b = a + 1
                 while b < n and plans[zbase + b] is plans[zbase + a]:
                     b += 1
                 o, m = out.planes(a, b), (spec.planes(a, b) if spec is not None else None)
-                if plans[zbase + a] is None:
+                if plans[zbase + a] is None and src.dtype == np.float32:
                     ops.fill_masked(src.planes(a, b), m, np.nan, out=o, stream=stream)
                 else:
-                    _, karr, ratio = plans[zbase + a]
+                    # (fill_masked has no float64 form: a float64 pass-through channel = the 1 x 1 kernel, the filled sample)
+                    _, karr, ratio = plans[zbase + a] or (None, np.ones((1, 1)), 1.0)
                     ops.spatial_conv(src.planes(a, b), karr, mask=m, out=o, stream=stream)
                     if ratio != 1.0:
                         ops.scale_inplace(o, ratio, stream=stream)
@@ -2370,29 +2366,8 @@ class VaryingResolutionSpectralCube(SpectralCube):
             return out
 
         if self._runs_wide():
-            # a float64 cube: the same runs on the float64 samples (a pass-through channel = the 1 x 1 kernel: the filled sample)
-            parent, dev_ = self, self.device
-
-            def run64():
-                src, spec = parent._device_data64(), parent._mask_spec64()
-                n = src.shape[0]
-                out = DeviceArray(src.shape, np.float64, dev_)
-                a = 0
-                while a < n:
-                    b = a + 1
-                    while b < n and plans[b] is plans[a]:
-                        b += 1
-                    o, m = out.planes(a, b), (spec.planes(a, b) if spec is not None else None)
-                    if plans[a] is None:
-                        ops.spatial_conv_f64(src.planes(a, b), np.ones((1, 1)), mask=m, out=o)
-                    else:
-                        _, karr, ratio = plans[a]
-                        ops.spatial_conv_f64(src.planes(a, b), karr, mask=m, out=o)
-                        if ratio != 1.0:
-                            ops.scale_inplace_f64(o, ratio)
-                    a = b
-                return out
-            return self._new_wide_cube(run64, plain=True).with_beam(beam, raise_error_jybm=False)
+            # a float64 cube: the same runs on the float64 samples
+            return self._derived(lambda data, mask, view: runs(data, mask, 0), plain=True).with_beam(beam, raise_error_jybm=False)
         if self._stream_source() is not None:
             # out of core: slabs of whole planes (every channel has its own kernel, the slab knows its first channel);
             # pending until write() / stream_into()

@@ -25,24 +25,9 @@ class MaskSpec:
     thr_hi: float = 0.0
     array: Optional[DeviceArray] = None      # uint8, same shape as the cube
 
-    def to_c(self):
-        m = _lib.SpcMask()
-        m.flags = self.flags
-        m.thr_lo = self.thr_lo
-        m.thr_hi = self.thr_hi
-        m.row_stride = 0
-        m.plane_stride = 0
-        if self.flags & _lib.MASK_ARRAY:
-            if self.array is None:
-                raise ValueError("MASK_ARRAY set without an array")
-            m.d_array = self.array.ptr
-            m.row_stride = getattr(self.array, "row_stride", 0)
-            m.plane_stride = getattr(self.array, "plane_stride", 0)
-        return m
-
-    def to_c64(self):
-        """spc_mask_f64: the thresholds as they are (a float64 cube is compared in float64)"""
-        m = _lib.SpcMask64()
+    def to_c(self, wide=False):
+        """spc_mask_f32, or (*wide*) spc_mask_f64: the thresholds as they are (a float64 cube is compared in float64)"""
+        m = _lib.SpcMask64() if wide else _lib.SpcMask()
         m.flags, m.thr_lo, m.thr_hi = self.flags, self.thr_lo, self.thr_hi
         m.row_stride = m.plane_stride = 0
         if self.flags & _lib.MASK_ARRAY:
@@ -68,9 +53,15 @@ class MaskSpec:
                         self.array.planes(z0, z1) if self.array is not None else None)
 
 
-def _cube_c(cube):
-    if cube.dtype != np.float32 or len(cube.shape) != 3:
-        raise TypeError("cube must be a float32 DeviceArray of shape (nz, ny, nx)")
+_F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
+
+
+def _cube_c(cube, dtype=None):
+    """spc_cube_f32 / spc_cube_f64 (one layout) of a float32 or float64 cube; *dtype*: the one sample type an operator
+    without the other form takes"""
+    ok = (_F32, _F64) if dtype is None else (dtype,)
+    if cube.dtype not in ok or len(cube.shape) != 3:
+        raise TypeError("cube must be a %s DeviceArray of shape (nz, ny, nx)" % " or ".join(d.name for d in ok))
     c = _lib.SpcCube()
     c.d_data = cube.ptr
     c.nz, c.ny, c.nx = cube.shape
@@ -85,7 +76,15 @@ def _mask_c(mask, cube):
     if mask.array is not None:
         if mask.array.shape != cube.shape or mask.array.dtype.itemsize != 1:
             raise ValueError("mask array must be 1-byte and match the cube shape")
-    return mask.to_c()
+    return mask.to_c(wide=cube.dtype == _F64)
+
+
+def _entry(base, cube, f32="_f32"):
+    """(exported symbol, output dtype) of operator *base* on *cube*: spc_<base>_f32 and float32, or spc_<base>_f64 and
+    float64 for a float64 cube (the reference keeps a float64 cube in float64, masks.py:225)"""
+    if cube.dtype == _F64:
+        return "spc_%s_f64" % base, _F64
+    return "spc_%s%s" % (base, f32), _F32
 
 
 def _kern(k):
@@ -169,7 +168,7 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
     ws = workspace
     if need and (ws is None or ws.nbytes < need):
         ws = DeviceArray((need,), np.uint8, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     _lib.call("spc_moments_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
               float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
               ws.nbytes if ws is not None else 0)
@@ -178,25 +177,6 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
 
 
 _WANT_F64 = ("m0", "m1", "m2", "mu", "s0", "argmax", "argmin", "vmax", "vmin", "nvalid")
-
-
-def _cube_c64(cube):
-    if cube.dtype != np.float64 or len(cube.shape) != 3:
-        raise TypeError("cube must be a float64 DeviceArray of shape (nz, ny, nx)")
-    c = _lib.SpcCube()
-    c.d_data = cube.ptr
-    c.nz, c.ny, c.nx = cube.shape
-    c.row_stride = getattr(cube, "row_stride", cube.shape[2])
-    c.plane_stride = getattr(cube, "plane_stride", cube.shape[1] * cube.shape[2])
-    return c
-
-
-def _mask_c64(mask, cube):
-    if mask is None:
-        mask = MaskSpec()
-    if mask.array is not None and (mask.array.shape != cube.shape or mask.array.dtype.itemsize != 1):
-        raise ValueError("mask array must be 1-byte and match the cube shape")
-    return mask.to_c64()
 
 
 def moments_f64(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=("m0", "m1", "m2"), stream=None):
@@ -220,7 +200,7 @@ def moments_f64(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=("m0", "m1", "m2"
         bufs[name] = DeviceArray((ny, nx), types[name], cube.device)
         setattr(o, "d_" + name, bufs[name].ptr)
     o.out_row_stride = 0
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
+    c, m = _cube_c(cube, _F64), _mask_c(mask, cube)
     _lib.call("spc_moments_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr), float(dv), float(m1_add), C.byref(o))
     if "m2" in want:
         bufs["m2"] = moment_order_f64(cube, cen, 2, bufs["mu"], bufs["s0"], mask=mask, stream=stream)
@@ -231,124 +211,9 @@ def moment_order_f64(cube, cen, order, mu, s0, mask=None, stream=None):
     """sum v (c - mu)^order / S0 of a float64 cube (dask_spectral_cube.py:1094-1099; _moments.py:185-193)"""
     nz, ny, nx = cube.shape
     out = DeviceArray((ny, nx), np.float64, cube.device)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
+    c, m = _cube_c(cube, _F64), _mask_c(mask, cube)
     _lib.call("spc_moment_order_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr), int(order),
               C.c_void_p(mu.ptr), C.c_void_p(s0.ptr), C.c_void_p(out.ptr), 0)
-    return out
-
-
-# ---- the other operators of a float64 cube (spc_wide_ops.hip; the reference keeps float64, masks.py:225) -------------------
-def stats_global_f64(cube, mask=None, stream=None):
-    """stats_global of a float64 cube (spc_stats_global_f64): min / max are float64 samples, thresholds compared in float64"""
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    h = (C.c_double * 5)()
-    ws, wsn = workspace(cube.device, stream, _lib.WS_STATS_GLOBAL_F64, *cube.shape)
-    _lib.call("spc_stats_global_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), h, ws, wsn)
-    return {"npts": h[0], "min": h[1], "max": h[2], "sum": h[3], "sumsq": h[4]}
-
-
-def stats_axis_f64(cube, axis, mask=None, want=("count", "min", "max", "sum", "sumsq"), stream=None):
-    """stats_axis of a float64 cube (spc_stats_axis_f64): every map but the int32 count is float64"""
-    if axis not in (0, 1, 2):
-        raise ValueError("axis must be 0, 1 or 2")
-    shp = tuple(n for i, n in enumerate(cube.shape) if i != axis)
-    res = {k: DeviceArray(shp, np.int32 if k == "count" else np.float64, cube.device) for k in want}
-    o = _lib.SpcStatsOutputs()
-    for k in want:
-        setattr(o, "d_" + k, res[k].ptr)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_stats_axis_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis), C.byref(o))
-    return res
-
-
-def spectral_conv_f64(cube, kernel1d, mask=None, out=None, stream=None):
-    """spectral_conv of a float64 cube: float64 in, float64 out (the Dask class keeps the chunk dtype,
-    dask_spectral_cube.py:829, :880-917)"""
-    if out is None:
-        out = DeviceArray(cube.shape, np.float64, cube.device)
-    k = np.ascontiguousarray(kernel1d, dtype=np.float64)
-    if k.ndim != 1:
-        raise ValueError("kernel must be 1-D")
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    ws, wsn = workspace(cube.device, stream, _lib.WS_SPECTRAL_CONV_F64, *cube.shape, len(k))
-    _lib.call("spc_spectral_conv_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), k.ctypes.data_as(C.POINTER(C.c_double)),
-              len(k), C.c_void_p(out.ptr), 0, 0, ws, wsn)
-    return out
-
-
-def spatial_conv_f64(cube, kernel2d, mask=None, out=None, stream=None):
-    """spatial_conv of a float64 cube (dask_spectral_cube.py:962-993): an outer-product kernel in two passes, any other
-    kernel summed directly"""
-    if out is None:
-        out = DeviceArray(cube.shape, np.float64, cube.device)
-    k2 = np.ascontiguousarray(kernel2d, dtype=np.float64)
-    if k2.ndim != 2:
-        raise ValueError("kernel must be 2-D")
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    sep = separable_factors(k2)
-    ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV_F64, *cube.shape, k2.shape[0], k2.shape[1])
-    if sep is not None:
-        ky, kx = (np.ascontiguousarray(f, dtype=np.float64) for f in sep)
-        _lib.call("spc_spatial_conv_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), ky.ctypes.data_as(C.POINTER(C.c_double)),
-                  len(ky), kx.ctypes.data_as(C.POINTER(C.c_double)), len(kx), 1, C.c_void_p(out.ptr), 0, 0, ws, wsn)
-    else:
-        _lib.call("spc_spatial_conv_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), k2.ctypes.data_as(C.POINTER(C.c_double)),
-                  k2.shape[0], None, k2.shape[1], 0, C.c_void_p(out.ptr), 0, 0, ws, wsn)
-    return out
-
-
-def spectral_lerp_f64(cube, lo, t, inv_dx, fill=np.nan, mask=None, out=None, stream=None):
-    """spectral_lerp of a float64 cube (scipy's interp1d on float64 samples, dask_spectral_cube.py:1342-1353)"""
-    nz_out = len(lo)
-    dev = cube.device
-    d_lo = DeviceArray.from_numpy(np.asarray(lo, dtype=np.int32), dev)
-    d_t = DeviceArray.from_numpy(np.asarray(t, dtype=np.float64), dev)
-    d_inv = DeviceArray.from_numpy(np.asarray(inv_dx, dtype=np.float64), dev)
-    if out is None:
-        out = DeviceArray((nz_out,) + cube.shape[1:], np.float64, dev)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_spectral_lerp_f64", dev, _sh(stream), C.byref(c), C.byref(m), nz_out, C.c_void_p(d_lo.ptr), C.c_void_p(d_t.ptr),
-              C.c_void_p(d_inv.ptr), float(fill), C.c_void_p(out.ptr), 0, 0)
-    out._plan = (d_lo, d_t, d_inv)
-    return out
-
-
-def resample_bilinear_f64(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_footprint=True, order=1, any_valid=None):
-    """resample_bilinear of a float64 cube (spc_resample_bilinear_f64): float64 weights, float64 result"""
-    dev = cube.device
-    if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
-        d_xs, d_ys = xs, ys
-        ny_out, nx_out = xs.shape
-    else:
-        xs = np.ascontiguousarray(xs, dtype=np.float64)
-        ys = np.ascontiguousarray(ys, dtype=np.float64)
-        ny_out, nx_out = xs.shape
-        d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
-    out = DeviceArray((cube.shape[0], ny_out, nx_out), np.float64, dev)
-    foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_resample_bilinear_f64", dev, _sh(stream), C.byref(c), C.byref(m), float(fill), ny_out, nx_out,
-              C.c_void_p(d_xs.ptr), C.c_void_p(d_ys.ptr), C.c_void_p(out.ptr), 0, 0,
-              C.c_void_p(foot.ptr) if foot is not None else None, int(order),
-              C.c_void_p(any_valid.ptr) if any_valid is not None else None)
-    out._plan = (d_xs, d_ys)
-    return out, foot
-
-
-def scale_inplace_f64(arr, factor, stream=None):
-    """arr *= factor for a float64 DeviceArray (spc_scale_f64)"""
-    _lib.call("spc_scale_f64", arr.device, _sh(stream), C.c_void_p(arr.ptr), int(np.prod(arr.shape, dtype=np.int64)), float(factor))
-    return arr
-
-
-def percentile_axis0_f64(cube, q, mask=None, center=None, scale=1.0, stream=None):
-    """percentile_axis0 of a float64 cube (spc_percentile_axis0_f64): float64 map; *center* a float64 (ny, nx) DeviceArray.
-    Rays along y: the swap01() view (as for the float32 kernel).  HipUnsupported beyond 4096 samples per ray."""
-    nz, ny, nx = cube.shape
-    out = DeviceArray((ny, nx), np.float64, cube.device)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_percentile_axis0_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
-              C.c_void_p(center.ptr) if center is not None else None, float(scale), C.c_void_p(out.ptr))
     return out
 
 
@@ -358,7 +223,7 @@ def sigma_clip_axis0_f64(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, ma
     if cenfunc not in ("median", "mean") or stdfunc not in ("std", "mad_std"):
         raise ValueError("cenfunc must be 'median' or 'mean', stdfunc 'std' or 'mad_std'")
     out = DeviceArray(cube.shape, np.float64, cube.device)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
+    c, m = _cube_c(cube, _F64), _mask_c(mask, cube)
     lo = float(sigma if sigma_lower is None else sigma_lower)
     hi = float(sigma if sigma_upper is None else sigma_upper)
     _lib.call("spc_sigma_clip_axis0_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), lo, hi,
@@ -369,16 +234,8 @@ def sigma_clip_axis0_f64(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, ma
 def narrow_f64(cube, stream=None):
     """float32 copy of a float64 DeviceArray (for the operators without a float64 form)"""
     out = DeviceArray(cube.shape, np.float32, cube.device)
-    c = _cube_c64(cube)
+    c = _cube_c(cube, _F64)
     _lib.call("spc_narrow_f64_to_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(out.ptr), 0, 0)
-    return out
-
-
-def mask_include_f64(cube, mask=None, nan_excluded=False, stream=None):
-    """mask_include on a float64 cube (spc_mask_include_f64)"""
-    out = DeviceArray(cube.shape, np.uint8, cube.device)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_mask_include_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(out.ptr))
     return out
 
 
@@ -400,7 +257,7 @@ def argextrema_axis(cube, axis, mask=None, want=("argmax", "argmin"), stream=Non
         raise ValueError("axis must be 1 or 2 (axis 0 comes out of ops.moments)")
     shape = (nz, nx) if axis == 1 else (nz, ny)
     bufs = {n: _given(out, n, shape, np.int64, cube.device) for n in want if n in ("argmax", "argmin")}
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ptr = lambda n: C.c_void_p(bufs[n].ptr) if n in bufs else None  # noqa: E731
     _lib.call("spc_argextrema_axis_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis),
               ptr("argmin"), ptr("argmax"))
@@ -412,7 +269,7 @@ def moment_order(cube, cen, order, mu, s0, mask=None, stream=None):
     (dask_spectral_cube.py:1094-1099)."""
     nz, ny, nx = cube.shape
     out = DeviceArray((ny, nx), np.float64, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     _lib.call("spc_moment_order_f32", cube.device, _sh(stream), C.byref(c), C.byref(m),
               C.c_void_p(cen.ptr), int(order), C.c_void_p(mu.ptr), C.c_void_p(s0.ptr),
               C.c_void_p(out.ptr), 0)
@@ -427,7 +284,7 @@ def moments_spatial(cube, cen2d, axis, pix_size, mask=None, want=_WANT_ALL, stre
         raise ValueError("axis must be 1 or 2")
     shape = (nz, nx) if axis == 1 else (nz, ny)
     bufs = {n: _given(out, n, shape, np.float64, cube.device) for n in want}
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ptr = lambda n: C.c_void_p(bufs[n].ptr) if n in bufs else None  # noqa: E731
     _lib.call("spc_moments_spatial_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis),
               C.c_void_p(cen2d.ptr), float(pix_size), ptr("m0"), ptr("m1"), ptr("m2"))
@@ -441,7 +298,7 @@ def moment_order_spatial(cube, cen2d, axis, order, mu, mask=None, stream=None, o
     if axis not in (1, 2):
         raise ValueError("axis must be 1 or 2")
     out = _given({"o": out} if out is not None else None, "o", (nz, nx) if axis == 1 else (nz, ny), np.float64, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     _lib.call("spc_moment_order_spatial_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis),
               C.c_void_p(cen2d.ptr), int(order), C.c_void_p(mu.ptr), C.c_void_p(out.ptr))
     return out
@@ -449,13 +306,16 @@ def moment_order_spatial(cube, cen2d, axis, order, mu, mask=None, stream=None, o
 
 def spectral_conv(cube, kernel1d, mask=None, out=None, stream=None):
     """NaN-aware convolution along the spectral axis = chunk function of
-    spectral_smooth (dask_spectral_cube.py:880-917)."""
+    spectral_smooth (dask_spectral_cube.py:880-917); the result has the cube's dtype (the Dask class keeps the chunk
+    dtype, dask_spectral_cube.py:829)."""
+    name, dtype = _entry("spectral_conv", cube)
     if out is None:
-        out = DeviceArray(cube.shape, np.float32, cube.device)
+        out = DeviceArray(cube.shape, dtype, cube.device)
     k, kp = _kern(kernel1d)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    ws, wsn = workspace(cube.device, stream, _lib.WS_SPECTRAL_CONV, *cube.shape, len(k))
-    _lib.call("spc_spectral_conv_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), kp, len(k),
+    # (the float64 kernel sizes its scratch by its own kind)
+    ws, wsn = workspace(cube.device, stream, _lib.WS_SPECTRAL_CONV_F64 if dtype == _F64 else _lib.WS_SPECTRAL_CONV, *cube.shape, len(k))
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), kp, len(k),
               C.c_void_p(out.ptr), 0, 0, ws, wsn)
     return out
 
@@ -490,24 +350,14 @@ def downsample(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fi
                stream=None, nan_excluded=False):
     """(data, include) of the cube block-downsampled along *axis* = SpectralCube.downsample_axis's in-memory form
     (spectral_cube.py:3466-3497): estimator (an SPC_DS_* code) over every run of *factor* filled samples, and any(include)
-    over the run's voxels, as a float32 and a uint8 DeviceArray.  *out* / *out_mask* may be strided views (rows() /
+    over the run's voxels, as a DeviceArray of the cube's dtype and a uint8 one.  *out* / *out_mask* may be strided views (rows() /
     planes()) of larger outputs: a strip is written in place.  *nan_excluded*: NaN samples count as excluded (the
     ~isnan mask of the cube's own data, which lowers to no MaskSpec term)."""
-    out, out_mask = _downsample_outputs(cube, axis, factor, truncate, np.float32, out, out_mask)
+    name, dtype = _entry("downsample", cube)
+    out, out_mask = _downsample_outputs(cube, axis, factor, truncate, dtype, out, out_mask)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     ors, ops_ = _strides(out)
-    _lib.call("spc_downsample_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
-              int(axis), int(factor), 1 if truncate else 0, int(estimator), C.c_void_p(out.ptr), ors, ops_, C.c_void_p(out_mask.ptr))
-    return out, out_mask
-
-
-def downsample_f64(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fill=np.nan, mask=None, out=None, out_mask=None,
-                   stream=None, nan_excluded=False):
-    """downsample of a float64 cube: float64 in, float64 out"""
-    out, out_mask = _downsample_outputs(cube, axis, factor, truncate, np.float64, out, out_mask)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    ors, ops_ = _strides(out)
-    _lib.call("spc_downsample_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
               int(axis), int(factor), 1 if truncate else 0, int(estimator), C.c_void_p(out.ptr), ors, ops_, C.c_void_p(out_mask.ptr))
     return out, out_mask
 
@@ -521,14 +371,22 @@ def normalize_view(view, shape):
     return out
 
 
-def _subcube_call(name, cube, c, m, start, step, shape, dtype, out, out_mask, want_mask, filled, fill, nan_excluded, stream):
+def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_mask=True, filled=False, fill=np.nan,
+            stream=None, nan_excluded=False):
+    """(data, include) of ``cube[start[a] :: step[a]]`` cut to *shape* = SpectralCube.__getitem__ with three slices
+    (spectral_cube.py:1308-1381): output sample (k, j, i) is parent sample (start + (k, j, i) * step), copied bit for bit
+    in the cube's dtype (*filled*: excluded voxels become *fill*), and the include byte of the parent's mask there.  ``want_mask=False``
+    (a parent without a mask) skips the mask output and returns None for it.  *out* / *out_mask* may be strided views
+    of larger outputs."""
+    name, dtype = _entry("subcube", cube)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
     shape = tuple(int(n) for n in shape)
     if out is None:
         out = DeviceArray(shape, dtype, cube.device)
     if out_mask is None and want_mask:
         out_mask = DeviceArray(shape, np.uint8, cube.device)
-    if tuple(out.shape) != shape or out.dtype != np.dtype(dtype):
-        raise ValueError("preallocated output must be %s %s" % (shape, np.dtype(dtype)))
+    if tuple(out.shape) != shape or out.dtype != dtype:
+        raise ValueError("preallocated output must be %s %s" % (shape, dtype))
     if out_mask is not None:
         if tuple(out_mask.shape) != shape or out_mask.dtype != np.uint8:
             raise ValueError("preallocated mask output must be %s uint8" % (shape,))
@@ -540,24 +398,6 @@ def _subcube_call(name, cube, c, m, start, step, shape, dtype, out, out_mask, wa
               shape[0], shape[1], shape[2], C.c_void_p(out.ptr), ors, ops_,
               C.c_void_p(out_mask.ptr) if out_mask is not None else None, 1 if filled else 0, float(fill))
     return out, out_mask
-
-
-def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_mask=True, filled=False, fill=np.nan,
-            stream=None, nan_excluded=False):
-    """(data, include) of ``cube[start[a] :: step[a]]`` cut to *shape* = SpectralCube.__getitem__ with three slices
-    (spectral_cube.py:1308-1381): output sample (k, j, i) is parent sample (start + (k, j, i) * step), copied bit for bit
-    (*filled*: excluded voxels become *fill*), and the include byte of the parent's mask there.  ``want_mask=False``
-    (a parent without a mask) skips the mask output and returns None for it.  *out* / *out_mask* may be strided views
-    of larger outputs."""
-    return _subcube_call("spc_subcube_f32", cube, _cube_c(cube), _mask_c(mask, cube), start, step, shape, np.float32, out,
-                         out_mask, want_mask, filled, fill, nan_excluded, stream)
-
-
-def subcube_f64(cube, start, step, shape, mask=None, out=None, out_mask=None, want_mask=True, filled=False, fill=np.nan,
-                stream=None, nan_excluded=False):
-    """subcube of a float64 cube: float64 in, float64 out"""
-    return _subcube_call("spc_subcube_f64", cube, _cube_c64(cube), _mask_c64(mask, cube), start, step, shape, np.float64, out,
-                         out_mask, want_mask, filled, fill, nan_excluded, stream)
 
 
 def _bbox_result(box, device, stream):
@@ -575,15 +415,7 @@ def mask_bbox(cube, mask=None, stream=None, nan_excluded=False):
     (spectral_cube.py:1925-1938) in one pass over the mask terms."""
     box = DeviceArray((6,), np.int64, cube.device)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    _lib.call("spc_mask_bbox_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(box.ptr))
-    return _bbox_result(box, cube.device, stream)
-
-
-def mask_bbox_f64(cube, mask=None, stream=None, nan_excluded=False):
-    """mask_bbox of a float64 cube (thresholds compared in float64)"""
-    box = DeviceArray((6,), np.int64, cube.device)
-    c, m = _cube_c64(cube), _mask_c64(mask, cube)
-    _lib.call("spc_mask_bbox_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(box.ptr))
+    _lib.call(_entry("mask_bbox", cube)[0], cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, C.c_void_p(box.ptr))
     return _bbox_result(box, cube.device, stream)
 
 
@@ -594,7 +426,7 @@ def spectral_conv_moments(cube, kernel1d, cen, dv=1.0, m1_add=0.0, mask=None, wa
     nz, ny, nx = cube.shape
     o, bufs = _moment_outputs((ny, nx), cube.device, want, out)
     k, kp = _kern(kernel1d)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     hc = None
     if cen_host is not None:
         cen_host = np.ascontiguousarray(cen_host, dtype=np.float64)
@@ -664,19 +496,28 @@ class masked_spatial_arithmetic:
 
 def spatial_conv(cube, kernel2d, mask=None, out=None, stream=None, arithmetic=None):
     """NaN-aware per-channel 2-D convolution = chunk function of
-    spatial_smooth (dask_spectral_cube.py:962-993, :540-547).  *arithmetic*: None (the library's default) or one of
-    MASKED_SPATIAL_ARITHMETIC for the masked separable stencil (see masked_spatial_arithmetic)."""
-    if arithmetic is not None:
+    spatial_smooth (dask_spectral_cube.py:962-993, :540-547): an outer-product kernel in two passes, any other kernel
+    summed directly; the result has the cube's dtype.  *arithmetic*: None (the library's default) or one of
+    MASKED_SPATIAL_ARITHMETIC for the masked separable stencil of a float32 cube (see masked_spatial_arithmetic)."""
+    wide = cube.dtype == _F64
+    if arithmetic is not None and not wide:          # (the float64 stencils have one arithmetic)
         with masked_spatial_arithmetic(arithmetic):
             return spatial_conv(cube, kernel2d, mask=mask, out=out, stream=stream)
     if out is None:
-        out = DeviceArray(cube.shape, np.float32, cube.device)
+        out = DeviceArray(cube.shape, cube.dtype, cube.device)
     k2 = np.ascontiguousarray(kernel2d, dtype=np.float64)
     if k2.ndim != 2:
         raise ValueError("kernel must be 2-D")
     c, m = _cube_c(cube), _mask_c(mask, cube)
     sep = separable_factors(k2)
-    if sep is not None:
+    if wide:
+        # float64: ONE entry point with a separable flag (the two factors, or the whole kernel and no second pointer) and one
+        # workspace kind
+        (ky, kyp), (kx, kxp) = (_kern(sep[0]), _kern(sep[1])) if sep is not None else (_kern(k2), (None, None))
+        ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV_F64, *cube.shape, k2.shape[0], k2.shape[1])
+        _lib.call("spc_spatial_conv_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), kyp, k2.shape[0], kxp, k2.shape[1],
+                  0 if sep is None else 1, C.c_void_p(out.ptr), 0, 0, ws, wsn)
+    elif sep is not None:
         (ky, kyp), (kx, kxp) = _kern(sep[0]), _kern(sep[1])
         ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV_SEP, *cube.shape, len(ky), len(kx))
         _lib.call("spc_spatial_conv_sep_f32", cube.device, _sh(stream), C.byref(c), C.byref(m),
@@ -717,17 +558,18 @@ def lerp_plan(inaxis, grid, fill_value=None):
 
 def spectral_lerp(cube, lo, t, inv_dx, fill=np.nan, mask=None, out=None, stream=None):
     """per-spaxel linear interpolation onto nz_out channels (chunk function
-    of spectral_interpolate, dask_spectral_cube.py:1342-1353).  *cube* must
+    of spectral_interpolate, dask_spectral_cube.py:1342-1353), in the cube's dtype.  *cube* must
     already be in ascending spectral order."""
     nz_out = len(lo)
     dev = cube.device
     d_lo = DeviceArray.from_numpy(np.asarray(lo, dtype=np.int32), dev)
     d_t = DeviceArray.from_numpy(np.asarray(t, dtype=np.float64), dev)
     d_inv = DeviceArray.from_numpy(np.asarray(inv_dx, dtype=np.float64), dev)
+    name, dtype = _entry("spectral_lerp", cube)
     if out is None:
-        out = DeviceArray((nz_out,) + cube.shape[1:], np.float32, dev)
+        out = DeviceArray((nz_out,) + cube.shape[1:], dtype, dev)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    _lib.call("spc_spectral_lerp_f32", dev, _sh(stream), C.byref(c), C.byref(m), nz_out,
+    _lib.call(name, dev, _sh(stream), C.byref(c), C.byref(m), nz_out,
               C.c_void_p(d_lo.ptr), C.c_void_p(d_t.ptr), C.c_void_p(d_inv.ptr), float(fill),
               C.c_void_p(out.ptr), 0, 0)
     out._plan = (d_lo, d_t, d_inv)     # keep alive until the stream has consumed them
@@ -778,8 +620,9 @@ def resample_bilinear(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_fo
     """bilinear spatial resample of every channel at (xs, ys) source pixel
     coordinates (resampler of reproject_interp, spectral_cube.py:2726-2732).  xs, ys: host arrays or
     float64 DeviceArrays (wcs_pixel_map).  order: 1 bilinear, 0 nearest neighbour.  any_valid: optional
-    1-element uint32 DeviceArray, set to 1 iff some output value is not NaN."""
+    1-element uint32 DeviceArray, set to 1 iff some output value is not NaN.  A float64 cube: float64 weights and result."""
     dev = cube.device
+    name, dtype = _entry("resample_bilinear", cube)
     if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
         if xs.dtype != np.float64 or ys.dtype != np.float64 or xs.shape != ys.shape or len(xs.shape) != 2:
             raise ValueError("xs, ys must be 2-D float64 maps of identical shape")
@@ -793,16 +636,17 @@ def resample_bilinear(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_fo
         ny_out, nx_out = xs.shape
         d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
     if out is None:
-        out = DeviceArray((cube.shape[0], ny_out, nx_out), np.float32, dev)
-    elif out.shape != (cube.shape[0], ny_out, nx_out) or out.dtype != np.float32 or getattr(out, "_is_view", False):
-        raise ValueError("out must be a contiguous float32 (nz, ny_out, nx_out) DeviceArray")
+        out = DeviceArray((cube.shape[0], ny_out, nx_out), dtype, dev)
+    elif out.shape != (cube.shape[0], ny_out, nx_out) or out.dtype != dtype or getattr(out, "_is_view", False):
+        raise ValueError("out must be a contiguous %s (nz, ny_out, nx_out) DeviceArray" % dtype)
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    ws, wsn = workspace(dev, stream, _lib.WS_RESAMPLE_BILINEAR, *cube.shape, ny_out, nx_out)
-    _lib.call("spc_resample_bilinear_f32", dev, _sh(stream), C.byref(c), C.byref(m), float(fill),
+    # (the float32 kernel alone takes a workspace)
+    scratch = workspace(dev, stream, _lib.WS_RESAMPLE_BILINEAR, *cube.shape, ny_out, nx_out) if dtype == _F32 else ()
+    _lib.call(name, dev, _sh(stream), C.byref(c), C.byref(m), float(fill),
               ny_out, nx_out, C.c_void_p(d_xs.ptr), C.c_void_p(d_ys.ptr), C.c_void_p(out.ptr), 0, 0,
               C.c_void_p(foot.ptr) if foot is not None else None, int(order),
-              C.c_void_p(any_valid.ptr) if any_valid is not None else None, ws, wsn)
+              C.c_void_p(any_valid.ptr) if any_valid is not None else None, *scratch)
     out._plan = (d_xs, d_ys)
     return out, foot
 
@@ -863,7 +707,7 @@ def resample_bilinear_lerp(cube, xs, ys, lo, t, inv_dx, fill=np.nan, mask=None, 
     elif out.shape != (nz_out, ny_out, nx_out) or out.dtype != np.float32 or getattr(out, "_is_view", False):
         raise ValueError("out must be a contiguous float32 (nz_out, ny_out, nx_out) DeviceArray")
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(dev, stream, _lib.WS_RESAMPLE_BILINEAR_LERP, *cube.shape, ny_out, nx_out)
     plane = ny_out * nx_out
     _lib.call("spc_resample_bilinear_lerp_f32", dev, _sh(stream), C.byref(c), C.byref(m), float(fill),
@@ -892,7 +736,7 @@ def spatial_conv_mfma(cube, kernel2d, mask=None, stream=None, out=None, want_cub
         out = DeviceArray((nz, ny, nx), np.float32, dev)
     if want_m0 and m0 is None:
         m0 = DeviceArray((ny, nx), np.float64, dev)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(dev, stream, _lib.WS_SPATIAL_CONV_MFMA, nz, ny, nx)
     _lib.call("spc_spatial_conv_sep_mfma_f32", dev, _sh(stream), C.byref(c), C.byref(m),
               ky.ctypes.data_as(C.POINTER(C.c_double)), len(ky), kx.ctypes.data_as(C.POINTER(C.c_double)), len(kx),
@@ -916,7 +760,7 @@ def spatial_conv_mfma_moments(cube, kernel2d, d_cen, dv=1.0, m1_add=0.0, mask=No
     if want_cube and out is None:
         out = DeviceArray((nz, ny, nx), np.float32, dev)
     maps = {w: DeviceArray((ny, nx), np.float64, dev) for w in want}
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     higher = ("m1" in maps) or ("m2" in maps)
     ws, wsn = workspace(dev, stream, _lib.WS_SPATIAL_CONV_MFMA, nz, ny, nx, 3 if higher else 1)
     ptr = lambda w: C.c_void_p(maps[w].ptr) if w in maps else None
@@ -964,7 +808,7 @@ def resample_spline(cube, xs, ys, order, stream=None, want_footprint=True, out=N
     coef = DeviceArray((planes * per_plane,), np.uint8, dev)
     for z0 in range(0, nz, planes):
         z1 = min(nz, z0 + planes)
-        c = _cube_c(cube.planes(z0, z1))
+        c = _cube_c(cube.planes(z0, z1), _F32)
         _lib.call("spc_resample_spline_f32", dev, _sh(stream), C.byref(c), int(order), ny_out, nx_out, C.c_void_p(d_xs.ptr),
                   C.c_void_p(d_ys.ptr), C.c_void_p(out.ptr + z0 * ny_out * nx_out * 4), 0, 0,
                   C.c_void_p(foot.ptr) if (foot is not None and z0 == 0) else None, C.c_void_p(coef.ptr), C.c_size_t(coef.nbytes))
@@ -984,11 +828,13 @@ _STAT_DTYPES = {"count": np.int32, "min": np.float32, "max": np.float32, "sum": 
 def stats_global(cube, mask=None, stream=None):
     """{npts, min, max, sum, sumsq} of the included samples of the whole cube in ONE pass
     (per-chunk compute_stats + aggregation of statistics(), dask_spectral_cube.py:769-814).
-    Returns python floats; synchronises."""
+    Returns python floats (min / max of a float64 cube are its float64 samples); synchronises."""
+    name, dtype = _entry("stats_global", cube)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     h = (C.c_double * 5)()
-    ws, wsn = workspace(cube.device, stream, _lib.WS_STATS_GLOBAL, *cube.shape)
-    _lib.call("spc_stats_global_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), h, ws, wsn)
+    # (the float64 kernel sizes its scratch by its own kind)
+    ws, wsn = workspace(cube.device, stream, _lib.WS_STATS_GLOBAL_F64 if dtype == _F64 else _lib.WS_STATS_GLOBAL, *cube.shape)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), h, ws, wsn)
     return {"npts": h[0], "min": h[1], "max": h[2], "sum": h[3], "sumsq": h[4]}
 
 
@@ -997,7 +843,7 @@ def stats_planes(cube, mask=None, stream=None):
     plane in ONE pass (nan-reductions with axis=(1, 2): spectra).  Synchronises."""
     nz = cube.shape[0]
     buf = (C.c_double * (5 * nz))()
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(cube.device, stream, _lib.WS_STATS_PLANES, *cube.shape)
     _lib.call("spc_stats_planes_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), buf, ws, wsn)
     a = np.frombuffer(buf, dtype=np.float64).reshape(nz, 5)
@@ -1007,23 +853,25 @@ def stats_planes(cube, mask=None, stream=None):
 def stats_axis(cube, axis, mask=None, want=STAT_KEYS, stream=None, out=None):
     """count / min / max / sum / sumsq maps along *axis* in ONE pass (the nan-reductions behind
     sum / mean / std / max / min, dask_spectral_cube.py:641-767).  Returns DeviceArrays
-    (*out*: dict of preallocated ones, reused)."""
+    (*out*: dict of preallocated ones, reused); min / max have the cube's dtype."""
     if axis not in (0, 1, 2):
         raise ValueError("axis must be 0, 1 or 2")
+    name, dtype = _entry("stats_axis", cube)
+    types = dict(_STAT_DTYPES, min=dtype, max=dtype)
     shp = tuple(n for i, n in enumerate(cube.shape) if i != axis)
     res = {}
     for k in want:
         a = out.get(k) if out else None
         if a is None:
-            a = DeviceArray(shp, _STAT_DTYPES[k], cube.device)
-        elif tuple(a.shape) != shp or a.dtype != _STAT_DTYPES[k]:
-            raise ValueError("out[%r] must be %s %s" % (k, shp, _STAT_DTYPES[k]))
+            a = DeviceArray(shp, types[k], cube.device)
+        elif tuple(a.shape) != shp or a.dtype != types[k]:
+            raise ValueError("out[%r] must be %s %s" % (k, shp, types[k]))
         res[k] = a
     o = _lib.SpcStatsOutputs()
     for k in want:
         setattr(o, "d_" + k, res[k].ptr)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    _lib.call("spc_stats_axis_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis), C.byref(o))
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis), C.byref(o))
     return res
 
 
@@ -1062,14 +910,16 @@ MAD_TO_STD = 1.482602218505602          # 1 / Phi^-1(3/4), astropy.stats.mad_std
 def percentile_axis0(cube, q, mask=None, center=None, scale=1.0, stream=None, out=None):
     """q-th percentile along the spectral axis per spaxel (median: q = 50), numpy 'linear'
     interpolation, NaN / masked samples ignored (dask_spectral_cube.py:657-693); with *center*
-    (a (ny, nx) float32 DeviceArray) of |x - center| times *scale* (mad_std, :711-731).
-    Selection along y: pass ``cube.swap01()`` (and ``mask.swap01()``); the result is (nz, nx)."""
+    (a (ny, nx) DeviceArray of the cube's dtype) of |x - center| times *scale* (mad_std, :711-731).  The map has the
+    cube's dtype.  Selection along y: pass ``cube.swap01()`` (and ``mask.swap01()``); the result is (nz, nx).
+    A float64 cube: HipUnsupported beyond 4096 samples per ray."""
+    name, dtype = _entry("percentile_axis0", cube)
     if out is None:
-        out = DeviceArray(cube.shape[1:], np.float32, cube.device)
+        out = DeviceArray(cube.shape[1:], dtype, cube.device)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    if center is not None and (center.dtype != np.float32 or tuple(center.shape) != tuple(cube.shape[1:])):
-        raise TypeError("center must be a float32 (ny, nx) DeviceArray")
-    _lib.call("spc_percentile_axis0_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
+    if center is not None and (center.dtype != dtype or tuple(center.shape) != tuple(cube.shape[1:])):
+        raise TypeError("center must be a %s (ny, nx) DeviceArray" % dtype)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
               C.c_void_p(center.ptr) if center is not None else None, float(scale), C.c_void_p(out.ptr))
     return out
 
@@ -1078,18 +928,18 @@ def fill_masked(cube, mask=None, fill=np.nan, stream=None, out=None):
     """device copy with excluded voxels replaced by *fill* (MaskBase._filled, masks.py:197-237)."""
     if out is None:
         out = DeviceArray(cube.shape, np.float32, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     _lib.call("spc_fill_masked_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(fill), C.c_void_p(out.ptr), 0, 0)
     return out
 
 
 def mask_include(cube, mask=None, nan_excluded=False, stream=None):
     """uint8 (nz, ny, nx) DeviceArray: 1 where *mask* (a MaskSpec evaluated on *cube*'s values) includes
-    the voxel (spc_mask_include_u8) - a lazy mask bound to another device-resident cube is lowered
+    the voxel (spc_mask_include_u8 / _f64: the one pair named irregularly) - a lazy mask bound to another device-resident cube is lowered
     like this instead of through a host copy of that cube."""
     out = DeviceArray(cube.shape, np.uint8, cube.device)
     c, m = _cube_c(cube), _mask_c(mask, cube)
-    _lib.call("spc_mask_include_u8", cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0,
+    _lib.call(_entry("mask_include", cube, "_u8")[0], cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0,
               C.c_void_p(out.ptr))
     return out
 
@@ -1100,7 +950,7 @@ def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, ou
     nz, ny, nx = cube.shape
     if out is None:
         out = DeviceArray((nz, ny), np.float32, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     if center is not None and (center.dtype != np.float32 or tuple(center.shape) != (nz, ny)):
         raise TypeError("center must be a float32 (nz, ny) DeviceArray")
     _lib.call("spc_percentile_axis2_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
@@ -1112,7 +962,7 @@ def percentile_global(cube, q, mask=None, center=None, stream=None):
     """q-th percentile of all included samples of the cube (np.nanpercentile(..., axis=None));
     with *center* of |x - center|.  Returns a python float (NaN when nothing is included)."""
     out = C.c_double(0.0)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(cube.device, stream, _lib.WS_PERCENTILE_GLOBAL, *cube.shape)
     _lib.call("spc_percentile_global_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
               0 if center is None else 1, 0.0 if center is None else float(center), C.byref(out), ws, wsn)
@@ -1124,7 +974,7 @@ def key_histogram(cube, prefix, pmask, shift, mask=None, center=None, stream=Non
     of the key byte at bit *shift* among the included samples whose key agrees with *prefix* on *pmask*.
     Returns a uint64 ndarray of 256."""
     h = np.zeros(256, np.uint64)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(cube.device, stream, _lib.WS_PERCENTILE_GLOBAL, *cube.shape)
     _lib.call("spc_key_histogram_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(prefix), int(pmask), int(shift),
               0 if center is None else 1, 0.0 if center is None else float(center),
@@ -1135,7 +985,7 @@ def key_histogram(cube, prefix, pmask, shift, mask=None, center=None, stream=Non
 def key_next(cube, prefix, mask=None, center=None, stream=None):
     """smallest sample key above *prefix* on this rank's part (0xffffffff when there is none)."""
     nxt = C.c_uint32(0)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(cube.device, stream, _lib.WS_PERCENTILE_GLOBAL, *cube.shape)
     _lib.call("spc_key_histogram_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(prefix), 0xffffffff, 0,
               0 if center is None else 1, 0.0 if center is None else float(center), None, C.byref(nxt), ws, wsn)
@@ -1152,7 +1002,7 @@ def fill_masked_transposed(cube, mask=None, fill=np.nan, stream=None):
     (spc_fill_masked_transpose_f32) - rays along x become rays along y."""
     nz, ny, nx = cube.shape
     out = DeviceArray((nz, nx, ny), np.float32, cube.device)
-    c, m = _cube_c(cube), _mask_c(mask, cube)
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     _lib.call("spc_fill_masked_transpose_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(fill), C.c_void_p(out.ptr))
     return out
 
@@ -1171,7 +1021,7 @@ def sigma_clip_axis0(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, maxite
     # the whole loop in one kernel, rays resident in registers (<= 4096 channels)
     if cube.shape[0] <= 4096 and os.environ.get("SPC_SIGMA_CLIP_FUSED", "1") != "0":
         out = DeviceArray(cube.shape, np.float32, cube.device)
-        c, m = _cube_c(cube), _mask_c(mask, cube)
+        c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
         ws, wsn = workspace(cube.device, stream, _lib.WS_SIGMA_CLIP, *cube.shape)
         try:
             _lib.call("spc_sigma_clip_axis0_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(lo_s), float(hi_s),
@@ -1214,8 +1064,16 @@ def sigma_clip_axis0(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, maxite
 
 
 def scale_inplace(arr, factor, stream=None):
-    """arr *= factor on the device (contiguous float32 DeviceArray)."""
-    if arr.dtype != np.float32 or getattr(arr, "_is_view", False):
-        raise TypeError("scale_inplace needs a contiguous float32 DeviceArray")
-    _lib.call("spc_scale_f32", arr.device, _sh(stream), C.c_void_p(arr.ptr), int(np.prod(arr.shape, dtype=np.int64)), float(factor))
+    """arr *= factor on the device (contiguous float32 or float64 DeviceArray)."""
+    if arr.dtype not in (_F32, _F64) or getattr(arr, "_is_view", False):
+        raise TypeError("scale_inplace needs a contiguous float32 or float64 DeviceArray")
+    _lib.call(_entry("scale", arr)[0], arr.device, _sh(stream), C.c_void_p(arr.ptr), int(np.prod(arr.shape, dtype=np.int64)), float(factor))
     return arr
+
+
+# ---- names bench.py still calls: each pair was folded into the function it now names (the dtype comes from the cube)
+percentile_axis0_f64 = percentile_axis0
+spatial_conv_f64 = spatial_conv
+spectral_conv_f64 = spectral_conv
+spectral_lerp_f64 = spectral_lerp
+stats_global_f64 = stats_global

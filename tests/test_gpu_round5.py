@@ -727,11 +727,11 @@ def test_float64_convolutions_refuse_kernels_that_cannot_be_normalised(gpu):
     """astropy: "The kernel can't be normalized, because its sum is close to zero" - the float64 entry points say so too"""
     d = DeviceArray.from_numpy(np.ones((5, 6, 7)))
     with pytest.raises(_lib.HipInvalidArgument, match="can't be normalized"):
-        ops.spectral_conv_f64(d, np.array([1.0, 0.0, -1.0]))
+        ops.spectral_conv(d, np.array([1.0, 0.0, -1.0]))
     with pytest.raises(_lib.HipInvalidArgument, match="can't be normalized"):
-        ops.spatial_conv_f64(d, np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 0.0], [0.0, -1.0, 0.0]]))
+        ops.spatial_conv(d, np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 0.0], [0.0, -1.0, 0.0]]))
     with pytest.raises(_lib.HipInvalidArgument, match="can't be normalized"):
-        ops.spectral_conv_f64(d, np.zeros(1))
+        ops.spectral_conv(d, np.zeros(1))
 
 
 def test_float64_varying_resolution_convolve_to(gpu, tmp_path):

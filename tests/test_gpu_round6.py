@@ -185,7 +185,7 @@ def test_float64_percentiles_by_radix_selection_are_numpy_s(gpu, shape, q):
     if shape[1] > 3 and shape[2] > 3:
         m[:, 1, 2] = False
     cube, mk = DeviceArray.from_numpy(d), DeviceArray.from_numpy(m.astype(np.uint8))
-    got = ops.percentile_axis0_f64(cube, q, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk)).get()
+    got = ops.percentile_axis0(cube, q, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk)).get()
     with warnings.catch_warnings(), np.errstate(all="ignore"):
         warnings.simplefilter("ignore")
         f = np.where(m, d, np.nan)
@@ -199,8 +199,8 @@ def test_float64_mad_by_radix_selection(gpu):
     m = rng.random(d.shape) < 0.7
     cube, mk = DeviceArray.from_numpy(d), DeviceArray.from_numpy(m.astype(np.uint8))
     spec = ops.MaskSpec(_lib.MASK_ARRAY, array=mk)
-    med = ops.percentile_axis0_f64(cube, 50.0, mask=spec)
-    mad = ops.percentile_axis0_f64(cube, 50.0, mask=spec, center=med, scale=1.482602218505602).get()
+    med = ops.percentile_axis0(cube, 50.0, mask=spec)
+    mad = ops.percentile_axis0(cube, 50.0, mask=spec, center=med, scale=1.482602218505602).get()
     f = np.where(m, d, np.nan)
     exp = 1.482602218505602 * np.nanmedian(np.abs(f - np.nanmedian(f, axis=0)), axis=0)
     assert np.array_equal(mad, exp, equal_nan=True)
@@ -216,7 +216,7 @@ def test_float64_spatial_smooth_four_outputs_per_thread_is_bit_identical(gpu, sh
     m = rng.random(shape) < 0.8
     k2 = Gaussian2DKernel(stddev).array
     cube, mk = DeviceArray.from_numpy(d), DeviceArray.from_numpy(m.astype(np.uint8))
-    got = ops.spatial_conv_f64(cube, k2, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk)).get()
+    got = ops.spatial_conv(cube, k2, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk)).get()
     exp = O.spatial_smooth(d, m, k2)
     assert np.array_equal(np.isnan(got), np.isnan(exp))
     ok = ~np.isnan(exp)
@@ -246,9 +246,9 @@ def test_float64_spatial_smooth_ring_form(gpu, shape, taps, flags, monkeypatch):
     fl = (_lib.MASK_ARRAY if "array" in flags else 0) | (_lib.MASK_FINITE if "finite" in flags else 0)
     spec = ops.MaskSpec(fl, array=mk) if fl else None
     monkeypatch.setenv("SPC_SPATIAL64_RING", "1")
-    ring = ops.spatial_conv_f64(cube, k2, mask=spec).get()
+    ring = ops.spatial_conv(cube, k2, mask=spec).get()
     monkeypatch.setenv("SPC_SPATIAL64_RING", "0")
-    two = ops.spatial_conv_f64(cube, k2, mask=spec).get()
+    two = ops.spatial_conv(cube, k2, mask=spec).get()
     assert np.array_equal(ring, two, equal_nan=True)
     inc = (m if "array" in flags else np.ones(shape, bool)) & ~np.isnan(d)
     exp = O.spatial_smooth(d, inc, k2)
@@ -275,9 +275,9 @@ def test_float64_spatial_smooth_ring_form_hands_infinite_samples_to_the_two_pass
         for fl in (_lib.MASK_ARRAY, _lib.MASK_ARRAY | _lib.MASK_FINITE):
             spec = ops.MaskSpec(fl, array=mk)
             monkeypatch.setenv("SPC_SPATIAL64_RING", "1")
-            ring = ops.spatial_conv_f64(cube, kern, mask=spec).get()
+            ring = ops.spatial_conv(cube, kern, mask=spec).get()
             monkeypatch.setenv("SPC_SPATIAL64_RING", "0")
-            two = ops.spatial_conv_f64(cube, kern, mask=spec).get()
+            two = ops.spatial_conv(cube, kern, mask=spec).get()
             assert np.array_equal(ring, two, equal_nan=True)
             if fl & _lib.MASK_FINITE:
                 assert np.isfinite(ring[1, 55:66, 95:106]).all()
@@ -305,9 +305,9 @@ def test_float64_spectral_smooth_ring_form(gpu, shape, taps, flags, monkeypatch)
     fl = (_lib.MASK_ARRAY if "array" in flags else 0) | (_lib.MASK_FINITE if "finite" in flags else 0)
     spec = ops.MaskSpec(fl, array=mk) if fl else None
     monkeypatch.setenv("SPC_SPECTRAL64_RING", "1")
-    ring = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+    ring = ops.spectral_conv(cube, k1, mask=spec).get()
     monkeypatch.setenv("SPC_SPECTRAL64_RING", "0")
-    runs = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+    runs = ops.spectral_conv(cube, k1, mask=spec).get()
     assert np.array_equal(ring, runs, equal_nan=True)
     inc = (m if "array" in flags else np.ones(shape, bool)) & ~np.isnan(d)
     exp = O.spectral_smooth(d, inc, k1)
@@ -334,9 +334,9 @@ def test_float64_spectral_smooth_ring_form_hands_over_what_it_does_not_take(gpu,
         for fl in (_lib.MASK_ARRAY, _lib.MASK_ARRAY | _lib.MASK_FINITE):
             spec = ops.MaskSpec(fl, array=mk)
             monkeypatch.setenv("SPC_SPECTRAL64_RING", "1")
-            ring = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+            ring = ops.spectral_conv(cube, k1, mask=spec).get()
             monkeypatch.setenv("SPC_SPECTRAL64_RING", "0")
-            runs = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+            runs = ops.spectral_conv(cube, k1, mask=spec).get()
             assert np.array_equal(ring, runs, equal_nan=True)
             if k1 is g and not (fl & _lib.MASK_FINITE):
                 assert not np.isfinite(ring[100, 3, 20])
@@ -361,13 +361,13 @@ def test_float64_ring_forms_on_row_and_plane_views(gpu, monkeypatch):
     inc = (m & ~np.isnan(d))[:, y0:y1]
     monkeypatch.setenv("SPC_SPATIAL64_RING", "1")
     monkeypatch.setenv("SPC_SPECTRAL64_RING", "1")
-    for got, exp in ((ops.spatial_conv_f64(sub, k2, mask=spec).get(), O.spatial_smooth(d[:, y0:y1], inc, k2)),
-                     (ops.spectral_conv_f64(sub, k1, mask=spec).get(), O.spectral_smooth(d[:, y0:y1], inc, k1))):
+    for got, exp in ((ops.spatial_conv(sub, k2, mask=spec).get(), O.spatial_smooth(d[:, y0:y1], inc, k2)),
+                     (ops.spectral_conv(sub, k1, mask=spec).get(), O.spectral_smooth(d[:, y0:y1], inc, k1))):
         ok = ~np.isnan(exp)
         assert np.array_equal(np.isnan(got), np.isnan(exp)) and np.abs(got[ok] - exp[ok]).max() <= 1e-13 * np.abs(exp[ok]).max()
     z0, z1 = 2, 5
     full = DeviceArray.from_numpy(np.full(shape, -7.0))
-    ops.spatial_conv_f64(cube.planes(z0, z1), k2, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk.planes(z0, z1)), out=full.planes(z0, z1))
+    ops.spatial_conv(cube.planes(z0, z1), k2, mask=ops.MaskSpec(_lib.MASK_ARRAY, array=mk.planes(z0, z1)), out=full.planes(z0, z1))
     got = full.get()
     exp = O.spatial_smooth(d[z0:z1], (m & ~np.isnan(d))[z0:z1], k2)
     ok = ~np.isnan(exp)

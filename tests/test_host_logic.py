@@ -779,3 +779,184 @@ def test_fk4_pixel_maps_against_astropy():
     # leaving the E-terms out (what equating FK4 with FK4-NO-E would do) is a 0.1 pixel error at this scale
     a, b = SimpleWCS(str(g["in6"]), naxis=2), SimpleWCS(str(g["out6"]), naxis=2)
     assert np.abs(g["xs6"] - np.arange(g["xs6"].shape[1])[None, :]).max() > 0.05
+
+
+# ---- the float32 / float64 seam: one binding per operator, the dtype taken from the cube ---------------------------------
+class _StandInArray:
+    """what ops.py reads of a DeviceArray (shape, dtype, device, ptr, nbytes), without a device"""
+
+    def __init__(self, shape, dtype, device=0):
+        self.shape, self.dtype, self.device, self.ptr = tuple(int(n) for n in shape), np.dtype(dtype), device, 0x1000
+        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
+
+    @classmethod
+    def from_numpy(cls, arr, device=0, stream=None, dtype=None):
+        a = np.asarray(arr, dtype=dtype)
+        return cls(a.shape, a.dtype, device)
+
+    def get(self, stream=None):
+        return np.zeros(self.shape, self.dtype)
+
+
+_LERP = (np.array([0, 1], np.int32), np.zeros(2), np.ones(2))
+_XY = np.zeros((3, 4))
+_BUILT, _F64_OWN = "built", "float64's own"
+# operator -> (call(cube, mask) -> the output that follows the cube's dtype or None, float32 symbol, float64 symbol,
+#              workspace kinds asked for on the float32 / the float64 path)
+_FOLDED = {
+    "downsample": (lambda c, m: ops.downsample(c, 0, 2, mask=m)[0], "spc_downsample_f32", "spc_downsample_f64", [], []),
+    "subcube": (lambda c, m: ops.subcube(c, (0, 0, 0), (1, 1, 1), (2, 2, 2), mask=m)[0], "spc_subcube_f32", "spc_subcube_f64", [], []),
+    "mask_bbox": (lambda c, m: ops.mask_bbox(c, mask=m) and None, "spc_mask_bbox_f32", "spc_mask_bbox_f64", [], []),
+    "mask_include": (lambda c, m: ops.mask_include(c, mask=m) and None, "spc_mask_include_u8", "spc_mask_include_f64", [], []),
+    "spectral_lerp": (lambda c, m: ops.spectral_lerp(c, *_LERP, mask=m), "spc_spectral_lerp_f32", "spc_spectral_lerp_f64", [], []),
+    "stats_global": (lambda c, m: ops.stats_global(c, mask=m) and None, "spc_stats_global_f32", "spc_stats_global_f64",
+                     [_lib.WS_STATS_GLOBAL], [_lib.WS_STATS_GLOBAL_F64]),
+    "stats_axis": (lambda c, m: ops.stats_axis(c, 1, mask=m)["max"], "spc_stats_axis_f32", "spc_stats_axis_f64", [], []),
+    "percentile_axis0": (lambda c, m: ops.percentile_axis0(c, 50.0, mask=m), "spc_percentile_axis0_f32", "spc_percentile_axis0_f64", [], []),
+    "spectral_conv": (lambda c, m: ops.spectral_conv(c, np.ones(3), mask=m), "spc_spectral_conv_f32", "spc_spectral_conv_f64",
+                      [_lib.WS_SPECTRAL_CONV], [_lib.WS_SPECTRAL_CONV_F64]),
+    "spatial_conv (outer product)": (lambda c, m: ops.spatial_conv(c, np.ones((3, 3)), mask=m), "spc_spatial_conv_sep_f32",
+                                     "spc_spatial_conv_f64", [_lib.WS_SPATIAL_CONV_SEP], [_lib.WS_SPATIAL_CONV_F64]),
+    "spatial_conv (any kernel)": (lambda c, m: ops.spatial_conv(c, np.eye(3) + 1.0, mask=m), "spc_spatial_conv2d_f32",
+                                  "spc_spatial_conv_f64", [_lib.WS_SPATIAL_CONV2D], [_lib.WS_SPATIAL_CONV_F64]),
+    "resample_bilinear": (lambda c, m: ops.resample_bilinear(c, _XY, _XY, mask=m)[0], "spc_resample_bilinear_f32",
+                          "spc_resample_bilinear_f64", [_lib.WS_RESAMPLE_BILINEAR], []),
+    "scale_inplace": (lambda c, m: ops.scale_inplace(c, 2.0), "spc_scale_f32", "spc_scale_f64", [], []),
+}
+
+
+@pytest.fixture
+def recorded_calls(monkeypatch):
+    """ops.py with _lib.call, the workspace and DeviceArray replaced: (entry points reached with their arguments, workspace kinds)"""
+    calls, kinds = [], []
+    monkeypatch.setattr(_lib, "call", lambda name, *a: calls.append((name, a)))
+    monkeypatch.setattr(ops, "workspace", lambda device, stream, kind, *a, **k: kinds.append(kind) or (None, 0))
+    monkeypatch.setattr(ops, "DeviceArray", _StandInArray)
+    return calls, kinds
+
+
+@pytest.mark.parametrize("name", sorted(_FOLDED))
+def test_folded_operator_takes_symbol_mask_and_output_dtype_from_the_cube(recorded_calls, name):
+    """a float32 cube reaches the _f32 entry point with spc_mask_f32 and gives float32, a float64 cube the _f64 entry point
+    with spc_mask_f64 and gives float64 (each with the workspace kind of its kernel); any other sample type is a TypeError"""
+    import ctypes as C
+    calls, kinds = recorded_calls
+    run, sym32, sym64, ws32, ws64 = _FOLDED[name]
+    for dtype, symbol, struct, ws in ((np.float32, sym32, _lib.SpcMask, ws32), (np.float64, sym64, _lib.SpcMask64, ws64)):
+        del calls[:], kinds[:]
+        cube = _StandInArray((4, 5, 6), dtype)
+        out = run(cube, ops.MaskSpec(_lib.MASK_GT, thr_lo=0.1))
+        assert [c[0] for c in calls] == [symbol] and kinds == ws
+        structs = [a._obj for a in calls[0][1] if hasattr(a, "_obj") and isinstance(a._obj, (_lib.SpcMask, _lib.SpcMask64))]
+        if name != "scale_inplace":                     # (no mask argument)
+            assert len(structs) == 1 and type(structs[0]) is struct
+            # the threshold as the kernel compares it: rounded to float32 for a float32 cube, kept for a float64 one
+            assert structs[0].thr_lo == (0.1 if dtype is np.float64 else float(np.float32(0.1)))
+            assert C.sizeof(structs[0]) == C.sizeof(struct)
+        if out is not None:
+            assert out.dtype == np.dtype(dtype)
+    del calls[:]
+    with pytest.raises(TypeError):
+        run(_StandInArray((4, 5, 6), np.int16), None)
+    assert calls == []
+
+
+def test_folded_operators_accept_a_preallocated_out_on_both_paths(recorded_calls):
+    for dtype in (np.float32, np.float64):
+        cube, other = _StandInArray((4, 5, 6), dtype), np.float64 if dtype is np.float32 else np.float32
+        for run, shape in ((lambda o: ops.percentile_axis0(cube, 50.0, out=o), (5, 6)),
+                           (lambda o: ops.spectral_lerp(cube, *_LERP, out=o), (2, 5, 6)),
+                           (lambda o: ops.spectral_conv(cube, np.ones(3), out=o), (4, 5, 6)),
+                           (lambda o: ops.resample_bilinear(cube, _XY, _XY, out=o)[0], (4, 3, 4)),
+                           (lambda o: ops.stats_axis(cube, 0, want=("max",), out={"max": o})["max"], (5, 6))):
+            out = _StandInArray(shape, dtype)
+            assert run(out) is out
+        # validation is the float32 form's, with the dtype taken from the cube
+        with pytest.raises(ValueError):
+            ops.resample_bilinear(cube, _XY, _XY, out=_StandInArray((4, 3, 4), other))
+        with pytest.raises(ValueError):
+            ops.stats_axis(cube, 0, want=("max",), out={"max": _StandInArray((5, 6), other)})
+        with pytest.raises(ValueError):
+            ops.downsample(cube, 0, 2, out=_StandInArray((2, 5, 6), other))
+        with pytest.raises(TypeError):
+            ops.percentile_axis0(cube, 50.0, center=_StandInArray((5, 6), other))
+        with pytest.raises(ValueError):
+            ops.resample_bilinear(cube, _XY, np.zeros((3, 5)))
+
+
+def test_operators_without_a_float64_form_refuse_a_float64_cube(recorded_calls):
+    calls, _ = recorded_calls
+    wide, cen = _StandInArray((4, 5, 6), np.float64), _StandInArray((4,), np.float64)
+    for run in (lambda: ops.moments(wide, cen), lambda: ops.argextrema_axis(wide, 1), lambda: ops.fill_masked(wide),
+                lambda: ops.percentile_axis2(wide, 50.0), lambda: ops.moments_f64(_StandInArray((4, 5, 6), np.float32), cen),
+                lambda: ops.narrow_f64(_StandInArray((4, 5, 6), np.float32))):
+        with pytest.raises(TypeError):
+            run()
+    assert calls == []
+
+
+def test_names_the_benchmark_calls_resolve():
+    for name, fn in (("percentile_axis0_f64", ops.percentile_axis0), ("spatial_conv_f64", ops.spatial_conv),
+                     ("spectral_conv_f64", ops.spectral_conv), ("spectral_lerp_f64", ops.spectral_lerp),
+                     ("stats_global_f64", ops.stats_global)):
+        assert getattr(ops, name) is fn
+    assert callable(ops.moments_f64) and callable(ops.sigma_clip_axis0_f64)
+    left = sorted(n for n in vars(ops) if n.endswith("_f64") or n.endswith("c64"))
+    assert left == sorted(["moments_f64", "moment_order_f64", "narrow_f64", "sigma_clip_axis0_f64", "percentile_axis0_f64",
+                           "spatial_conv_f64", "spectral_conv_f64", "spectral_lerp_f64", "stats_global_f64"])
+
+
+_HDR3 = {"CTYPE1": "RA---TAN", "CTYPE2": "DEC--TAN", "CTYPE3": "VRAD", "CDELT1": -1e-3, "CDELT2": 1e-3, "CDELT3": 1.0,
+         "CUNIT3": "km/s", "CRPIX1": 1, "CRPIX2": 1, "CRPIX3": 1, "CRVAL1": 10.0, "CRVAL2": 20.0, "CRVAL3": 0.0}
+
+
+def test_operand_follows_the_path_the_cube_runs_on(monkeypatch):
+    """SpectralCube._operand(): the float64 samples, the float64 lowering of the mask and a _WideView for a wide resident cube;
+    the float32 samples, the float32 lowering and the cube itself otherwise - decided as _runs_wide() decides"""
+    from spectral_cube_amd import cube as cube_mod
+    monkeypatch.setenv("SPC_HBM_BUDGET", "1G")
+    monkeypatch.setattr(cube_mod, "DeviceArray", _StandInArray)
+    monkeypatch.setattr(_lib, "require_gpu", lambda: None)
+    for dtype, wide in ((np.float64, True), (np.float32, False)):
+        c = SpectralCube(np.zeros((4, 5, 6), dtype), header=_HDR3)
+        c = c.with_mask(c > 0.1)
+        data, mask, view = c._operand()
+        assert c._runs_wide() is wide and data.dtype == np.dtype(dtype)
+        assert isinstance(view, cube_mod._WideView) if wide else view is c
+        assert mask is (c._mask_spec64() if wide else c._mask_spec())
+        assert mask.thr_lo == (0.1 if wide else float(np.float32(0.1))) and mask.flags == _lib.MASK_GT
+    # both lowerings of one mask are kept, each in its own cache
+    assert c._mask_spec64() is not c._mask_spec() and c._mask_spec64() is c._mask_spec64()
+    # a float64 cube larger than the budget streams as float32
+    monkeypatch.setenv("SPC_HBM_BUDGET", "64")
+    big = SpectralCube(np.zeros((4, 5, 6), np.float64), header=_HDR3)
+    assert big._runs_wide() is False
+
+
+def test_dropped_float64_result_releases_its_buffer_without_a_collection(monkeypatch):
+    """the result of a float64 cube -> cube operator (smoothed, cut, downsampled) holds its float64 buffer on its data token;
+    nothing the result is made of refers back to the result cube, so dropping the last reference frees the buffer at
+    once - no wait for the cycle collector (8 bytes per voxel of HBM)"""
+    import gc
+    import weakref
+    monkeypatch.setenv("SPC_HBM_BUDGET", "1G")
+
+    class Buffer:
+        pass
+
+    cube = SpectralCube(np.zeros((8, 5, 6), np.float64), header=_HDR3)
+    cube = cube.with_mask(cube > 0.1)
+    gc.collect()
+    gc.disable()
+    try:
+        for make in (lambda: cube.spectral_smooth(K.Gaussian1DKernel(1.0)), lambda: cube.spatial_smooth(K.Gaussian2DKernel(1.0)),
+                     lambda: cube[1:5, :, 2:4], lambda: cube.downsample_axis(2, 0)):
+            res = make()
+            tok = res._data_id
+            assert tok.derived64 and tok.lazy64 is not None and tok is not cube._data_id
+            tok.dev64 = Buffer()                      # stands for the float64 DeviceArray the pending operator would leave
+            buf, alive = weakref.ref(tok.dev64), weakref.ref(res)
+            del tok, res
+            assert alive() is None and buf() is None
+    finally:
+        gc.enable()

@@ -82,18 +82,18 @@ for it in range(rounds):
         k2 = np.outer(kernel1d(ty, tk), kernel1d(tx, "sym" if tk == "asym" else tk))
         tag = "it%d spatial %s taps %dx%d %s mask %s inf %d" % (it, shape, ty, tx, tk, kind, with_inf)
         os.environ["SPC_SPATIAL64_RING"] = "1"
-        ring = ops.spatial_conv_f64(cube, k2, mask=spec).get()
+        ring = ops.spatial_conv(cube, k2, mask=spec).get()
         os.environ["SPC_SPATIAL64_RING"] = "0"
-        other = ops.spatial_conv_f64(cube, k2, mask=spec).get()
+        other = ops.spatial_conv(cube, k2, mask=spec).get()
         exp = O.spatial_smooth(d, inc, k2)
     else:
         t1 = int(rng.choice([1, 3, 9, 17, 19, 25, 33, 41]))
         k1 = kernel1d(t1, tk)
         tag = "it%d spectral %s taps %d %s mask %s inf %d" % (it, shape, t1, tk, kind, with_inf)
         os.environ["SPC_SPECTRAL64_RING"] = "1"
-        ring = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+        ring = ops.spectral_conv(cube, k1, mask=spec).get()
         os.environ["SPC_SPECTRAL64_RING"] = "0"
-        other = ops.spectral_conv_f64(cube, k1, mask=spec).get()
+        other = ops.spectral_conv(cube, k1, mask=spec).get()
         exp = O.spectral_smooth(d, inc, k1)
     compare(tag, ring, other, exp)
 print("rounds %d failures %d" % (rounds, fails))

@@ -21,7 +21,7 @@ PEAK = 8.0e12
 
 
 def time_case(cube, mask, axis, f, reps, wide):
-    fn = ops.downsample_f64 if wide else ops.downsample
+    fn = ops.downsample
     st = Stream(cube.device)
     shape = ops.downsample_shape(cube.shape, axis, f, False)
     out = DeviceArray(shape, np.float64 if wide else np.float32, cube.device)

@@ -18,7 +18,7 @@ def timeit(fn, n=5):
     for _ in range(n):
         e0, e1 = Event(), Event(); e0.record(); fn(); e1.record(); e1.synchronize(); ts.append(e0.elapsed_ms(e1))
     return float(np.median(ts))
-t = timeit(lambda: ops.percentile_axis0_f64(cube, 50.0, mask=ms))
+t = timeit(lambda: ops.percentile_axis0(cube, 50.0, mask=ms))
 print("SPC_SELECT64=%s nz=%d: median f64 %.3f ms = %.0f GB/s algorithmic" % (os.environ.get("SPC_SELECT64", "default"), nz, t, nz * 1024 * 1024 * 9 / t / 1e6))
 if nz <= 1024:
     keep = {}

@@ -37,7 +37,7 @@ tag = "SPC_SPATIAL64_RING=%s" % os.environ.get("SPC_SPATIAL64_RING", "default")
 samples = {}
 for taps, sigma in ((29, 8 / 2.3548200450309493), (15, 2.0), (33, 4.0)):
     k2 = np.outer(gauss(taps, sigma), gauss(taps, sigma))
-    t = timeit(lambda: ops.spatial_conv_f64(cube, k2, mask=ms, out=out))
+    t = timeit(lambda: ops.spatial_conv(cube, k2, mask=ms, out=out))
     print("%s nz=%d taps=%d: %.3f ms = %.0f GB/s algorithmic (17 B/voxel)" % (tag, nz, taps, t, nz * 1024 * 1024 * 17 / t / 1e6), flush=True)
     samples["t%d" % taps] = np.concatenate([out.planes(z, z + 1).get()[0][rows] for z in (0, nz - 1) for rows in (slice(0, 40), slice(500, 540), slice(-40, None))])
 np.savez("/tmp/spatial64_%s.npz" % ("two_pass" if child else "ring"), **samples)

@@ -36,7 +36,7 @@ for taps, sigma in ((33, 4.0), (17, 2.0), (9, 1.0)):
     got = {}
     for form in ("1", "0"):
         os.environ["SPC_SPECTRAL64_RING"] = form
-        t = timeit(lambda: ops.spectral_conv_f64(cube, k1, mask=ms, out=out))
+        t = timeit(lambda: ops.spectral_conv(cube, k1, mask=ms, out=out))
         print("SPC_SPECTRAL64_RING=%s nz=%d taps=%d: %.3f ms = %.0f GB/s algorithmic (17 B/voxel)" % (form, nz, taps, t, nz * 1024 * 1024 * 17 / t / 1e6), flush=True)
         got[form] = np.concatenate([out.planes(z, z + 1).get()[0][:24] for z in (0, 1, 15, 16, 17, nz // 2, nz - 18, nz - 2, nz - 1)])
     a, b = got["1"], got["0"]

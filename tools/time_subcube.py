@@ -55,8 +55,7 @@ def gather_cases(cube, mask, wide, reps, emit, label):
     e = 8 if wide else 4
     dtype = "float64" if wide else "float32"
     st = Stream(cube.device)
-    sub = ops.subcube_f64 if wide else ops.subcube
-    down = ops.downsample_f64 if wide else ops.downsample
+    sub, down = ops.subcube, ops.downsample
     nz = cube.shape[0]
     # yardstick: downsample by a factor of 1 moves the bytes of a full-view gather (always with an output mask)
     out = DeviceArray(cube.shape, np.float64 if wide else np.float32, cube.device)
@@ -86,13 +85,13 @@ def bbox_cases(cube, masks, wide, reps, emit):
     dtype = "float64" if wide else "float32"
     st = Stream(cube.device)
     n = int(np.prod(cube.shape))
-    stats = ops.stats_global_f64 if wide else ops.stats_global
+    stats = ops.stats_global
     d_box = DeviceArray((6,), np.int64, cube.device)
-    c = ops._cube_c64(cube) if wide else ops._cube_c(cube)
+    c = ops._cube_c(cube)
 
     def box(cube, mask, stream):
         # (the entry point with a box allocated once, then the 48 bytes read back: stats_global ends in a read-back too)
-        m = ops._mask_c64(mask, cube) if wide else ops._mask_c(mask, cube)
+        m = ops._mask_c(mask, cube)
         _lib.call("spc_mask_bbox_f64" if wide else "spc_mask_bbox_f32", cube.device, stream.handle, C.byref(c), C.byref(m), 0,
                   C.c_void_p(d_box.ptr))
         return d_box.get(stream)
