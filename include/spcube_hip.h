@@ -368,6 +368,41 @@ int spc_mask_bbox_f32(int device, void* stream, const spc_cube_f32* cube, const 
 int spc_mask_bbox_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                       int64_t* d_box);
 
+/* ---- rank filters: median / minimum / maximum / percentile / rank over a sliding window ----
+ * spectral_smooth_median / spectral_filter (spectral_cube.py:2844-2898, dask_spectral_cube.py:920-960) and
+ * spatial_smooth_median / spatial_filter (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029) with a filter of
+ * scipy.ndimage's rank family: every output sample is element `rank` (0 = smallest) of the sorted window of FILLED
+ * samples (masked voxels -> fill; nan_excluded as for spc_downsample_*) around it.  _axis0: a window of `ksize` samples
+ * along the spectral axis of every spaxel; _plane: ky x kx samples of every image plane.  As in scipy (origin 0) a
+ * window reaches size / 2 samples back and size - 1 - size / 2 forward, so an even size is allowed.
+ * mode: how a window is continued past an edge, scipy's names (spc_rank_mode); cval is the sample of SPC_RANK_CONSTANT.
+ * NaN ranks LAST, numpy's sort order: the result is np.sort(window)[rank] for every window (scipy's own result with a
+ * NaN in the window depends on its version).  The result is one of the window's samples, bit for bit (a NaN result is
+ * the quiet NaN; which of -0.0 / +0.0 comes out of a window holding both is by their sign bit).
+ * mode SPC_RANK_CONSTANT with a mask: a spaxel (_axis0) / plane (_plane) without one included sample is written as
+ * fill, not filtered (_apply_spectral_function / _apply_spatial_function, spectral_cube.py:147-172); a second pass over
+ * the input finds them.  In every other mode each input byte is read once per window it is staged for.
+ * Limits: ksize 1 ... SPC_RANK_FILTER_MAX_KSIZE, ky / kx 1 ... SPC_RANK_FILTER_MAX_KSIZE_SPATIAL, and a window may
+ * reach at most one axis length past an edge (size / 2 <= n), else SPC_ERR_INVALID.  d_out: the output view, strides in
+ * elements (0 = C-contiguous), never the input.  Launches are split inside: no limit on any axis.  No workspace. */
+typedef enum {
+    SPC_RANK_REFLECT = 0, SPC_RANK_CONSTANT = 1, SPC_RANK_NEAREST = 2, SPC_RANK_MIRROR = 3, SPC_RANK_WRAP = 4
+} spc_rank_mode;
+#define SPC_RANK_FILTER_MAX_KSIZE 129
+#define SPC_RANK_FILTER_MAX_KSIZE_SPATIAL 15
+int spc_rank_filter_axis0_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
+                              float fill, int ksize, int rank, int mode, float cval,
+                              float* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_rank_filter_axis0_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
+                              double fill, int ksize, int rank, int mode, double cval,
+                              double* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_rank_filter_plane_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
+                              float fill, int ky, int kx, int rank, int mode, float cval,
+                              float* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_rank_filter_plane_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
+                              double fill, int ky, int kx, int rank, int mode, double cval,
+                              double* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

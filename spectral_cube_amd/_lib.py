@@ -30,6 +30,9 @@ MAP_MUL, MAP_SECOND_MOMENT_SUM, MAP_DIV_ADD, MAP_DIV_SUB_SQ = 0, 1, 2, 3
  WS_RESAMPLE_BILINEAR_LERP, WS_STATS_GLOBAL_F64, WS_SPECTRAL_CONV_F64, WS_SPATIAL_CONV_F64) = range(17)
 # spc_ds_estimator (spc_downsample_f32 / _f64)
 DS_NANMEAN, DS_NANSUM, DS_NANMAX, DS_NANMIN, DS_MEAN, DS_SUM, DS_MAX, DS_MIN = range(8)
+# spc_rank_mode and the built window limits (spc_rank_filter_axis0_* / _plane_*)
+RANK_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}
+RANK_FILTER_MAX_KSIZE, RANK_FILTER_MAX_KSIZE_SPATIAL = 129, 15
 
 
 class HipLibraryError(RuntimeError):
@@ -166,6 +169,10 @@ SIGNATURES = {
     "spc_subcube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _P(_i64), _P(_i64), _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _d]),
     "spc_mask_bbox_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp]),
     "spc_mask_bbox_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
+    "spc_rank_filter_axis0_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _f, _vp, _i64, _i64]),
+    "spc_rank_filter_axis0_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _d, _vp, _i64, _i64]),
+    "spc_rank_filter_plane_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _i, _f, _vp, _i64, _i64]),
+    "spc_rank_filter_plane_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _i, _d, _vp, _i64, _i64]),
     "spc_moments_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _d, _vp, _vp, _vp]),
     "spc_moment_order_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i, _vp, _vp]),
     "spc_spectral_conv_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _i, _vp, _i64, _i64, _vp, _sz]),

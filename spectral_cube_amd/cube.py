@@ -208,6 +208,57 @@ def _ds_estimator(estimator):
                               "np.mean, np.sum, np.max (np.amax), np.min (np.amin)" % (getattr(estimator, "__name__", estimator),))
 
 
+# scipy.ndimage's rank family, recognised by name (the package never imports scipy)
+_RANK_FILTERS = ("median_filter", "minimum_filter", "maximum_filter", "percentile_filter", "rank_filter")
+_RANK_IGNORED = ("use_memmap", "verbose", "num_cores", "parallel", "update_function", "save_to_tmp_dir")
+
+
+def _rank_filter_name(filter):
+    name = filter if isinstance(filter, str) else getattr(filter, "__name__", None)
+    if name not in _RANK_FILTERS:
+        raise NotImplementedError("filter %r is not built: the device runs scipy.ndimage's rank family - %s (the function or "
+                                  "its name)" % (name if name is not None else filter, ", ".join(_RANK_FILTERS)))
+    return name
+
+
+def _rank_filter_options(filter, w, kwargs):
+    """(rank, mode, cval) of a rank filter over a window of *w* samples: the one integer rank into the sorted window that
+    scipy's median / minimum / maximum / percentile / rank filter selects (ndimage/_filters.py, _rank_filter), and the
+    boundary keywords.  Keywords the device does not honour raise; the reference's scheduling keywords are dropped."""
+    name = _rank_filter_name(filter)
+    kw = {k: v for k, v in kwargs.items() if k not in _RANK_IGNORED}
+    mode, cval = kw.pop("mode", "reflect"), kw.pop("cval", 0.0)
+    origin = kw.pop("origin", 0)
+    if np.any(np.asarray(origin) != 0):
+        raise NotImplementedError("origin other than 0 is not built on the device (got %r)" % (origin,))
+    if kw.pop("footprint", None) is not None:
+        raise NotImplementedError("a footprint is not built on the device: rectangular windows (ksize) only")
+    if mode not in _lib.RANK_MODES:
+        raise ValueError("mode must be one of %s (got %r)" % (", ".join(sorted(_lib.RANK_MODES)), mode))
+    if name == "rank_filter":
+        if "rank" not in kw:
+            raise TypeError("rank_filter needs rank=")
+        rank = operator.index(kw.pop("rank"))
+        if rank < 0:
+            rank += w
+        if rank < 0 or rank >= w:
+            raise ValueError("rank not within the window of %d samples" % w)
+    elif name == "percentile_filter":
+        if "percentile" not in kw:
+            raise TypeError("percentile_filter needs percentile=")
+        p = kw.pop("percentile")
+        if p < 0:
+            p += 100
+        if p < 0 or p > 100:
+            raise ValueError("invalid percentile (got %r)" % (kwargs["percentile"],))
+        rank = w - 1 if p == 100 else int(float(w) * p / 100.0)
+    else:
+        rank = {"median_filter": w // 2, "minimum_filter": 0, "maximum_filter": w - 1}[name]
+    if kw:
+        raise TypeError("unexpected keyword arguments for %s: %s" % (name, sorted(kw)))
+    return rank, mode, float(cval)
+
+
 def _nan_term_dropped(cube, view):
     """True when the cube's mask goes to the kernels as device terms (``_device_terms(view)``, *view* what it is lowered
     against) and names ~isnan of the cube's own data.  That term lowers to nothing (NotNaNMask: a reduction skips NaN
@@ -1849,6 +1900,95 @@ class SpectralCube:
                 return ops.spatial_conv(dev, karr, mask=mspec, stream=stream, arithmetic=arithmetic)
 
         return self._new_cube_with(lazy=_Lazy(), shape=self._shape)
+
+    # ---- median and rank filters -----------------------------------------------------------------
+    def _rank_filtered(self, sizes, axis_lengths, filter, kwargs):
+        """the pending result of a rank filter with a window of *sizes* samples ((ksize,) along the spectral axis, (ky, kx)
+        per plane) on the FILLED data; mask, fill value, WCS, unit, meta and beams stay the parent's"""
+        rank, mode, cval = _rank_filter_options(filter, int(np.prod(sizes)), kwargs)
+        spectral = len(sizes) == 1
+        limit = _lib.RANK_FILTER_MAX_KSIZE if spectral else _lib.RANK_FILTER_MAX_KSIZE_SPATIAL
+        for k, n in zip(sizes, axis_lengths):
+            if k < 1:
+                raise ValueError("ksize must be at least 1 (got %d)" % k)
+            if k > limit:
+                raise ValueError("ksize %d is above the built limit of %d %s" % (k, limit, "channels" if spectral else "pixels per axis"))
+            if k // 2 > n:
+                raise ValueError("ksize %d reaches more than one axis length (%d samples) past the edge: the limit is "
+                                 "ksize // 2 <= %d (scipy's own versions disagree beyond it)" % (k, n, n))
+        parent, fill = self, self._fill_value
+        fn = ops.rank_filter_axis0 if spectral else ops.rank_filter_plane
+
+        def run(data, mask, view, stream=None):
+            return fn(data, *sizes, rank, mode=mode, cval=cval, fill=fill, mask=mask, stream=stream,
+                      nan_excluded=_nan_term_dropped(parent, view))
+        if self._runs_wide():            # (resident, float64 throughout)
+            return self._derived(run)
+
+        class _Lazy:
+            op = "spectral_filter" if spectral else "spatial_filter"
+            fusable = False
+            keeps_mask = True
+
+            def __init__(self):
+                self.parent = parent
+
+            def __call__(self):
+                return run(parent._device_data(), parent._mask_spec(), parent)
+
+        def part(dev, mspec, stream):    # a strip of whole spaxels / a slab of whole planes of an out-of-core parent
+            return run(dev, mspec, parent, stream)
+        lazy = _Lazy()
+        setattr(lazy, "strip_fn" if spectral else "slab_fn", part)
+        return self._new_cube_with(lazy=lazy, shape=self._shape)
+
+    def spectral_filter(self, ksize, filter, **kwargs):
+        """Filter every spectrum with one of scipy.ndimage's rank filters over a window of *ksize* channels
+        (spectral_cube.py:2844-2868, dask_spectral_cube.py:926-960).  *filter*: ``median_filter``, ``minimum_filter``,
+        ``maximum_filter``, ``percentile_filter`` (with ``percentile=``) or ``rank_filter`` (with ``rank=``) - the scipy
+        function itself (recognised by its name; scipy is never imported here) or that name as a string; anything else
+        raises NotImplementedError.  Keywords ``mode`` ('reflect', the default, 'constant', 'nearest', 'mirror', 'wrap')
+        and ``cval`` are scipy's; ``origin`` other than 0 and ``footprint`` are not built; ``use_memmap``, ``verbose``,
+        ``num_cores``, ``parallel``, ``update_function`` and ``save_to_tmp_dir`` are accepted and ignored.
+
+        The filter runs on the filled data (masked samples -> fill_value) and the mask is left unchanged.  An even
+        *ksize* behaves as in scipy: ``ksize // 2`` samples back, the rest forward, the median the upper middle sample.
+        A spectrum without one included sample is left as it is (:147-159).  By design a NaN ranks LAST in its window
+        (numpy's sort order: the result is ``np.sort(window)[rank]``), where scipy's result depends on its version; on
+        windows without a NaN the two agree bit for bit.  Limits: ksize 1 ... 129 and ``ksize // 2 <= nz``.
+
+        Pending like ``spectral_smooth``; a parent larger than the HBM budget runs strip by strip."""
+        if isinstance(ksize, (bool, np.bool_)):
+            raise TypeError("ksize should be an integer (got {0})".format(ksize))
+        try:
+            integral = float(ksize).is_integer()
+        except (TypeError, ValueError):
+            integral = False
+        if not integral:
+            raise TypeError("ksize should be an integer (got {0})".format(ksize))
+        return self._rank_filtered((int(ksize),), self._shape[:1], filter, kwargs)
+
+    def spectral_smooth_median(self, ksize, **kwargs):
+        """Median-filter every spectrum over *ksize* channels (spectral_cube.py:2870-2898): ``spectral_filter`` with
+        ``median_filter`` (a ``filter=`` keyword names another member of the family, as in the reference)."""
+        return self.spectral_filter(ksize, kwargs.pop("filter", "median_filter"), **kwargs)
+
+    def spatial_filter(self, ksize, filter, raise_error_jybm=True, **kwargs):
+        """Filter every image plane with one of scipy.ndimage's rank filters over a window of *ksize* pixels, one integer
+        or ``(ky, kx)`` (spectral_cube.py:2775-2806, dask_spectral_cube.py:995-1021).  Filters, keywords, the filled data,
+        the unchanged mask and the NaN-last rule as ``spectral_filter``; a plane without one included sample is left as
+        it is (:161-172).  Limits: ky, kx 1 ... 15 and ``k // 2`` at most the axis length.  A parent larger than the HBM
+        budget runs in slabs of whole planes."""
+        self.check_jybeam_smoothing(raise_error_jybm=raise_error_jybm)
+        sizes = tuple(ksize) if isinstance(ksize, (tuple, list, np.ndarray)) else (ksize, ksize)
+        if len(sizes) != 2 or any(isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer, float, np.floating))
+                                  or not float(k).is_integer() for k in sizes):
+            raise TypeError("ksize should be an integer or a pair of integers (got {0})".format(ksize))
+        return self._rank_filtered(tuple(int(k) for k in sizes), self._shape[1:], filter, kwargs)
+
+    def spatial_smooth_median(self, ksize, raise_error_jybm=True, **kwargs):
+        """Median-filter every image plane (spectral_cube.py:2749-2772): ``spatial_filter`` with ``median_filter``."""
+        return self.spatial_filter(ksize, kwargs.pop("filter", "median_filter"), raise_error_jybm=raise_error_jybm, **kwargs)
 
     @property
     def beam(self):

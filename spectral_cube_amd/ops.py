@@ -362,6 +362,37 @@ def downsample(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fi
     return out, out_mask
 
 
+def _rank_filter(base, cube, sizes, rank, mode, cval, fill, mask, out, stream, nan_excluded):
+    name, dtype = _entry(base, cube)
+    if mode not in _lib.RANK_MODES:
+        raise ValueError("mode must be one of %s (got %r)" % (", ".join(sorted(_lib.RANK_MODES)), mode))
+    if out is None:
+        out = DeviceArray(cube.shape, dtype, cube.device)
+    if tuple(out.shape) != tuple(cube.shape) or out.dtype != dtype:
+        raise ValueError("preallocated output must be %s %s" % (tuple(cube.shape), dtype))
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    ors, ops_ = _strides(out)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+              *[int(s) for s in sizes], int(rank), _lib.RANK_MODES[mode], float(cval), C.c_void_p(out.ptr), ors, ops_)
+    return out
+
+
+def rank_filter_axis0(cube, ksize, rank, mode="reflect", cval=0.0, fill=np.nan, mask=None, out=None, stream=None,
+                      nan_excluded=False):
+    """element *rank* of the sorted window of *ksize* FILLED samples along the spectral axis, for every voxel = the chunk
+    function of spectral_smooth_median / spectral_filter with one of scipy.ndimage's rank filters (spectral_cube.py:2844-2898,
+    dask_spectral_cube.py:920-960); *mode* / *cval* as scipy names them.  NaN ranks last (``np.sort(window)[rank]``).  The
+    result has the cube's dtype and holds samples of the cube bit for bit.  *nan_excluded* as for ``downsample``."""
+    return _rank_filter("rank_filter_axis0", cube, (ksize,), rank, mode, cval, fill, mask, out, stream, nan_excluded)
+
+
+def rank_filter_plane(cube, ky, kx, rank, mode="reflect", cval=0.0, fill=np.nan, mask=None, out=None, stream=None,
+                      nan_excluded=False):
+    """rank_filter_axis0 with a window of *ky* x *kx* samples of every image plane: spatial_smooth_median / spatial_filter
+    (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029)"""
+    return _rank_filter("rank_filter_plane", cube, (ky, kx), rank, mode, cval, fill, mask, out, stream, nan_excluded)
+
+
 def normalize_view(view, shape):
     """(start, step, length) per axis of a tuple of three slices applied to *shape* (``slice.indices``, as numpy indexes)"""
     out = []
