@@ -403,6 +403,40 @@ int spc_rank_filter_plane_f64(int device, void* stream, const spc_cube_f64* cube
                               double fill, int ky, int kx, int rank, int mode, double cval,
                               double* d_out, int64_t out_row_stride, int64_t out_plane_stride);
 
+/* ---- stack_spectra: Fourier-shift every spectrum by its own number of channels, and stack ----
+ * spectral_cube.analysis_utilities: stack_spectra (analysis_utilities.py:134-318), fourier_shift (:14-78) and
+ * _fourier_shifter (:81-94).  For each of the npos positions d_idx[p] (int32, the flat spaxel index y * nx + x of the
+ * cube view) the FILLED spectrum (masked voxels -> fill; nan_excluded as for the downsample entry points) is zero-padded
+ * by pad_lo channels in front and pad_hi behind (M = nz + pad_lo + pad_hi) and shifted by d_shift[p] channels (float64,
+ * any sign, fractional) exactly as the reference's fft / phase ramp / ifft does: the circular convolution
+ *     out[n] = sum_j x[j] h_M(n - j - s),   h_M(t) = sin(pi t) / (M sin(pi t / M))  (M odd),
+ *                                            h_M(t) = sin(pi t) / (M tan(pi t / M))  (M even),   1 where M divides t
+ * summed directly in float64 for float32 and float64 cubes alike.  NaN as in fourier_shift (:35-78): non-finite samples
+ * count as 0; a spectrum that has some also has its indicator (1 / 0) shifted, and output samples where that exceeds 0.5
+ * are NaN; a spectrum without one finite sample, a non-finite shift or a position outside the map gives an all-NaN row.
+ *   _shift: d_out (M, npos) float64, C-contiguous, receives the shifted spectra, one per column.
+ *   _sum:   the shifted spectra are never written; d_sum[M] receives the sum over the rows that are not NaN at that
+ *           channel, d_count[M] their number and d_nan[M] the number of rows that are NaN there (int64 both), from which
+ *           the host finishes np.nanmean / np.mean / np.nansum / np.sum.  Partial sums are kept per block in the workspace
+ *           and added in a fixed order by a second kernel: no floating-point atomics, the split depends on the sizes
+ *           alone, two runs agree bit for bit.
+ * M up to SPC_STACK_MAX_CHANNELS, else SPC_ERR_UNSUPPORTED; no limit on npos or on any axis.  d_workspace: the number
+ * of bytes the workspace query below returns for the same sizes (fused = 1 for _sum).  Everything is queued on the stream. */
+#define SPC_STACK_MAX_CHANNELS 8192
+size_t spc_stack_workspace_bytes(int64_t nz, int64_t npos, int pad_lo, int pad_hi, int fused);
+int spc_stack_shift_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
+                        const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_out,
+                        void* d_workspace, size_t workspace_bytes);
+int spc_stack_shift_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
+                        const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_out,
+                        void* d_workspace, size_t workspace_bytes);
+int spc_stack_sum_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
+                      const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_sum,
+                      int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes);
+int spc_stack_sum_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
+                      const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_sum,
+                      int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

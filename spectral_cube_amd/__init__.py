@@ -18,3 +18,5 @@ from .masks import (BooleanArrayMask, LazyMask, LazyComparisonMask, CompositeMas
 from .kernels import (Gaussian1DKernel, Gaussian2DKernel, Box1DKernel, Tophat2DKernel,  # noqa: F401
                       CustomKernel)
 from .wcs import SimpleWCS  # noqa: F401
+from . import analysis_utilities  # noqa: F401
+from .analysis_utilities import stack_spectra, BadVelocitiesWarning  # noqa: F401

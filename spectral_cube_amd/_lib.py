@@ -33,6 +33,8 @@ DS_NANMEAN, DS_NANSUM, DS_NANMAX, DS_NANMIN, DS_MEAN, DS_SUM, DS_MAX, DS_MIN = r
 # spc_rank_mode and the built window limits (spc_rank_filter_axis0_* / _plane_*)
 RANK_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}
 RANK_FILTER_MAX_KSIZE, RANK_FILTER_MAX_KSIZE_SPATIAL = 129, 15
+# the longest padded spectrum of spc_stack_shift_* / spc_stack_sum_*
+STACK_MAX_CHANNELS = 8192
 
 
 class HipLibraryError(RuntimeError):
@@ -173,6 +175,11 @@ SIGNATURES = {
     "spc_rank_filter_axis0_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _d, _vp, _i64, _i64]),
     "spc_rank_filter_plane_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _i, _f, _vp, _i64, _i64]),
     "spc_rank_filter_plane_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _i, _d, _vp, _i64, _i64]),
+    "spc_stack_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
+    "spc_stack_shift_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz]),
+    "spc_stack_shift_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz]),
+    "spc_stack_sum_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    "spc_stack_sum_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz]),
     "spc_moments_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _d, _vp, _vp, _vp]),
     "spc_moment_order_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i, _vp, _vp]),
     "spc_spectral_conv_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _i, _vp, _i64, _i64, _vp, _sz]),

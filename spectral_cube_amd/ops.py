@@ -393,6 +393,67 @@ def rank_filter_plane(cube, ky, kx, rank, mode="reflect", cval=0.0, fill=np.nan,
     return _rank_filter("rank_filter_plane", cube, (ky, kx), rank, mode, cval, fill, mask, out, stream, nan_excluded)
 
 
+def _stack_inputs(cube, idx, shifts, pad, fused):
+    """(device idx, device shifts, npos, (pad_lo, pad_hi), workspace) of the two stack operators: the positions are checked on
+    the host (the kernel would give an all-NaN row for one outside the map) and travel as int32"""
+    idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+    shifts = np.ascontiguousarray(shifts, dtype=np.float64).ravel()
+    nz, ny, nx = cube.shape
+    if idx.size < 1 or idx.size != shifts.size:
+        raise ValueError("need one shift per position and at least one position (got %d and %d)" % (idx.size, shifts.size))
+    if ny * nx > 2**31 - 1:
+        raise ValueError("a map of %d x %d spaxels does not index with int32" % (ny, nx))
+    if idx.min() < 0 or idx.max() >= ny * nx:
+        raise IndexError("position outside the %d x %d map" % (ny, nx))
+    pad_lo, pad_hi = int(pad[0]), int(pad[1])
+    if pad_lo < 0 or pad_hi < 0:
+        raise ValueError("pads must not be negative (got %r)" % (pad,))
+    need = int(_lib.load().spc_stack_workspace_bytes(nz, idx.size, min(pad_lo, 2**30), min(pad_hi, 2**30), 1 if fused else 0))
+    ws = DeviceArray((max(need, 256),), np.uint8, cube.device)
+    d_idx = DeviceArray.from_numpy(idx.astype(np.int32), cube.device)
+    d_shift = DeviceArray.from_numpy(shifts, cube.device)
+    return d_idx, d_shift, idx.size, (min(pad_lo, 2**30), min(pad_hi, 2**30)), ws
+
+
+def stack_shift(cube, idx, shifts, pad=(0, 0), fill=np.nan, mask=None, out=None, stream=None, nan_excluded=False):
+    """(M, P) float64 DeviceArray of the P filled spectra at the flat spaxel indices *idx* (y * nx + x), zero-padded by
+    *pad* = (front, back) channels and Fourier-shifted by *shifts* channels each: column p is
+    ``fourier_shift(cube.filled_data[:, y, x], shifts[p], add_pad=True, pad_size=pad)`` (analysis_utilities.py:14-94), M = nz
+    + front + back.  A NaN shift or a spectrum without a finite sample gives an all-NaN column.  *idx* and *shifts* are host
+    arrays.  M above _lib.STACK_MAX_CHANNELS raises HipUnsupported."""
+    name, _ = _entry("stack_shift", cube)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    d_idx, d_shift, npos, (pad_lo, pad_hi), ws = _stack_inputs(cube, idx, shifts, pad, False)
+    shape = (cube.shape[0] + pad_lo + pad_hi, npos)
+    if out is None:
+        out = DeviceArray(shape if shape[0] <= _lib.STACK_MAX_CHANNELS else (1, 1), np.float64, cube.device)
+    elif tuple(out.shape) != shape or out.dtype != _F64:
+        raise ValueError("preallocated output must be %s float64" % (shape,))
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+              C.c_void_p(d_idx.ptr), C.c_void_p(d_shift.ptr), npos, pad_lo, pad_hi, C.c_void_p(out.ptr), C.c_void_p(ws.ptr), ws.nbytes)
+    if stream is not None:                   # (the inputs and the workspace go back to the pool when this returns)
+        _lib.call("spc_stream_sync", cube.device, _sh(stream))
+    return out
+
+
+def stack_sum(cube, idx, shifts, pad=(0, 0), fill=np.nan, mask=None, stream=None, nan_excluded=False):
+    """(sum, count, nan_count) over the rows of ``stack_shift`` without writing them: per output channel the float64 sum of
+    the rows that are not NaN there, their number and the number of rows that are NaN (int64), as host arrays of length M -
+    what np.nanmean / np.mean / np.nansum / np.sum of stack_spectra (analysis_utilities.py:301-304) are finished from.
+    Reproducible: partial sums per block, added in a fixed order."""
+    name, _ = _entry("stack_sum", cube)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    d_idx, d_shift, npos, (pad_lo, pad_hi), ws = _stack_inputs(cube, idx, shifts, pad, True)
+    M = min(cube.shape[0] + pad_lo + pad_hi, _lib.STACK_MAX_CHANNELS)
+    total = DeviceArray((M,), np.float64, cube.device)
+    count = DeviceArray((M,), np.int64, cube.device)
+    nnan = DeviceArray((M,), np.int64, cube.device)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
+              C.c_void_p(d_idx.ptr), C.c_void_p(d_shift.ptr), npos, pad_lo, pad_hi, C.c_void_p(total.ptr), C.c_void_p(count.ptr),
+              C.c_void_p(nnan.ptr), C.c_void_p(ws.ptr), ws.nbytes)
+    return total.get(stream), count.get(stream), nnan.get(stream)
+
+
 def normalize_view(view, shape):
     """(start, step, length) per axis of a tuple of three slices applied to *shape* (``slice.indices``, as numpy indexes)"""
     out = []
