@@ -58,7 +58,11 @@ typedef enum {
  *   LazyMask(np.isfinite) (io/fits.py:214) -> SPC_MASK_FINITE
  *   LazyComparisonMask cube > x etc. (masks.py:670-758) -> SPC_MASK_GT/GE/LT/LE
  * Flags are AND-ed (CompositeMask 'and', masks.py:425-435).  Other
- * compositions are materialised to a uint8 array by the host.
+ * compositions (or / xor / not, == and !=, thresholds that are maps, spectra
+ * or cubes, terms on several cubes) are compiled into a spc_mask_program and
+ * evaluated once on the device into a uint8 array (spc_mask_eval_*, below);
+ * only what that cannot express (an arbitrary Python function) is
+ * materialised by the host.
  * A voxel is "valid" when it is included AND its value is not NaN (NaN-filled
  * data fed to nansum, dask_spectral_cube.py:1083). */
 #define SPC_MASK_NONE   0u
@@ -367,6 +371,72 @@ int spc_mask_bbox_f32(int device, void* stream, const spc_cube_f32* cube, const 
                       int64_t* d_box);
 int spc_mask_bbox_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                       int64_t* d_box);
+
+/* ---- mask expressions evaluated once on the device (masks.py:239-250 composition, :399-455 CompositeMask / InvertedMask,
+ * :670-758 LazyComparisonMask) ----
+ * A mask tree that is not an AND of spc_mask terms - a threshold that is a map, a spectrum or a cube, `|` `^` `~`, == and
+ * !=, terms on several cubes - is compiled by the host into a postfix program; one kernel runs it over the cube and writes
+ * the uint8 include array (1 / 0), which every other entry point then takes as SPC_MASK_ARRAY.
+ *   data slots: the cubes comparison terms read, all (nz, ny, nx) samples of the entry point's type (float for _f32, double
+ *     for _f64); strides in elements, 0 = C-contiguous.  Only z * plane_stride + y * row_stride + x is ever formed, so the
+ *     views of rows / planes / exchanged first axes are accepted.
+ *   operands: arrays a term is compared with or loaded from: float, double or uint8 elements and one ELEMENT stride per
+ *     axis, 0 = broadcast along that axis (a (ny, nx) map has stride_z 0, a spectrum stride_y = stride_x = 0).
+ *   instructions, postfix, over a stack of include bits:
+ *     SPC_MOP_CMP     push  slot[slot] <cmp> (operand >= 0 ? operands[operand] : imm); a uint8 operand is invalid
+ *     SPC_MOP_FINITE  push  isfinite(slot[slot])
+ *     SPC_MOP_LOAD    push  operands[operand] != 0; the operand must be uint8
+ *     SPC_MOP_NOT     negate the top;  SPC_MOP_AND / _OR / _XOR  pop two, push the result
+ * A comparison converts the sample to double (exact) and compares it with the double threshold under IEEE rules: a NaN
+ * on either side is false, true for SPC_CMP_NE - numpy's result for a Python scalar rounded to the sample type by the
+ * host, a typed scalar, and bool / integer / float16 / float32 / float64 arrays (all but float32 converted to float64).
+ * The program travels as kernel arguments: wave-uniform, the interpreter loop does not diverge.  A lane owns 4 consecutive
+ * x: slots and unit-stride operands are read with 16-byte loads and the 4 include bytes leave in one 4-byte store wherever
+ * a row's addresses allow, sample by sample at the ends of a row and in rows that are not aligned; every slot is read once
+ * however many terms name it.  No LDS, no atomics, no workspace; launches are split inside: no limit on any axis.
+ * SPC_ERR_INVALID, before anything is queued and with d_out untouched: a NULL pointer, a count beyond the limits below, an
+ * unknown opcode / comparison / element type, a slot or operand index out of range, a float operand under SPC_MOP_LOAD or
+ * a uint8 one under SPC_MOP_CMP, a stack that underflows or grows past SPC_MASK_PROG_MAX_STACK, a program that does not
+ * leave exactly one value.  d_out: uint8, strides in elements (0 = C-contiguous). */
+#define SPC_MASK_PROG_MAX_SLOTS    4
+#define SPC_MASK_PROG_MAX_OPERANDS 8
+#define SPC_MASK_PROG_MAX_INSTR    16
+#define SPC_MASK_PROG_MAX_STACK    8
+typedef enum {
+    SPC_MOP_CMP = 0, SPC_MOP_FINITE = 1, SPC_MOP_LOAD = 2, SPC_MOP_NOT = 3, SPC_MOP_AND = 4, SPC_MOP_OR = 5, SPC_MOP_XOR = 6
+} spc_mask_opcode;
+typedef enum {
+    SPC_CMP_GT = 0, SPC_CMP_GE = 1, SPC_CMP_LT = 2, SPC_CMP_LE = 3, SPC_CMP_EQ = 4, SPC_CMP_NE = 5
+} spc_mask_cmp;
+typedef enum { SPC_ELEM_F32 = 0, SPC_ELEM_F64 = 1, SPC_ELEM_U8 = 2 } spc_mask_elem;
+typedef struct {
+    const void* d_data;          /* float (_f32) or double (_f64) samples of a (nz, ny, nx) cube */
+    int64_t row_stride;          /* elements; 0 = nx */
+    int64_t plane_stride;        /* elements; 0 = ny * row_stride */
+} spc_mask_slot;
+typedef struct {
+    const void* d_data;
+    int32_t elem;                /* spc_mask_elem */
+    int32_t reserved;
+    int64_t stride_z, stride_y, stride_x;   /* elements, >= 0; 0 = broadcast along that axis */
+} spc_mask_operand;
+typedef struct {
+    int32_t opcode;              /* spc_mask_opcode */
+    int32_t slot;                /* CMP, FINITE */
+    int32_t cmp;                 /* CMP: spc_mask_cmp */
+    int32_t operand;             /* CMP: operand index, or -1 = compare with imm; LOAD: operand index */
+    double imm;
+} spc_mask_instr;
+typedef struct {
+    int32_t n_slots, n_operands, n_instr, reserved;
+    spc_mask_slot slots[SPC_MASK_PROG_MAX_SLOTS];
+    spc_mask_operand operands[SPC_MASK_PROG_MAX_OPERANDS];
+    spc_mask_instr instr[SPC_MASK_PROG_MAX_INSTR];
+} spc_mask_program;
+int spc_mask_eval_f32(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask_program* prog,
+                      uint8_t* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_mask_eval_f64(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask_program* prog,
+                      uint8_t* d_out, int64_t out_row_stride, int64_t out_plane_stride);
 
 /* ---- rank filters: median / minimum / maximum / percentile / rank over a sliding window ----
  * spectral_smooth_median / spectral_filter (spectral_cube.py:2844-2898, dask_spectral_cube.py:920-960) and

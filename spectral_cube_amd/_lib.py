@@ -35,6 +35,11 @@ RANK_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}
 RANK_FILTER_MAX_KSIZE, RANK_FILTER_MAX_KSIZE_SPATIAL = 129, 15
 # the longest padded spectrum of spc_stack_shift_* / spc_stack_sum_*
 STACK_MAX_CHANNELS = 8192
+# spc_mask_program (spc_mask_eval_f32 / _f64): limits, spc_mask_opcode, spc_mask_cmp, spc_mask_elem
+MASK_PROG_MAX_SLOTS, MASK_PROG_MAX_OPERANDS, MASK_PROG_MAX_INSTR, MASK_PROG_MAX_STACK = 4, 8, 16, 8
+MOP_CMP, MOP_FINITE, MOP_LOAD, MOP_NOT, MOP_AND, MOP_OR, MOP_XOR = range(7)
+CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_EQ, CMP_NE = range(6)
+ELEM_F32, ELEM_F64, ELEM_U8 = range(3)
 
 
 class HipLibraryError(RuntimeError):
@@ -86,6 +91,26 @@ class SpcCelestialWcs(C.Structure):
     _fields_ = [("proj", C.c_int32), ("sip_order", C.c_int32), ("crpix", C.c_double * 2), ("lin", C.c_double * 4),
                 ("lin_inv", C.c_double * 4), ("alpha_p", C.c_double), ("delta_p", C.c_double), ("phi_p", C.c_double),
                 ("pv1", C.c_double), ("plane0", C.c_double * 2), ("sip_a", C.c_double * 55), ("sip_b", C.c_double * 55)]
+
+
+class SpcMaskSlot(C.Structure):
+    _fields_ = [("d_data", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
+
+
+class SpcMaskOperand(C.Structure):
+    _fields_ = [("d_data", C.c_void_p), ("elem", C.c_int32), ("reserved", C.c_int32),
+                ("stride_z", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
+
+
+class SpcMaskInstr(C.Structure):
+    _fields_ = [("opcode", C.c_int32), ("slot", C.c_int32), ("cmp", C.c_int32), ("operand", C.c_int32), ("imm", C.c_double)]
+
+
+class SpcMaskProgram(C.Structure):
+    """spc_mask_program: the postfix form of a mask tree (masks.compile_mask), run by spc_mask_eval_f32 / _f64"""
+    _fields_ = [("n_slots", C.c_int32), ("n_operands", C.c_int32), ("n_instr", C.c_int32), ("reserved", C.c_int32),
+                ("slots", SpcMaskSlot * MASK_PROG_MAX_SLOTS), ("operands", SpcMaskOperand * MASK_PROG_MAX_OPERANDS),
+                ("instr", SpcMaskInstr * MASK_PROG_MAX_INSTR)]
 
 
 class SpcStatsOutputs(C.Structure):
@@ -171,6 +196,8 @@ SIGNATURES = {
     "spc_subcube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _P(_i64), _P(_i64), _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _d]),
     "spc_mask_bbox_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp]),
     "spc_mask_bbox_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
+    "spc_mask_eval_f32": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),
+    "spc_mask_eval_f64": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _f, _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _d, _vp, _i64, _i64]),
     "spc_rank_filter_plane_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _i, _f, _vp, _i64, _i64]),

@@ -903,6 +903,18 @@ class SpectralCube:
             inc = ops.mask_include(owner._device_data64() if wide else owner._device_data(), ops.MaskSpec(flags, lo, hi, darr),
                                    nan_excluded=M.contains(self._mask, M.NotNaNMask))
             return ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
+        if self._mask is not None:
+            terms = self._mask._device_terms(view(self))
+            if ((terms is None or (terms[3] is not None and 0 in np.asarray(terms[3]).strides and np.size(terms[3]) > 1))
+                    and self._stream_source() is None):
+                # not an AND of device terms (a map / spectrum / cube threshold, | ^ ~, == !=, terms on several cubes), or
+                # an array term smaller than the cube: compiled and evaluated once on the device (ops.mask_eval) - no
+                # host copy of any cube, no broadcast upload.  What compile_mask cannot express takes the host form below
+                prog = M.compile_mask(self._mask, view(self), self._shape, wide)
+                if prog is not None:
+                    prog.slots = [c._device_data64() if wide else c._device_data() for c in prog.slots]
+                    inc = ops.mask_eval(prog, self._shape, self.device, np.float64 if wide else np.float32)
+                    return ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
         flags, lo, hi, arr = M.lower_mask(self._mask, view(self), self._shape)
         darr = DeviceArray.from_numpy(arr, self.device) if arr is not None else None
         return ops.MaskSpec(flags, lo, hi, darr)
@@ -977,6 +989,20 @@ class SpectralCube:
         return self._mask._filled(d, fill=self._fill_value)
 
     unitless_filled_data = filled_data
+
+    def get_mask_array(self):
+        """the include map of the cube's mask as a host bool array, all True without a mask (spectral_cube.py:552).  Of a
+        resident cube it is evaluated on the device (the lowered mask as it is, ops.mask_include or ops.mask_eval) and
+        only the map comes down; an out-of-core cube evaluates the tree on the host."""
+        if self._mask is None:
+            return np.ones(self._shape, dtype=bool)
+        if self._stream_source() is not None:
+            return np.array(np.broadcast_to(self._mask.include(data=self._host_data()), self._shape), dtype=bool)
+        data, mspec, view = self._operand()
+        nan_ex = _nan_term_dropped(self, view)
+        if mspec.flags == _lib.MASK_ARRAY and not nan_ex:
+            return mspec.array.get().view(bool)
+        return ops.mask_include(data, mspec, nan_excluded=nan_ex).get().view(bool)
 
     @property
     def unmasked_data(self):

@@ -8,6 +8,9 @@ Semantics restated from the reference:
   * ``&`` ``|`` ``^`` ``~`` composition (masks.py:239-250, 399-455);
   * BooleanArrayMask (masks.py:457-584), LazyMask (:586-668),
     LazyComparisonMask (:670-758), FunctionMask (:760-803).
+A tree that is not an AND of device terms is compiled into a postfix program
+(:func:`compile_mask`) that the device evaluates once (ops.mask_eval); only
+what has no device form is evaluated here, by numpy (:func:`lower_mask`).
 WCS consistency checks between mask and cube are not reproduced (metadata
 bookkeeping, out of scope).
 """
@@ -310,6 +313,159 @@ def lower_mask(mask, data, shape):
     lo = float(lo) if flags & (_lib.MASK_GT | _lib.MASK_GE) else 0.0
     hi = float(hi) if flags & (_lib.MASK_LT | _lib.MASK_LE) else 0.0
     return (flags, lo, hi, arr)
+
+
+# ---- mask tree -> postfix program for ops.mask_eval (spc_mask_eval_f32 / _f64) -------------------------------------
+_PROG_CMP = {operator.gt: _lib.CMP_GT, operator.ge: _lib.CMP_GE, operator.lt: _lib.CMP_LT, operator.le: _lib.CMP_LE,
+             operator.eq: _lib.CMP_EQ, operator.ne: _lib.CMP_NE}
+_PROG_OP = {"and": _lib.MOP_AND, "or": _lib.MOP_OR, "xor": _lib.MOP_XOR}
+
+
+class MaskProgram:
+    """A mask tree in the postfix form the device evaluates (spc_mask_program, include/spcube_hip.h).
+
+    slots:    the cubes the comparison terms read, in slot order - as compile_mask() returns it the cube objects
+              themselves; ops.mask_eval() wants their DeviceArrays of the path's sample type in their place
+    operands: [(array, (stride_z, stride_y, stride_x))]: un-broadcast C-contiguous host arrays (float32, float64 or
+              uint8) or uint8 DeviceArrays, element strides, 0 = broadcast along that axis
+    instr:    [(opcode, slot, cmp, operand, imm)], _lib.MOP_* / _lib.CMP_*; operand -1 = compare with imm"""
+    __slots__ = ("slots", "operands", "instr")
+
+    def __init__(self):
+        self.slots, self.operands, self.instr = [], [], []
+
+
+class _NotCompilable(Exception):
+    pass
+
+
+def _bcast_strides(arr_shape, shape):
+    """(3-D shape, element strides) of a C-contiguous array of *arr_shape* read as (nz, ny, nx): missing leading axes and
+    axes of length 1 get stride 0"""
+    s3 = (1,) * (3 - len(arr_shape)) + tuple(arr_shape)
+    strides, run = [0, 0, 0], 1
+    for a in (2, 1, 0):
+        if s3[a] != 1:
+            strides[a] = run
+        run *= s3[a]
+    return s3, tuple(strides)
+
+
+def _threshold_ok(dtype):
+    # longdouble is 'f' with more than 8 bytes: numpy would compare in extended precision, which no kernel does
+    return dtype.kind in "biu" or (dtype.kind == "f" and dtype.itemsize <= 8)
+
+
+def compile_mask(mask, data, shape, wide):
+    """*mask* as a :class:`MaskProgram` for kernels that read *data* (the cube, or its float64 view) on the float32 or
+    (*wide*) the float64 path, or None when a term has no device form: FunctionMask, LazyMask of a function other than
+    np.isfinite, a threshold of another dtype or shape, a term bound to a bare array that is not the cube's own, a
+    cube that cannot hand out device samples of the path's type as they are, or a tree beyond the program's limits.
+
+    Thresholds follow numpy (NEP 50): a Python float / int is rounded to the sample type, every other scalar is used
+    as an exact double; arrays stay un-broadcast, float32 as it is and bool / integer / float16 / float64 as float64 -
+    the device compares sample and threshold as doubles, which is numpy's result for each of these."""
+    shape = tuple(int(n) for n in shape)
+    cube = getattr(data, "_cube", data)
+    prog = MaskProgram()
+    seen = {}                                   # id(source array) -> operand index
+
+    def slot_of(ref):
+        if isinstance(ref, _Holder):
+            own = getattr(cube, "_data", None)
+            if own is None or ref._d is not own:
+                raise _NotCompilable
+            ref = cube
+        elif ref._is_same_data(data):
+            ref = cube
+        for i, c in enumerate(prog.slots):
+            if c is ref or c._is_same_data(ref):
+                return i
+        ok = (hasattr(ref, "_device_data") and tuple(ref._shape) == shape and ref._stream_source() is None
+              and (ref._wide_resident() if wide else not ref._is_wide()))
+        if not ok or len(prog.slots) == _lib.MASK_PROG_MAX_SLOTS:
+            raise _NotCompilable
+        prog.slots.append(ref)
+        return len(prog.slots) - 1
+
+    def operand_of(src, arr, arr_shape):
+        if id(src) in seen:
+            return seen[id(src)]
+        try:
+            if np.broadcast_shapes(tuple(arr_shape), shape) != shape:
+                raise _NotCompilable
+        except ValueError:
+            raise _NotCompilable
+        if len(prog.operands) == _lib.MASK_PROG_MAX_OPERANDS:
+            raise _NotCompilable
+        prog.operands.append((arr, _bcast_strides(arr_shape, shape)[1]))
+        seen[id(src)] = len(prog.operands) - 1
+        return seen[id(src)]
+
+    def walk(m):
+        if isinstance(m, CompositeMask):
+            walk(m._mask1)
+            walk(m._mask2)
+            prog.instr.append((_PROG_OP[m._operation], 0, 0, -1, 0.0))
+        elif isinstance(m, InvertedMask):
+            walk(m._mask)
+            prog.instr.append((_lib.MOP_NOT, 0, 0, -1, 0.0))
+        elif isinstance(m, DeviceBooleanMask):
+            dev = m.device_array()
+            if tuple(dev.shape) != shape:
+                raise _NotCompilable
+            if len(prog.operands) == _lib.MASK_PROG_MAX_OPERANDS:
+                raise _NotCompilable
+            prog.operands.append((dev, (getattr(dev, "plane_stride", shape[1] * shape[2]), getattr(dev, "row_stride", shape[2]), 1)))
+            prog.instr.append((_lib.MOP_LOAD, 0, 0, len(prog.operands) - 1, 0.0))
+        elif isinstance(m, BooleanArrayMask):
+            b = m._mask
+            prog.instr.append((_lib.MOP_LOAD, 0, 0, operand_of(b, np.ascontiguousarray(b).view(np.uint8), b.shape), 0.0))
+            if not m._include_flag:
+                prog.instr.append((_lib.MOP_NOT, 0, 0, -1, 0.0))
+        elif isinstance(m, NotNaNMask):
+            # v <= +inf: false for NaN alone - a term of its own, so the include array is complete without nan_excluded
+            prog.instr.append((_lib.MOP_CMP, slot_of(m._data_ref), _lib.CMP_LE, -1, float("inf")))
+        elif isinstance(m, LazyComparisonMask):
+            if m._cmp not in _PROG_CMP:
+                raise _NotCompilable
+            slot, v = slot_of(m._data_ref), m._value
+            if type(v) in (float, int):
+                try:
+                    imm = float(v) if wide else float(np.float32(v))
+                except OverflowError:
+                    raise _NotCompilable
+                prog.instr.append((_lib.MOP_CMP, slot, _PROG_CMP[m._cmp], -1, imm))
+                return
+            try:
+                a = np.asarray(v)
+            except Exception:
+                raise _NotCompilable
+            if not _threshold_ok(a.dtype):
+                raise _NotCompilable
+            if a.ndim == 0:
+                prog.instr.append((_lib.MOP_CMP, slot, _PROG_CMP[m._cmp], -1, float(a)))
+                return
+            up = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+            prog.instr.append((_lib.MOP_CMP, slot, _PROG_CMP[m._cmp], operand_of(v, up, a.shape), 0.0))
+        elif type(m) is LazyMask and m._function is np.isfinite:
+            prog.instr.append((_lib.MOP_FINITE, slot_of(m._data_ref), 0, -1, 0.0))
+        else:
+            raise _NotCompilable
+
+    try:
+        walk(mask)
+    except _NotCompilable:
+        return None
+    if len(prog.instr) > _lib.MASK_PROG_MAX_INSTR:
+        return None
+    depth = deepest = 0
+    for op in prog.instr:
+        depth += {_lib.MOP_NOT: 0, _lib.MOP_AND: -1, _lib.MOP_OR: -1, _lib.MOP_XOR: -1}.get(op[0], 1)
+        deepest = max(deepest, depth)
+    if deepest > _lib.MASK_PROG_MAX_STACK:
+        return None
+    return prog
 
 
 def contains(mask, cls):

@@ -1036,6 +1036,54 @@ def mask_include(cube, mask=None, nan_excluded=False, stream=None):
     return out
 
 
+_ELEM = {np.dtype(np.float32): _lib.ELEM_F32, np.dtype(np.float64): _lib.ELEM_F64, np.dtype(np.uint8): _lib.ELEM_U8,
+         np.dtype(bool): _lib.ELEM_U8}
+
+
+def mask_eval(program, shape, device, dtype, out=None, stream=None):
+    """uint8 (nz, ny, nx) DeviceArray: 1 where the mask tree compiled into *program* (masks.compile_mask, with the
+    DeviceArrays of sample type *dtype* as its slots) includes the voxel - CompositeMask / InvertedMask over comparison,
+    isfinite and boolean-array terms (masks.py:239-250, 399-455, 670-758) in one pass over the cubes it names
+    (spc_mask_eval_f32 / _f64).  Host operands are uploaded un-broadcast; they stay alive with the result.  *out* may be
+    a strided view of a larger array."""
+    shape = tuple(int(n) for n in shape)
+    name, dtype = _entry("mask_eval", np.empty(0, dtype=np.dtype(dtype)))
+    if np.dtype(dtype) not in (_F32, _F64) or len(shape) != 3:
+        raise TypeError("mask_eval runs on float32 or float64 cubes of shape (nz, ny, nx)")
+    if (len(program.slots) > _lib.MASK_PROG_MAX_SLOTS or len(program.operands) > _lib.MASK_PROG_MAX_OPERANDS
+            or len(program.instr) > _lib.MASK_PROG_MAX_INSTR):
+        raise ValueError("mask program beyond the limits of spc_mask_program (%d slots, %d operands, %d instructions)"
+                         % (_lib.MASK_PROG_MAX_SLOTS, _lib.MASK_PROG_MAX_OPERANDS, _lib.MASK_PROG_MAX_INSTR))
+    p = _lib.SpcMaskProgram()
+    p.n_slots, p.n_operands, p.n_instr = len(program.slots), len(program.operands), len(program.instr)
+    for i, s in enumerate(program.slots):
+        if s.dtype != dtype or tuple(s.shape) != shape:
+            raise TypeError("data slot %d must be a %s DeviceArray of shape %s" % (i, np.dtype(dtype).name, shape))
+        p.slots[i].d_data = s.ptr
+        p.slots[i].row_stride, p.slots[i].plane_stride = _strides(s)
+    held = []
+    for i, (a, strides) in enumerate(program.operands):
+        if not isinstance(a, DeviceArray):
+            a = DeviceArray.from_numpy(a, device, stream)
+        if a.dtype not in _ELEM:
+            raise TypeError("operand %d: float32, float64 or uint8 elements, not %s" % (i, a.dtype))
+        held.append(a)
+        o = p.operands[i]
+        o.d_data, o.elem = a.ptr, _ELEM[a.dtype]
+        o.stride_z, o.stride_y, o.stride_x = (int(v) for v in strides)
+    for i, (opcode, slot, cmp_, operand, imm) in enumerate(program.instr):
+        q = p.instr[i]
+        q.opcode, q.slot, q.cmp, q.operand, q.imm = int(opcode), int(slot), int(cmp_), int(operand), float(imm)
+    if out is None:
+        out = DeviceArray(shape, np.uint8, device)
+    elif tuple(out.shape) != shape or out.dtype != np.uint8:
+        raise ValueError("preallocated output must be %s uint8" % (shape,))
+    ors, ops_ = _strides(out)
+    _lib.call(name, device, _sh(stream), shape[0], shape[1], shape[2], C.byref(p), C.c_void_p(out.ptr), ors, ops_)
+    out._mask_operands = held       # the kernel may still be queued: the operands live as long as the result
+    return out
+
+
 def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, out=None):
     """q-th percentile along x per (z, y) row, no transposed copy (spc_percentile_axis2_f32); *center*: a (nz, ny)
     float32 DeviceArray.  Raises HipUnsupported for rows of more than 4096 samples."""
