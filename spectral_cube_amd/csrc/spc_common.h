@@ -6,6 +6,8 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <cmath>
+#include <limits>
 #include "../../include/spcube_hip.h"
 
 void spc_set_error(const char* fmt, ...);
@@ -117,42 +119,59 @@ static inline hipError_t spc_flags_clear(unsigned char* d_flags, size_t n, hipSt
     return n ? hipMemsetAsync(d_flags, 0, n, st) : hipSuccess;
 }
 
-// ---- device-side mask evaluation -----------------------------------------
+// ---- the mask of a cube on the device, float32 or float64 ----------------------------------------------------
+// One layer for both sample types: T = float goes with (spc_cube_f32, spc_mask), T = double with (spc_cube_f64,
+// spc_mask_f64), whose thresholds stay float64 (numpy compares a float64 cube in float64, spectral_cube/masks.py:225).
+template <typename T> struct SpcAbi;
+template <> struct SpcAbi<float> { typedef spc_cube_f32 cube; typedef spc_mask mask; };
+template <> struct SpcAbi<double> { typedef spc_cube_f64 cube; typedef spc_mask_f64 mask; };
+
+__host__ __device__ __forceinline__ float spc_abs(float v) { return fabsf(v); }
+__host__ __device__ __forceinline__ double spc_abs(double v) { return fabs(v); }
+__host__ __device__ __forceinline__ int64_t spc_min64(int64_t a, int64_t b) { return a < b ? a : b; }
+static inline bool spc_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
 // mask predicate -> |v| <= lim && !(v <= lo) && !(v >= hi): three compares whatever the flags.  An absent bound is
 // NaN (the negated compare is then true for every v), >= / <= become strict compares against the neighbouring float,
-// a NaN threshold rejects everything (numpy: x > nan is False); lim = FLT_MAX under isfinite, +inf otherwise (NaN
-// samples fail |v| <= lim either way: they are never valid).
-static inline void spc_canonical_pred(uint32_t f, float thr_lo, float thr_hi, float* lim, float* lo, float* hi) {
-    *lim = (f & SPC_MASK_FINITE) ? 3.402823466e+38f : INFINITY;
-    *lo = NAN;
-    *hi = NAN;
+// a NaN threshold rejects everything (numpy: x > nan is False); lim = FLT_MAX / DBL_MAX under isfinite, +inf otherwise
+// (NaN samples fail |v| <= lim either way: they are never valid).
+template <typename T>
+static inline void spc_canonical_pred(uint32_t f, T thr_lo, T thr_hi, T* lim, T* lo, T* hi) {
+    const T inf = std::numeric_limits<T>::infinity();
+    *lim = (f & SPC_MASK_FINITE) ? std::numeric_limits<T>::max() : inf;
+    *lo = (T)NAN;
+    *hi = (T)NAN;
     if (f & (SPC_MASK_GT | SPC_MASK_GE)) {
-        if (thr_lo != thr_lo) *lim = -1.f;
+        if (thr_lo != thr_lo) *lim = (T)-1;
         else if (f & SPC_MASK_GT) *lo = thr_lo;
-        else *lo = (thr_lo == -INFINITY) ? NAN : nextafterf(thr_lo, -INFINITY);
+        else *lo = (thr_lo == -inf) ? (T)NAN : std::nextafter(thr_lo, -inf);
     }
     if (f & (SPC_MASK_LT | SPC_MASK_LE)) {
-        if (thr_hi != thr_hi) *lim = -1.f;
+        if (thr_hi != thr_hi) *lim = (T)-1;
         else if (f & SPC_MASK_LT) *hi = thr_hi;
-        else *hi = (thr_hi == INFINITY) ? NAN : nextafterf(thr_hi, INFINITY);
+        else *hi = (thr_hi == inf) ? (T)NAN : std::nextafter(thr_hi, inf);
     }
 }
 
-struct MaskDev {
+template <typename T>
+struct SpcMaskDev {
     uint32_t flags;
-    float thr_lo, thr_hi;
+    T thr_lo, thr_hi;
     const uint8_t* arr;
     int64_t row_stride, plane_stride;
-    float lim, lo, hi;           // the predicate terms in canonical form (spc_canonical_pred), set by spc_mask_to_dev
+    T lim, lo, hi;               // the predicate terms in canonical form (spc_canonical_pred), set by spc_mask_to_dev
 };
+using MaskDev = SpcMaskDev<float>;
+using MaskDev64 = SpcMaskDev<double>;
 
-static inline int spc_mask_to_dev(const spc_mask* m, const spc_cube_f32* c, MaskDev* out) {
-    out->flags = 0; out->thr_lo = 0.f; out->thr_hi = 0.f; out->arr = nullptr;
+template <typename T>
+static inline int spc_mask_to_dev(const typename SpcAbi<T>::mask* m, const typename SpcAbi<T>::cube* c, SpcMaskDev<T>* out) {
+    out->flags = 0; out->thr_lo = 0; out->thr_hi = 0; out->arr = nullptr;
     out->row_stride = c->row_stride; out->plane_stride = c->plane_stride;
-    spc_canonical_pred(0u, 0.f, 0.f, &out->lim, &out->lo, &out->hi);
+    spc_canonical_pred<T>(0u, 0, 0, &out->lim, &out->lo, &out->hi);
     if (!m) return SPC_OK;
     out->flags = m->flags; out->thr_lo = m->thr_lo; out->thr_hi = m->thr_hi;
-    spc_canonical_pred(m->flags, m->thr_lo, m->thr_hi, &out->lim, &out->lo, &out->hi);
+    spc_canonical_pred<T>(m->flags, m->thr_lo, m->thr_hi, &out->lim, &out->lo, &out->hi);
     if (m->flags & SPC_MASK_ARRAY) {
         SPC_REQUIRE(m->d_array != nullptr, "SPC_MASK_ARRAY set but d_array is NULL");
         out->arr = m->d_array;
@@ -163,7 +182,9 @@ static inline int spc_mask_to_dev(const spc_mask* m, const spc_cube_f32* c, Mask
     return SPC_OK;
 }
 
-static inline int spc_check_cube(const spc_cube_f32* c) {
+// C: spc_cube_f32 or spc_cube_f64
+template <typename C>
+static inline int spc_check_cube(const C* c) {
     SPC_REQUIRE(c != nullptr && c->d_data != nullptr, "cube pointer is NULL");
     SPC_REQUIRE(c->nz > 0 && c->ny > 0 && c->nx > 0, "cube shape must be positive (got %lld,%lld,%lld)",
                 (long long)c->nz, (long long)c->ny, (long long)c->nx);
@@ -174,13 +195,63 @@ static inline int spc_check_cube(const spc_cube_f32* c) {
 
 // for kernels that only ever form z * plane_stride + y * row_stride + x: also accepts a view whose
 // first two axes are exchanged (row_stride > plane_stride), e.g. selection along y instead of z
-static inline int spc_check_cube_any_order(const spc_cube_f32* c) {
+template <typename C>
+static inline int spc_check_cube_any_order(const C* c) {
     SPC_REQUIRE(c != nullptr && c->d_data != nullptr, "cube pointer is NULL");
     SPC_REQUIRE(c->nz > 0 && c->ny > 0 && c->nx > 0, "cube shape must be positive (got %lld,%lld,%lld)",
                 (long long)c->nz, (long long)c->ny, (long long)c->nx);
     SPC_REQUIRE(c->row_stride >= c->nx && c->plane_stride >= c->nx, "row / plane stride smaller than nx");
     SPC_REQUIRE(c->plane_stride >= c->row_stride * (c->ny - 1) + c->nx ||
                 c->row_stride >= c->plane_stride * (c->nz - 1) + c->nx, "overlapping rows and planes");
+    return SPC_OK;
+}
+
+// The views spc_check_cube accepts, refused in the words the float64 rank filter and stack have always used (those of
+// spc_check_cube_any_order, then the plane stride): kept so that no message moves; nothing else should call it.
+template <typename C>
+static inline int spc_check_cube_any_order_words(const C* c) {
+    const int rc = spc_check_cube_any_order(c);
+    if (rc) return rc;
+    SPC_REQUIRE(c->plane_stride >= c->row_stride * (c->ny - 1) + c->nx, "plane_stride too small");
+    return SPC_OK;
+}
+
+// the float64 moment kernel packs a count and two z indices into 21 bits each; every entry point of spc_wide_ops.hip
+// has carried its bound too.  Called after the cube check proper
+static inline int spc_check_nz_f64(const spc_cube_f64* c) {
+    SPC_REQUIRE(c->nz < (1LL << 21), "nz too large for the float64 moment kernel (%lld)", (long long)c->nz);
+    return SPC_OK;
+}
+
+// ---- "is this voxel included": the mask as the operators with a fill value see it -----------------------------
+// A two-width operator embeds one SpcInclude<T> in its kernel arguments, fills it with spc_include_from and asks
+// spc_include for every sample it loads (mb = the sample's byte of the mask array, 1 without one).
+template <typename T>
+struct SpcInclude {
+    const uint8_t* marr;                  // mask array term, or nullptr
+    int64_t mrs, mps;
+    T lim, lo, hi;                        // predicate terms in canonical form (spc_canonical_pred)
+    int pred;                             // any predicate flag set: otherwise a NaN sample is included (array term only)
+    int nan_excluded;                     // a NaN sample is excluded whatever the terms say (a ~isnan mask of the cube's data)
+};
+
+template <typename T>
+__device__ __forceinline__ bool spc_include(const SpcInclude<T>& I, T v, uint8_t mb) {
+    const bool p = (spc_abs(v) <= I.lim) & !(v <= I.lo) & !(v >= I.hi);
+    return (mb != 0) & (!I.pred | p) & (!I.nan_excluded | (v == v));
+}
+
+template <typename T>
+static inline int spc_include_from(const typename SpcAbi<T>::mask* mask, const typename SpcAbi<T>::cube* cube, int nan_excluded,
+                                   SpcInclude<T>* out) {
+    SpcMaskDev<T> M;
+    const int rc = spc_mask_to_dev(mask, cube, &M);
+    if (rc) return rc;
+    out->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
+    out->mrs = M.row_stride; out->mps = M.plane_stride;
+    out->lim = M.lim; out->lo = M.lo; out->hi = M.hi;
+    out->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
+    out->nan_excluded = nan_excluded != 0;
     return SPC_OK;
 }
 
@@ -195,8 +266,9 @@ __device__ __forceinline__ auto spc_plane_srd(const void* base) {
 
 // predicate part of the mask AND "not NaN", in the canonical form: three compares and no flag tests (spc_pred below costs five
 // flag-guarded compares and ~11 scalar instructions per sample whatever the mask: round 4 found the reductions bound by that)
-__device__ __forceinline__ bool spc_pred_valid(const MaskDev& m, float v) {
-    return (fabsf(v) <= m.lim) & !(v <= m.lo) & !(v >= m.hi);
+template <typename T>
+__device__ __forceinline__ bool spc_pred_valid(const SpcMaskDev<T>& m, T v) {
+    return (spc_abs(v) <= m.lim) & !(v <= m.lo) & !(v >= m.hi);
 }
 
 // predicate part of the mask (array part is handled by the caller's loads); a NaN sample passes unless isfinite is asked for

@@ -7,7 +7,7 @@
 // Axis 2: the runs lie along the contiguous axis.  A block stages a row tile (whole runs, 16-byte loads) in LDS, filled
 // and with its include bytes, and a thread reduces one run from there; runs too long for a tile (factor > 512) get a
 // block each, reduced across the block.
-#include "spc_wide.h"
+#include "spc_common.h"
 
 namespace {
 
@@ -16,17 +16,11 @@ constexpr int DS_BLOCK = 256;
 constexpr int DS_TILE = 2048;             // samples of a row tile in LDS (axis 2)
 constexpr int DS_TILE_MAX_FACTOR = DS_TILE / 4;
 
-__host__ __device__ __forceinline__ int64_t ds_min(int64_t a, int64_t b) { return a < b ? a : b; }
-
 template <typename T>
 struct DsArgs {
     const T* in;
     int64_t nz, ny, nx, rs, ps;           // input view, strides in elements
-    const uint8_t* marr;                  // mask array term, or nullptr
-    int64_t mrs, mps;
-    T lim, lo, hi;                        // predicate terms in canonical form (spc_canonical_pred / canonical64)
-    int pred;                             // any predicate flag set: otherwise a NaN sample is included (array term only)
-    int nan_excluded;                     // a NaN sample is excluded whatever the terms say (a ~isnan mask of the cube's data)
+    SpcInclude<T> m;                      // which samples count; the others enter as fill
     T fill;
     int64_t f, n_ax;                      // factor, input length along the axis
     int64_t nzo, nyo, nxo;                // output shape
@@ -35,15 +29,6 @@ struct DsArgs {
     int64_t ors, ops;                     // output strides (elements), shared by out and omask
     int nan_skip, mean;                   // estimator: skip NaN samples (nan*), divide by the count (mean)
 };
-
-__device__ __forceinline__ float ds_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double ds_abs(double v) { return fabs(v); }
-
-template <typename T>
-__device__ __forceinline__ bool ds_include(const DsArgs<T>& A, T v, uint8_t mb) {
-    const bool p = (ds_abs(v) <= A.lim) & !(v <= A.lo) & !(v >= A.hi);
-    return (mb != 0) & (!A.pred | p) & (!A.nan_excluded | (v == v));
-}
 
 template <typename T, int KIND>
 struct Acc {
@@ -157,15 +142,15 @@ template <typename T, int KIND, bool VEC>
 __global__ __launch_bounds__(DS_BLOCK) void ds_axis01_kernel(const DsArgs<T> A, int axis) {
     const int64_t x0 = ((int64_t)blockIdx.x * DS_BLOCK + threadIdx.x) * 4;
     if (x0 >= A.nx) return;
-    const int nv = (int)ds_min(4, A.nx - x0);
+    const int nv = (int)spc_min64(4, A.nx - x0);
     const int64_t a = blockIdx.y;
     const int64_t nb = axis == 0 ? A.nzo : A.nz;
-    const int64_t step = axis == 0 ? A.ps : A.rs, mstep = axis == 0 ? A.mps : A.mrs;
+    const int64_t step = axis == 0 ? A.ps : A.rs, mstep = axis == 0 ? A.m.mps : A.m.mrs;
     for (int64_t b = blockIdx.z; b < nb; b += gridDim.z) {
         const int64_t z0 = axis == 0 ? b * A.f : b, y0 = axis == 0 ? a : a * A.f;
-        const int64_t cnt = ds_min(A.f, A.n_ax - (axis == 0 ? z0 : y0));       // real samples of the run
+        const int64_t cnt = spc_min64(A.f, A.n_ax - (axis == 0 ? z0 : y0));       // real samples of the run
         const T* p = A.in + z0 * A.ps + y0 * A.rs + x0;
-        const uint8_t* mp = A.marr ? A.marr + z0 * A.mps + y0 * A.mrs + x0 : nullptr;
+        const uint8_t* mp = A.m.marr ? A.m.marr + z0 * A.m.mps + y0 * A.m.mrs + x0 : nullptr;
         Acc<T, KIND> acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j].init();
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis01_kernel(const DsArgs<T> A, 
             loadm4<VEC>(mp ? mp + k * mstep : nullptr, nv, mb);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool inc = ds_include(A, v[j], mb[j]);
+                const bool inc = spc_include(A.m, v[j], mb[j]);
                 acc[j].any |= inc;
                 acc[j].add(inc ? v[j] : A.fill);
             }
@@ -204,12 +189,12 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis2_tile_kernel(const DsArgs<T>
     const int f = (int)A.f;
     const int64_t y = blockIdx.y;
     const int64_t xo0 = (int64_t)blockIdx.x * nout_tile;
-    const int nout = (int)ds_min(nout_tile, A.nxo - xo0);
+    const int nout = (int)spc_min64(nout_tile, A.nxo - xo0);
     const int64_t xs = xo0 * f;
-    const int span = (int)(ds_min(A.nx, (xo0 + nout) * f) - xs);           // real samples of the tile
+    const int span = (int)(spc_min64(A.nx, (xo0 + nout) * f) - xs);           // real samples of the tile
     for (int64_t z = blockIdx.z; z < A.nz; z += gridDim.z) {
         const T* p = A.in + z * A.ps + y * A.rs + xs;
-        const uint8_t* mp = A.marr ? A.marr + z * A.mps + y * A.mrs + xs : nullptr;
+        const uint8_t* mp = A.m.marr ? A.m.marr + z * A.m.mps + y * A.m.mrs + xs : nullptr;
         for (int i = threadIdx.x * 4; i < span; i += DS_BLOCK * 4) {
             const int nv = span - i < 4 ? span - i : 4;
             T v[4];
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis2_tile_kernel(const DsArgs<T>
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j < nv) {
-                    const bool inc = ds_include(A, v[j], mb[j]);
+                    const bool inc = spc_include(A.m, v[j], mb[j]);
                     sv[i + j] = inc ? v[j] : A.fill;
                     sm[i + j] = inc ? 1 : 0;
                 }
@@ -256,15 +241,15 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis2_run_kernel(const DsArgs<T> 
     __shared__ uint8_t sfl[DS_BLOCK];
     const int64_t xo = blockIdx.x, y = blockIdx.y;
     const int64_t xs = xo * A.f;
-    const int64_t span = ds_min(A.nx, xs + A.f) - xs;
+    const int64_t span = spc_min64(A.nx, xs + A.f) - xs;
     const int tid = threadIdx.x;
     for (int64_t z = blockIdx.z; z < A.nz; z += gridDim.z) {
         const T* p = A.in + z * A.ps + y * A.rs + xs;
-        const uint8_t* mp = A.marr ? A.marr + z * A.mps + y * A.mrs + xs : nullptr;
+        const uint8_t* mp = A.m.marr ? A.m.marr + z * A.m.mps + y * A.m.mrs + xs : nullptr;
         Acc<T, KIND> acc;
         acc.init();
         for (int64_t i = (int64_t)tid * 4; i < span; i += DS_BLOCK * 4) {
-            const int nv = (int)ds_min(4, span - i);
+            const int nv = (int)spc_min64(4, span - i);
             T v[4];
             uint8_t mb[4];
             load4<VEC>(p + i, nv, v);
@@ -272,7 +257,7 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis2_run_kernel(const DsArgs<T> 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j < nv) {
-                    const bool inc = ds_include(A, v[j], mb[j]);
+                    const bool inc = spc_include(A.m, v[j], mb[j]);
                     acc.any |= inc;
                     acc.add(inc ? v[j] : A.fill);
                 }
@@ -302,11 +287,9 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_axis2_run_kernel(const DsArgs<T> 
     }
 }
 
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 template <typename T, int KIND, bool VEC>
 void ds_launch_kind(const DsArgs<T>& A, int axis, hipStream_t st) {
-    const unsigned gz = (unsigned)ds_min(axis == 0 ? A.nzo : A.nz, 65535);
+    const unsigned gz = (unsigned)spc_min64(axis == 0 ? A.nzo : A.nz, 65535);
     if (axis < 2) {
         const int64_t lanes = (A.nx + 3) / 4;
         dim3 grid((unsigned)((lanes + DS_BLOCK - 1) / DS_BLOCK), (unsigned)(axis == 0 ? A.ny : A.nyo), gz);
@@ -361,11 +344,11 @@ int ds_setup(DsArgs<T>& A, int axis, int64_t factor, int truncate, int estimator
 template <typename T>
 bool ds_vec_ok(const DsArgs<T>& A, int axis) {
     const size_t e = sizeof(T);
-    bool ok = aligned(A.in, 16) && (A.rs * e) % 16 == 0 && (A.ps * e) % 16 == 0;
-    if (A.marr) ok = ok && aligned(A.marr, 4) && A.mrs % 4 == 0 && A.mps % 4 == 0;
+    bool ok = spc_aligned(A.in, 16) && (A.rs * e) % 16 == 0 && (A.ps * e) % 16 == 0;
+    if (A.m.marr) ok = ok && spc_aligned(A.m.marr, 4) && A.m.mrs % 4 == 0 && A.m.mps % 4 == 0;
     if (axis < 2) {
-        ok = ok && aligned(A.out, 16) && A.ors % 4 == 0 && A.ops % 4 == 0 && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
-        if (A.omask) ok = ok && aligned(A.omask, 4);
+        ok = ok && spc_aligned(A.out, 16) && A.ors % 4 == 0 && A.ops % 4 == 0 && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
+        if (A.omask) ok = ok && spc_aligned(A.omask, 4);
     }
     if (axis == 2 && A.f > DS_TILE_MAX_FACTOR) ok = ok && A.f % 4 == 0;
     return ok;
@@ -380,15 +363,15 @@ int ds_run(int device, void* stream, const DsArgs<T>& A, int axis, int estimator
     const int64_t rows = axis == 1 ? A.nyo : A.ny;   // blockIdx.y: output rows along y, input rows otherwise
     for (int64_t r0 = 0; r0 < rows; r0 += 65535) {   // slabs of at most 65535 rows (gridDim.y)
         DsArgs<T> S = A;
-        const int64_t n = ds_min(65535, rows - r0), in_r0 = axis == 1 ? r0 * A.f : r0;
+        const int64_t n = spc_min64(65535, rows - r0), in_r0 = axis == 1 ? r0 * A.f : r0;
         S.in = A.in + in_r0 * A.rs;
-        if (S.marr) S.marr = A.marr + in_r0 * A.mrs;
+        if (S.m.marr) S.m.marr = A.m.marr + in_r0 * A.m.mrs;
         S.out = A.out + r0 * A.ors;
         if (S.omask) S.omask = A.omask + r0 * A.ors;
         if (axis == 1) {
             S.n_ax = A.n_ax - in_r0;
             S.nyo = n;
-            S.ny = ds_min(S.n_ax, n * A.f);
+            S.ny = spc_min64(S.n_ax, n * A.f);
         } else {
             S.ny = S.nyo = n;
         }
@@ -399,6 +382,27 @@ int ds_run(int device, void* stream, const DsArgs<T>& A, int axis, int estimator
     return SPC_OK;
 }
 
+template <typename T>
+int ds_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded,
+             T fill, int axis, int64_t factor, int truncate, int estimator, T* d_out, int64_t out_row_stride,
+             int64_t out_plane_stride, uint8_t* d_out_mask) {
+    int rc = spc_check_cube(cube);
+    if (rc) return rc;
+    if constexpr (sizeof(T) == 8) {                  // inherited from the float64 moment kernel's cube check; nothing here needs it
+        rc = spc_check_nz_f64(cube);
+        if (rc) return rc;
+    }
+    DsArgs<T> A{};
+    rc = spc_include_from(mask, cube, nan_excluded, &A.m);
+    if (rc) return rc;
+    A.in = cube->d_data; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
+    A.rs = cube->row_stride; A.ps = cube->plane_stride;
+    A.fill = fill;
+    rc = ds_setup(A, axis, factor, truncate, estimator, d_out, out_row_stride, out_plane_stride, d_out_mask);
+    if (rc) return rc;
+    return ds_run(device, stream, A, axis, estimator);
+}
+
 }  // namespace
 
 extern "C" {
@@ -406,45 +410,15 @@ extern "C" {
 int spc_downsample_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
                        float fill, int axis, int64_t factor, int truncate, int estimator,
                        float* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask) {
-    int rc = spc_check_cube(cube);
-    if (rc) return rc;
-    MaskDev M;
-    rc = spc_mask_to_dev(mask, cube, &M);
-    if (rc) return rc;
-    DsArgs<float> A{};
-    A.in = cube->d_data; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
-    A.rs = cube->row_stride; A.ps = cube->plane_stride;
-    A.marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A.mrs = M.row_stride; A.mps = M.plane_stride;
-    A.lim = M.lim; A.lo = M.lo; A.hi = M.hi;
-    A.pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A.nan_excluded = nan_excluded != 0;
-    A.fill = fill;
-    rc = ds_setup(A, axis, factor, truncate, estimator, d_out, out_row_stride, out_plane_stride, d_out_mask);
-    if (rc) return rc;
-    return ds_run(device, stream, A, axis, estimator);
+    return ds_entry<float>(device, stream, cube, mask, nan_excluded, fill, axis, factor, truncate, estimator, d_out, out_row_stride,
+                           out_plane_stride, d_out_mask);
 }
 
 int spc_downsample_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                        double fill, int axis, int64_t factor, int truncate, int estimator,
                        double* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask) {
-    int rc = check_cube64(cube);
-    if (rc) return rc;
-    MaskDev64 M;
-    rc = mask64_to_dev(mask, cube, &M);
-    if (rc) return rc;
-    DsArgs<double> A{};
-    A.in = cube->d_data; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
-    A.rs = cube->row_stride; A.ps = cube->plane_stride;
-    A.marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A.mrs = M.row_stride; A.mps = M.plane_stride;
-    A.lim = M.clim; A.lo = M.clo; A.hi = M.chi;
-    A.pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A.nan_excluded = nan_excluded != 0;
-    A.fill = fill;
-    rc = ds_setup(A, axis, factor, truncate, estimator, d_out, out_row_stride, out_plane_stride, d_out_mask);
-    if (rc) return rc;
-    return ds_run(device, stream, A, axis, estimator);
+    return ds_entry<double>(device, stream, cube, mask, nan_excluded, fill, axis, factor, truncate, estimator, d_out, out_row_stride,
+                            out_plane_stride, d_out_mask);
 }
 
 }  // extern "C"

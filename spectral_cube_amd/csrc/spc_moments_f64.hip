@@ -13,7 +13,7 @@
 //
 // HBM-bound (8 B per voxel per pass); eight waves of a block split the channels, their partial sums meet in LDS.
 #include "spc_common.h"
-#include "spc_wide.h"
+#include "spc_common.h"
 
 #include <algorithm>
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kLanes * kZW) void moments_f64_kernel(const Mom64Ar
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             const double val = vget(v, i);
-            bool ok = pred64(A.mask, val);
+            bool ok = spc_pred_valid(A.mask, val);
             if (ARR) ok = ok & (mget(m, i) != 0);
             const double wd = ok ? val : 0.0;
             if (ORDER) {
@@ -215,12 +215,13 @@ extern "C" {
 
 int spc_moments_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, const double* d_cen,
                     double dv, double m1_add, const spc_moment_outputs_f64* out) {
-    int rc = check_cube64(cube);
+    int rc = spc_check_cube(cube);
+    if (!rc) rc = spc_check_nz_f64(cube);
     if (rc) return rc;
     SPC_REQUIRE(out != nullptr, "outputs struct is NULL");
     SPC_REQUIRE(d_cen != nullptr, "d_cen is NULL");
     Mom64Args A{};
-    rc = mask64_to_dev(mask, cube, &A.mask);
+    rc = spc_mask_to_dev(mask, cube, &A.mask);
     if (rc) return rc;
     SPC_DEVICE(device);
     A.cube = cube->d_data;
@@ -235,12 +236,13 @@ int spc_moments_f64(int device, void* stream, const spc_cube_f64* cube, const sp
 
 int spc_moment_order_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, const double* d_cen,
                          int order, const double* d_mu, const double* d_s0, double* d_out, int64_t out_row_stride) {
-    int rc = check_cube64(cube);
+    int rc = spc_check_cube(cube);
+    if (!rc) rc = spc_check_nz_f64(cube);
     if (rc) return rc;
     SPC_REQUIRE(order >= 1 && order <= 64, "order must be in [1,64], got %d", order);
     SPC_REQUIRE(d_cen && d_mu && d_s0 && d_out, "NULL pointer argument");
     Mom64Args A{};
-    rc = mask64_to_dev(mask, cube, &A.mask);
+    rc = spc_mask_to_dev(mask, cube, &A.mask);
     if (rc) return rc;
     SPC_DEVICE(device);
     A.cube = cube->d_data;

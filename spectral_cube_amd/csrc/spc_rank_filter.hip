@@ -17,7 +17,7 @@
 //  * mode "constant" with a mask: the reference leaves a spectrum / plane without one included sample unfiltered
 //    (_apply_spectral_function / _apply_spatial_function, spectral_cube.py:147-172); a second small kernel finds those
 //    and writes them back as fill.  In every other mode the filter of an all-fill ray is all fill anyway.
-#include "spc_wide.h"
+#include "spc_common.h"
 
 namespace {
 
@@ -26,8 +26,6 @@ constexpr int RF_BLOCK = 256;
 constexpr int RF_ZCHUNK = 128;            // outputs per lane and chunk of the network kernel (ksize - 1 halo planes per chunk)
 constexpr int RF_TILE = 32;               // spatial tile edge (outputs)
 constexpr int RF_LDS_BYTES = 64 * 1024;
-
-__host__ __device__ __forceinline__ int64_t rf_min(int64_t a, int64_t b) { return a < b ? a : b; }
 
 // ---- order-preserving keys, NaN last ------------------------------------------------------------------------
 template <typename T> struct Key;
@@ -65,10 +63,7 @@ struct RfArgs {
     typedef typename Key<T>::K K;
     const T* in;
     int64_t nz, ny, nx, rs, ps;           // input view, strides in elements
-    const uint8_t* marr;                  // mask array term, or nullptr
-    int64_t mrs, mps;
-    T lim, lo, hi;                        // predicate terms in canonical form (spc_canonical_pred / canonical64)
-    int pred, nan_excluded;               // as spc_downsample_*
+    SpcInclude<T> m;                      // which samples count; the others enter as fill
     T fill;
     int mode;
     K ckey;                               // key of cval (mode constant)
@@ -77,15 +72,6 @@ struct RfArgs {
     int64_t ors, ops;
     int64_t zchunk, nchunks;              // spectral: outputs per lane and chunk
 };
-
-__device__ __forceinline__ float rf_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double rf_abs(double v) { return fabs(v); }
-
-template <typename T>
-__device__ __forceinline__ bool rf_include(const RfArgs<T>& A, T v, uint8_t mb) {
-    const bool p = (rf_abs(v) <= A.lim) & !(v <= A.lo) & !(v >= A.hi);
-    return (mb != 0) & (!A.pred | p) & (!A.nan_excluded | (v == v));
-}
 
 // scipy's boundary modes (ni_support.c, NI_ExtendLine): index i of an axis of n samples -> the sample it stands for, -1
 // = the constant.  Periodic forms, so any reach is in bounds (the callers refuse more than one axis length anyway).
@@ -109,8 +95,8 @@ __device__ __forceinline__ int64_t rf_map(int64_t i, int64_t n, int mode) {
 template <typename T>
 __device__ __forceinline__ typename Key<T>::K rf_key_at(const RfArgs<T>& A, int64_t z, int64_t y, int64_t x) {
     const T v = A.in[z * A.ps + y * A.rs + x];
-    const uint8_t mb = A.marr ? A.marr[z * A.mps + y * A.mrs + x] : (uint8_t)1;
-    return Key<T>::to(rf_include(A, v, mb) ? v : A.fill);
+    const uint8_t mb = A.m.marr ? A.m.marr[z * A.m.mps + y * A.m.mrs + x] : (uint8_t)1;
+    return Key<T>::to(spc_include(A.m, v, mb) ? v : A.fill);
 }
 
 template <typename K> __device__ __forceinline__ K rf_kmin(K a, K b) { return a < b ? a : b; }
@@ -164,7 +150,7 @@ __device__ __forceinline__ void rf_fetch_row(const RfArgs<T>& A, int64_t z, int6
         return;
     }
     const T* p = A.in + zi * A.ps + y * A.rs + x0;
-    const uint8_t* mp = A.marr ? A.marr + zi * A.mps + y * A.mrs + x0 : nullptr;
+    const uint8_t* mp = A.m.marr ? A.m.marr + zi * A.m.mps + y * A.m.mrs + x0 : nullptr;
     T v[CPL];
     uint8_t mb[CPL];
     if (VEC && nv == CPL) {
@@ -189,7 +175,7 @@ __device__ __forceinline__ void rf_fetch_row(const RfArgs<T>& A, int64_t z, int6
         }
     }
 #pragma unroll
-    for (int j = 0; j < CPL; ++j) k[j] = Key<T>::to(rf_include(A, v[j], mb[j]) ? v[j] : A.fill);
+    for (int j = 0; j < CPL; ++j) k[j] = Key<T>::to(spc_include(A.m, v[j], mb[j]) ? v[j] : A.fill);
 }
 
 template <typename T, int W, bool VEC>
@@ -198,11 +184,11 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_axis0_net_kernel(const RfArgs<T> 
     constexpr int CPL = 16 / (int)sizeof(T);
     const int64_t x0 = ((int64_t)blockIdx.x * RF_BLOCK + threadIdx.x) * CPL;
     if (x0 >= A.nx) return;
-    const int nv = (int)rf_min(CPL, A.nx - x0);
+    const int nv = (int)spc_min64(CPL, A.nx - x0);
     const int64_t y = blockIdx.y;
     constexpr int BACK = W / 2;
     for (int64_t c = blockIdx.z; c < A.nchunks; c += gridDim.z) {
-        const int64_t z0 = c * A.zchunk, z1 = rf_min(A.nz, z0 + A.zchunk);
+        const int64_t z0 = c * A.zchunk, z1 = spc_min64(A.nz, z0 + A.zchunk);
         K ring[W][CPL];                    // ring[j]: window offset j of the current output
 #pragma unroll
         for (int j = 1; j < W; ++j) rf_fetch_row<T, CPL, VEC>(A, z0 - BACK + j - 1, y, x0, nv, ring[j]);
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(NL) void rf_axis0_sorted_kernel(const RfArgs<T> A) 
     const int64_t y = blockIdx.y;
     const int w = A.kz, back = A.kz / 2;
     for (int64_t c = blockIdx.z; c < A.nchunks; c += gridDim.z) {
-        const int64_t z0 = c * A.zchunk, z1 = rf_min(A.nz, z0 + A.zchunk);
+        const int64_t z0 = c * A.zchunk, z1 = spc_min64(A.nz, z0 + A.zchunk);
         for (int j = 0; j < w; ++j) {      // insertion sort of the first window
             const K k = rf_fetch1(A, z0 - back + j, y, x);
             int i = j;
@@ -291,8 +277,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_dead_spectra_kernel(const RfArgs<
     const int64_t y = blockIdx.y;
     for (int64_t z = 0; z < A.nz; ++z) {
         const T v = A.in[z * A.ps + y * A.rs + x];
-        const uint8_t mb = A.marr ? A.marr[z * A.mps + y * A.mrs + x] : (uint8_t)1;
-        if (rf_include(A, v, mb)) return;
+        const uint8_t mb = A.m.marr ? A.m.marr[z * A.m.mps + y * A.m.mrs + x] : (uint8_t)1;
+        if (spc_include(A.m, v, mb)) return;
     }
     for (int64_t z = 0; z < A.nz; ++z) A.out[z * A.ops + y * A.ors + x] = A.fill;
 }
@@ -369,8 +355,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_dead_planes_kernel(const RfArgs<T
             if (e < n) {
                 const int64_t y = e / A.nx, x = e - y * A.nx;
                 const T v = A.in[z * A.ps + y * A.rs + x];
-                const uint8_t mb = A.marr ? A.marr[z * A.mps + y * A.mrs + x] : (uint8_t)1;
-                mine = rf_include(A, v, mb) ? 1 : 0;
+                const uint8_t mb = A.m.marr ? A.m.marr[z * A.m.mps + y * A.m.mrs + x] : (uint8_t)1;
+                mine = spc_include(A.m, v, mb) ? 1 : 0;
             }
             found = __syncthreads_or(mine);
         }
@@ -383,14 +369,12 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_dead_planes_kernel(const RfArgs<T
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-inline bool rf_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 template <typename T>
 bool rf_vec_ok(const RfArgs<T>& A) {
     const size_t e = sizeof(T), cpl = 16 / sizeof(T);
-    bool ok = rf_aligned(A.in, 16) && (A.rs * e) % 16 == 0 && (A.ps * e) % 16 == 0;
-    ok = ok && rf_aligned(A.out, 16) && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
-    if (A.marr) ok = ok && rf_aligned(A.marr, cpl) && A.mrs % cpl == 0 && A.mps % cpl == 0;
+    bool ok = spc_aligned(A.in, 16) && (A.rs * e) % 16 == 0 && (A.ps * e) % 16 == 0;
+    ok = ok && spc_aligned(A.out, 16) && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
+    if (A.m.marr) ok = ok && spc_aligned(A.m.marr, cpl) && A.m.mrs % cpl == 0 && A.m.mps % cpl == 0;
     return ok;
 }
 
@@ -409,7 +393,7 @@ template <typename T>
 RfArgs<T> rf_row_slab(const RfArgs<T>& A, int64_t r0, int64_t n) {
     RfArgs<T> S = A;
     S.in = A.in + r0 * A.rs;
-    if (S.marr) S.marr = A.marr + r0 * A.mrs;
+    if (S.m.marr) S.m.marr = A.m.marr + r0 * A.m.mrs;
     S.out = A.out + r0 * A.ors;
     S.ny = n;
     return S;
@@ -428,10 +412,10 @@ int rf_run_axis0(int device, void* stream, RfArgs<T> A) {
                 SPC_RANK_FILTER_MAX_KSIZE);
     A.zchunk = net ? RF_ZCHUNK : (A.kz * 8 > 256 ? A.kz * 8 : 256);
     A.nchunks = (A.nz + A.zchunk - 1) / A.zchunk;
-    const unsigned gz = (unsigned)rf_min(A.nchunks, 65535);
-    const bool dead = A.mode == RF_CONSTANT && (A.marr || A.pred || A.nan_excluded);
+    const unsigned gz = (unsigned)spc_min64(A.nchunks, 65535);
+    const bool dead = A.mode == RF_CONSTANT && (A.m.marr || A.m.pred || A.m.nan_excluded);
     for (int64_t r0 = 0; r0 < A.ny; r0 += 65535) {
-        const RfArgs<T> S = rf_row_slab(A, r0, rf_min(65535, A.ny - r0));
+        const RfArgs<T> S = rf_row_slab(A, r0, spc_min64(65535, A.ny - r0));
         if (net) {
             const int64_t cpl = 16 / sizeof(T), lanes = (S.nx + cpl - 1) / cpl;
             dim3 grid((unsigned)((lanes + RF_BLOCK - 1) / RF_BLOCK), (unsigned)S.ny, gz);
@@ -460,14 +444,14 @@ int rf_run_plane(int device, void* stream, const RfArgs<T>& A) {
     hipStream_t st = (hipStream_t)stream;
     const int64_t gy = (A.ny + RF_TILE - 1) / RF_TILE, gx = (A.nx + RF_TILE - 1) / RF_TILE;
     SPC_REQUIRE(gy <= 65535 && gx <= 0x7fffffff, "plane of %lld x %lld is too large", (long long)A.ny, (long long)A.nx);
-    dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)rf_min(A.nz, 65535));
+    dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)spc_min64(A.nz, 65535));
     const size_t lds = (size_t)(RF_TILE + A.ky - 1) * (RF_TILE + A.kx - 1) * sizeof(K);
     if (A.ky == 3 && A.kx == 3) hipLaunchKernelGGL((rf_plane_kernel<T, 3, 3>), grid, dim3(RF_BLOCK), lds, st, A);
     else if (A.ky == 5 && A.kx == 5) hipLaunchKernelGGL((rf_plane_kernel<T, 5, 5>), grid, dim3(RF_BLOCK), lds, st, A);
     else hipLaunchKernelGGL((rf_plane_kernel<T, 0, 0>), grid, dim3(RF_BLOCK), lds, st, A);
     SPC_LAUNCH_CHECK();
-    if (A.mode == RF_CONSTANT && (A.marr || A.pred || A.nan_excluded)) {
-        hipLaunchKernelGGL((rf_dead_planes_kernel<T>), dim3((unsigned)rf_min(A.nz, 65535)), dim3(RF_BLOCK), 0, st, A);
+    if (A.mode == RF_CONSTANT && (A.m.marr || A.m.pred || A.m.nan_excluded)) {
+        hipLaunchKernelGGL((rf_dead_planes_kernel<T>), dim3((unsigned)spc_min64(A.nz, 65535)), dim3(RF_BLOCK), 0, st, A);
         SPC_LAUNCH_CHECK();
     }
     return SPC_OK;
@@ -502,39 +486,39 @@ int rf_setup(RfArgs<T>& A, int kz, int ky, int kx, int rank, int mode, T cval, T
     return SPC_OK;
 }
 
-int rf_args32(const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill, RfArgs<float>* A) {
-    int rc = spc_check_cube(cube);
+template <typename T>
+int rf_args(const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded, T fill, RfArgs<T>* A) {
+    int rc = sizeof(T) == 8 ? spc_check_cube_any_order_words(cube) : spc_check_cube(cube);
     if (rc) return rc;
-    MaskDev M;
-    rc = spc_mask_to_dev(mask, cube, &M);
+    rc = spc_include_from(mask, cube, nan_excluded, &A->m);
     if (rc) return rc;
     A->in = cube->d_data; A->nz = cube->nz; A->ny = cube->ny; A->nx = cube->nx;
     A->rs = cube->row_stride; A->ps = cube->plane_stride;
-    A->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A->mrs = M.row_stride; A->mps = M.plane_stride;
-    A->lim = M.lim; A->lo = M.lo; A->hi = M.hi;
-    A->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A->nan_excluded = nan_excluded != 0;
     A->fill = fill;
     return SPC_OK;
 }
 
-int rf_args64(const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill, RfArgs<double>* A) {
-    int rc = check_cube64_any_order(cube);
+template <typename T>
+int rf_axis0_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded,
+                   T fill, int ksize, int rank, int mode, T cval, T* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
+    RfArgs<T> A{};
+    int rc = rf_args<T>(cube, mask, nan_excluded, fill, &A);
     if (rc) return rc;
-    SPC_REQUIRE(cube->plane_stride >= cube->row_stride * (cube->ny - 1) + cube->nx, "plane_stride too small");
-    MaskDev64 M;
-    rc = mask64_to_dev(mask, cube, &M);
+    SPC_REQUIRE(ksize != 0, "ksize must be 1 ... %d (got 0)", SPC_RANK_FILTER_MAX_KSIZE);
+    rc = rf_setup(A, ksize, 0, 0, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
     if (rc) return rc;
-    A->in = cube->d_data; A->nz = cube->nz; A->ny = cube->ny; A->nx = cube->nx;
-    A->rs = cube->row_stride; A->ps = cube->plane_stride;
-    A->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A->mrs = M.row_stride; A->mps = M.plane_stride;
-    A->lim = M.clim; A->lo = M.clo; A->hi = M.chi;
-    A->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A->nan_excluded = nan_excluded != 0;
-    A->fill = fill;
-    return SPC_OK;
+    return rf_run_axis0(device, stream, A);
+}
+
+template <typename T>
+int rf_plane_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded,
+                   T fill, int ky, int kx, int rank, int mode, T cval, T* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
+    RfArgs<T> A{};
+    int rc = rf_args<T>(cube, mask, nan_excluded, fill, &A);
+    if (rc) return rc;
+    rc = rf_setup(A, 0, ky, kx, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
+    if (rc) return rc;
+    return rf_run_plane(device, stream, A);
 }
 
 }  // namespace
@@ -544,47 +528,25 @@ extern "C" {
 int spc_rank_filter_axis0_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
                               float fill, int ksize, int rank, int mode, float cval,
                               float* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
-    RfArgs<float> A{};
-    int rc = rf_args32(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    SPC_REQUIRE(ksize != 0, "ksize must be 1 ... %d (got 0)", SPC_RANK_FILTER_MAX_KSIZE);
-    rc = rf_setup(A, ksize, 0, 0, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
-    if (rc) return rc;
-    return rf_run_axis0(device, stream, A);
+    return rf_axis0_entry<float>(device, stream, cube, mask, nan_excluded, fill, ksize, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
 }
 
 int spc_rank_filter_axis0_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                               double fill, int ksize, int rank, int mode, double cval,
                               double* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
-    RfArgs<double> A{};
-    int rc = rf_args64(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    SPC_REQUIRE(ksize != 0, "ksize must be 1 ... %d (got 0)", SPC_RANK_FILTER_MAX_KSIZE);
-    rc = rf_setup(A, ksize, 0, 0, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
-    if (rc) return rc;
-    return rf_run_axis0(device, stream, A);
+    return rf_axis0_entry<double>(device, stream, cube, mask, nan_excluded, fill, ksize, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
 }
 
 int spc_rank_filter_plane_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
                               float fill, int ky, int kx, int rank, int mode, float cval,
                               float* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
-    RfArgs<float> A{};
-    int rc = rf_args32(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    rc = rf_setup(A, 0, ky, kx, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
-    if (rc) return rc;
-    return rf_run_plane(device, stream, A);
+    return rf_plane_entry<float>(device, stream, cube, mask, nan_excluded, fill, ky, kx, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
 }
 
 int spc_rank_filter_plane_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                               double fill, int ky, int kx, int rank, int mode, double cval,
                               double* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
-    RfArgs<double> A{};
-    int rc = rf_args64(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    rc = rf_setup(A, 0, ky, kx, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
-    if (rc) return rc;
-    return rf_run_plane(device, stream, A);
+    return rf_plane_entry<double>(device, stream, cube, mask, nan_excluded, fill, ky, kx, rank, mode, cval, d_out, out_row_stride, out_plane_stride);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 //  * the fused stack never writes a shifted spectrum: every (block, spaxel slot) owns a row of partial sums and counts
 //    in the workspace, touched by one lane per channel; a second kernel adds the rows in slot order.  No floating-point
 //    atomics, and the split into blocks depends on the sizes alone: two runs agree bit for bit.
-#include "spc_wide.h"
+#include "spc_common.h"
 
 namespace {
 
@@ -33,21 +33,11 @@ constexpr int ST_GMAX = 8;                 // spaxels per block and round
 constexpr size_t ST_LDS_SMALL = 64 * 1024;
 constexpr size_t ST_LDS_MAX = 160 * 1024;
 
-template <typename T> struct StLim;
-template <> struct StLim<float> { static __device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e+38f; } };
-template <> struct StLim<double> { static __device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.7976931348623157e308; } };
-
-__device__ __forceinline__ float st_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double st_abs(double v) { return fabs(v); }
-
 template <typename T>
 struct StArgs {
     const T* in;
     int64_t nz, ny, nx, rs, ps;           // input view, strides in elements
-    const uint8_t* marr;                  // mask array term, or nullptr
-    int64_t mrs, mps;
-    T lim, lo, hi;                        // predicate terms in canonical form
-    int pred, nan_excluded;
+    SpcInclude<T> m;                      // which samples count; the others enter as fill
     T fill;
     const int32_t* idx;                   // npos flat spaxel indices y * nx + x
     const double* shift;                  // npos shifts in channels (NaN: an all-NaN row)
@@ -60,12 +50,6 @@ struct StArgs {
     int G, logG;
     int64_t ngroups, gpb;                 // groups of G positions; groups per block
 };
-
-template <typename T>
-__device__ __forceinline__ bool st_include(const StArgs<T>& A, T v, uint8_t mb) {
-    const bool p = (st_abs(v) <= A.lim) & !(v <= A.lo) & !(v >= A.hi);
-    return (mb != 0) & (!A.pred | p) & (!A.nan_excluded | (v == v));
-}
 
 __global__ __launch_bounds__(ST_BLOCK) void st_table_kernel(double* tab, int M) {
     const int k = blockIdx.x * ST_BLOCK + threadIdx.x;
@@ -141,9 +125,9 @@ __global__ __launch_bounds__(ST_BLOCK) void st_shift_kernel(const StArgs<T> A) {
             uint8_t isb = 0;
             if (z < A.nz && s_y[gi] >= 0) {
                 const T v = A.in[z * A.ps + s_y[gi] * A.rs + s_x[gi]];
-                const uint8_t mb = A.marr ? A.marr[z * A.mps + s_y[gi] * A.mrs + s_x[gi]] : (uint8_t)1;
-                const T f = st_include(A, v, mb) ? v : A.fill;
-                if (StLim<T>::finite(f)) { val = f; s_good[gi] = 1; }        // (every writer stores the same 1)
+                const uint8_t mb = A.m.marr ? A.m.marr[z * A.m.mps + s_y[gi] * A.m.mrs + s_x[gi]] : (uint8_t)1;
+                const T f = spc_include(A.m, v, mb) ? v : A.fill;
+                if (spc_abs(f) <= std::numeric_limits<T>::max()) { val = f; s_good[gi] = 1; }        // (every writer stores the same 1)
                 else { isb = 1; s_bad[gi] = 1; }
             }
             xs[(size_t)gi * nzp + z] = val;
@@ -323,39 +307,20 @@ int st_run(int device, void* stream, StArgs<T> A, const int32_t* d_idx, const do
     return SPC_OK;
 }
 
-int st_args32(const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill, StArgs<float>* A) {
-    int rc = spc_check_cube(cube);
+template <typename T>
+int st_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded, T fill,
+             const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, bool fused, double* d_out, double* d_sum,
+             int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes) {
+    StArgs<T> A{};
+    int rc = sizeof(T) == 8 ? spc_check_cube_any_order_words(cube) : spc_check_cube(cube);
     if (rc) return rc;
-    MaskDev M;
-    rc = spc_mask_to_dev(mask, cube, &M);
+    rc = spc_include_from(mask, cube, nan_excluded, &A.m);
     if (rc) return rc;
-    A->in = cube->d_data; A->nz = cube->nz; A->ny = cube->ny; A->nx = cube->nx;
-    A->rs = cube->row_stride; A->ps = cube->plane_stride;
-    A->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A->mrs = M.row_stride; A->mps = M.plane_stride;
-    A->lim = M.lim; A->lo = M.lo; A->hi = M.hi;
-    A->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A->nan_excluded = nan_excluded != 0;
-    A->fill = fill;
-    return SPC_OK;
-}
-
-int st_args64(const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill, StArgs<double>* A) {
-    int rc = check_cube64_any_order(cube);
-    if (rc) return rc;
-    SPC_REQUIRE(cube->plane_stride >= cube->row_stride * (cube->ny - 1) + cube->nx, "plane_stride too small");
-    MaskDev64 M;
-    rc = mask64_to_dev(mask, cube, &M);
-    if (rc) return rc;
-    A->in = cube->d_data; A->nz = cube->nz; A->ny = cube->ny; A->nx = cube->nx;
-    A->rs = cube->row_stride; A->ps = cube->plane_stride;
-    A->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    A->mrs = M.row_stride; A->mps = M.plane_stride;
-    A->lim = M.clim; A->lo = M.clo; A->hi = M.chi;
-    A->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    A->nan_excluded = nan_excluded != 0;
-    A->fill = fill;
-    return SPC_OK;
+    A.in = cube->d_data; A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
+    A.rs = cube->row_stride; A.ps = cube->plane_stride;
+    A.fill = fill;
+    SPC_REQUIRE(fused || d_out != nullptr, "d_out is NULL");
+    return st_run(device, stream, A, d_idx, d_shift, npos, pad_lo, pad_hi, d_out, d_sum, d_count, d_nan, d_workspace, workspace_bytes);
 }
 
 }  // namespace
@@ -373,41 +338,29 @@ size_t spc_stack_workspace_bytes(int64_t nz, int64_t npos, int pad_lo, int pad_h
 int spc_stack_shift_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
                         const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_out,
                         void* d_workspace, size_t workspace_bytes) {
-    StArgs<float> A{};
-    int rc = st_args32(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    SPC_REQUIRE(d_out != nullptr, "d_out is NULL");
-    return st_run(device, stream, A, d_idx, d_shift, npos, pad_lo, pad_hi, d_out, nullptr, nullptr, nullptr, d_workspace, workspace_bytes);
+    return st_entry<float>(device, stream, cube, mask, nan_excluded, fill, d_idx, d_shift, npos, pad_lo, pad_hi, false, d_out, nullptr, nullptr,
+                        nullptr, d_workspace, workspace_bytes);
 }
 
 int spc_stack_shift_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
                         const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_out,
                         void* d_workspace, size_t workspace_bytes) {
-    StArgs<double> A{};
-    int rc = st_args64(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    SPC_REQUIRE(d_out != nullptr, "d_out is NULL");
-    return st_run(device, stream, A, d_idx, d_shift, npos, pad_lo, pad_hi, d_out, nullptr, nullptr, nullptr, d_workspace, workspace_bytes);
+    return st_entry<double>(device, stream, cube, mask, nan_excluded, fill, d_idx, d_shift, npos, pad_lo, pad_hi, false, d_out, nullptr, nullptr,
+                        nullptr, d_workspace, workspace_bytes);
 }
 
 int spc_stack_sum_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
                       const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_sum,
                       int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes) {
-    StArgs<float> A{};
-    int rc = st_args32(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    return st_run(device, stream, A, d_idx, d_shift, npos, pad_lo, pad_hi, (double*)nullptr, d_sum, d_count, d_nan, d_workspace,
-                  workspace_bytes);
+    return st_entry<float>(device, stream, cube, mask, nan_excluded, fill, d_idx, d_shift, npos, pad_lo, pad_hi, true, nullptr, d_sum, d_count,
+                        d_nan, d_workspace, workspace_bytes);
 }
 
 int spc_stack_sum_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
                       const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_sum,
                       int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes) {
-    StArgs<double> A{};
-    int rc = st_args64(cube, mask, nan_excluded, fill, &A);
-    if (rc) return rc;
-    return st_run(device, stream, A, d_idx, d_shift, npos, pad_lo, pad_hi, (double*)nullptr, d_sum, d_count, d_nan, d_workspace,
-                  workspace_bytes);
+    return st_entry<double>(device, stream, cube, mask, nan_excluded, fill, d_idx, d_shift, npos, pad_lo, pad_hi, true, nullptr, d_sum, d_count,
+                        d_nan, d_workspace, workspace_bytes);
 }
 
 }  // extern "C"

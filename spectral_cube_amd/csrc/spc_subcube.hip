@@ -8,7 +8,7 @@
 // 16-byte store); otherwise a lane owns one sample per row (consecutive lanes = consecutive samples, one load each).
 // Bounding box: every lane keeps the extremes of the (z, y, x) of its included voxels, a wave folds them with
 // cross-lane shuffles, the block's waves meet in LDS, and lane 0 issues one atomicMin / atomicMax per bound.
-#include "spc_wide.h"
+#include "spc_common.h"
 
 namespace {
 
@@ -16,23 +16,13 @@ constexpr int SC_BLOCK = 256;
 constexpr int SC_WAVES = SC_BLOCK / 64;
 constexpr int64_t SC_GRID_LIMIT = 65535;
 
-__host__ __device__ __forceinline__ int64_t sc_min(int64_t a, int64_t b) { return a < b ? a : b; }
 __host__ __device__ __forceinline__ int64_t sc_max(int64_t a, int64_t b) { return a > b ? a : b; }
-
-template <typename T>
-struct ScMask {
-    const uint8_t* marr;                  // mask array term, or nullptr
-    int64_t mrs, mps;
-    T lim, lo, hi;                        // predicate terms in canonical form (spc_canonical_pred / canonical64)
-    int pred;                             // any predicate flag set: otherwise a NaN sample is included (array term only)
-    int nan_excluded;                     // a NaN sample is excluded whatever the terms say
-};
 
 template <typename T>
 struct ScArgs {
     const T* in;                          // parent sample (z0, y0, x0): the start offsets are folded into the pointers
     int64_t sz, sy, sx;                   // element offset between selected planes / rows / samples (step * stride, signed)
-    ScMask<T> m;                          // marr likewise at (z0, y0, x0); mrs / mps already multiplied by the steps
+    SpcInclude<T> m;                          // marr likewise at (z0, y0, x0); mrs / mps already multiplied by the steps
     int64_t msx;
     int64_t nzo, nyo, nxo;
     T* out;
@@ -41,15 +31,6 @@ struct ScArgs {
     int filled;
     T fill;
 };
-
-__device__ __forceinline__ float sc_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double sc_abs(double v) { return fabs(v); }
-
-template <typename T>
-__device__ __forceinline__ bool sc_include(const ScMask<T>& M, T v, uint8_t mb) {
-    const bool p = (sc_abs(v) <= M.lim) & !(v <= M.lo) & !(v >= M.hi);
-    return (mb != 0) & (!M.pred | p) & (!M.nan_excluded | (v == v));
-}
 
 __device__ __forceinline__ void sc_load4(const float* p, float (&v)[4]) {
     const float4 q = *reinterpret_cast<const float4*>(p);
@@ -73,7 +54,7 @@ template <typename T>
 __global__ __launch_bounds__(SC_BLOCK) void sc_gather_vec_kernel(const ScArgs<T> A) {
     const int64_t x = ((int64_t)blockIdx.x * SC_BLOCK + threadIdx.x) * 4;
     if (x >= A.nxo) return;
-    const int nv = (int)sc_min(4, A.nxo - x);
+    const int nv = (int)spc_min64(4, A.nxo - x);
     const int64_t j = blockIdx.y;
     for (int64_t k = blockIdx.z; k < A.nzo; k += gridDim.z) {
         const T* p = A.in + k * A.sz + j * A.sy + x;
@@ -98,7 +79,7 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_gather_vec_kernel(const ScArgs<T>
         uint32_t packed = 0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const bool inc = sc_include(A.m, v[t], mb[t]);
+            const bool inc = spc_include(A.m, v[t], mb[t]);
             packed |= (inc ? 1u : 0u) << (8 * t);
             if (A.filled) v[t] = inc ? v[t] : A.fill;
         }
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_gather_kernel(const ScArgs<T> A) 
     for (int64_t k = blockIdx.z; k < A.nzo; k += gridDim.z) {
         T v = A.in[k * A.sz + j * A.sy + i * A.sx];
         const uint8_t mb = A.m.marr ? A.m.marr[k * A.m.mps + j * A.m.mrs + i * A.msx] : (uint8_t)1;
-        const bool inc = sc_include(A.m, v, mb);
+        const bool inc = spc_include(A.m, v, mb);
         if (A.filled) v = inc ? v : A.fill;
         const int64_t o = k * A.ops + j * A.ors + i;
         A.out[o] = v;
@@ -131,14 +112,12 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_gather_kernel(const ScArgs<T> A) 
     }
 }
 
-inline bool sc_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 // ---- bounding box -------------------------------------------------------------------------------------------------
 template <typename T>
 struct BbArgs {
     const T* in;
     int64_t nz, ny, nx, rs, ps;
-    ScMask<T> m;
+    SpcInclude<T> m;
     long long* box;                       // {zmin, zmax, ymin, ymax, xmin, xmax}
 };
 
@@ -149,7 +128,7 @@ __global__ void bb_init_kernel(long long* box) {
 
 __device__ __forceinline__ int64_t bb_wave_min(int64_t v) {
 #pragma unroll
-    for (int w = 32; w > 0; w >>= 1) v = sc_min(v, (int64_t)__shfl_xor((long long)v, w));
+    for (int w = 32; w > 0; w >>= 1) v = spc_min64(v, (int64_t)__shfl_xor((long long)v, w));
     return v;
 }
 __device__ __forceinline__ int64_t bb_wave_max(int64_t v) {
@@ -169,7 +148,7 @@ __global__ __launch_bounds__(SC_BLOCK) void bb_kernel(const BbArgs<T> A) {
     int64_t zmin = big, zmax = -1, ymin = big, ymax = -1;
     uint32_t hits = 0;                                        // bit t: sample x + t included somewhere
     if (x < A.nx) {
-        const int nv = (int)sc_min(W, A.nx - x);
+        const int nv = (int)spc_min64(W, A.nx - x);
         for (int64_t z = blockIdx.z; z < A.nz; z += gridDim.z) {
             uint32_t hz = 0;
 #pragma unroll 4
@@ -197,17 +176,17 @@ __global__ __launch_bounds__(SC_BLOCK) void bb_kernel(const BbArgs<T> A) {
                 uint32_t h = 0;
 #pragma unroll
                 for (int t = 0; t < W; ++t) {
-                    const bool inc = DATA ? sc_include(A.m, v[t], mb[t]) : (mb[t] != 0);
+                    const bool inc = DATA ? spc_include(A.m, v[t], mb[t]) : (mb[t] != 0);
                     h |= (inc ? 1u : 0u) << t;
                 }
                 if (h) {
-                    ymin = sc_min(ymin, y);
+                    ymin = spc_min64(ymin, y);
                     ymax = sc_max(ymax, y);
                 }
                 hz |= h;
             }
             if (hz) {
-                zmin = sc_min(zmin, z);
+                zmin = spc_min64(zmin, z);
                 zmax = sc_max(zmax, z);
             }
             hits |= hz;
@@ -230,7 +209,7 @@ __global__ __launch_bounds__(SC_BLOCK) void bb_kernel(const BbArgs<T> A) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             int64_t a = sred[q][0];
-            for (int w = 1; w < SC_WAVES; ++w) a = (q & 1) ? sc_max(a, sred[q][w]) : sc_min(a, sred[q][w]);
+            for (int w = 1; w < SC_WAVES; ++w) a = (q & 1) ? sc_max(a, sred[q][w]) : spc_min64(a, sred[q][w]);
             r[q] = a;
         }
         if (r[1] >= 0) {
@@ -244,7 +223,7 @@ __global__ __launch_bounds__(SC_BLOCK) void bb_kernel(const BbArgs<T> A) {
 }
 
 template <typename T>
-int sc_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_t nx, int64_t rs, int64_t ps, ScMask<T> M,
+int sc_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_t nx, int64_t rs, int64_t ps, SpcInclude<T> M,
            const int64_t* start, const int64_t* step, int64_t nzo, int64_t nyo, int64_t nxo, T* d_out, int64_t ors, int64_t ops,
            uint8_t* d_out_mask, int filled, T fill) {
     SPC_REQUIRE(start != nullptr && step != nullptr, "start / step is NULL");
@@ -276,18 +255,18 @@ int sc_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_
     A.out = d_out; A.omask = d_out_mask;
     A.filled = filled != 0; A.fill = fill;
     const size_t e = sizeof(T);
-    bool vec = step[2] == 1 && sc_aligned(A.in, 16) && (A.sz * (int64_t)e) % 16 == 0 && (A.sy * (int64_t)e) % 16 == 0 &&
-               sc_aligned(A.out, 16) && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
-    if (A.m.marr) vec = vec && sc_aligned(A.m.marr, 4) && A.m.mrs % 4 == 0 && A.m.mps % 4 == 0;
-    if (A.omask) vec = vec && sc_aligned(A.omask, 4) && A.ors % 4 == 0 && A.ops % 4 == 0;
+    bool vec = step[2] == 1 && spc_aligned(A.in, 16) && (A.sz * (int64_t)e) % 16 == 0 && (A.sy * (int64_t)e) % 16 == 0 &&
+               spc_aligned(A.out, 16) && (A.ors * e) % 16 == 0 && (A.ops * e) % 16 == 0;
+    if (A.m.marr) vec = vec && spc_aligned(A.m.marr, 4) && A.m.mrs % 4 == 0 && A.m.mps % 4 == 0;
+    if (A.omask) vec = vec && spc_aligned(A.omask, 4) && A.ors % 4 == 0 && A.ops % 4 == 0;
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const unsigned gz = (unsigned)sc_min(nzo, SC_GRID_LIMIT);
+    const unsigned gz = (unsigned)spc_min64(nzo, SC_GRID_LIMIT);
     const int64_t per_block = vec ? 4 * SC_BLOCK : SC_BLOCK;
     const unsigned gx = (unsigned)((nxo + per_block - 1) / per_block);
     for (int64_t j0 = 0; j0 < nyo; j0 += SC_GRID_LIMIT) {      // slabs of at most 65535 output rows (gridDim.y)
         ScArgs<T> S = A;
-        S.nyo = sc_min(SC_GRID_LIMIT, nyo - j0);
+        S.nyo = spc_min64(SC_GRID_LIMIT, nyo - j0);
         S.in = A.in + j0 * A.sy;
         if (S.m.marr) S.m.marr = A.m.marr + j0 * A.m.mrs;
         S.out = A.out + j0 * A.ors;
@@ -301,10 +280,10 @@ int sc_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_
 }
 
 template <typename T>
-int bb_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_t nx, int64_t rs, int64_t ps, ScMask<T> M,
+int bb_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_t nx, int64_t rs, int64_t ps, SpcInclude<T> M,
            int64_t* d_box) {
     SPC_REQUIRE(d_box != nullptr, "d_box is NULL");
-    SPC_REQUIRE(sc_aligned(d_box, 8), "d_box must be 8-byte aligned");
+    SPC_REQUIRE(spc_aligned(d_box, 8), "d_box must be 8-byte aligned");
     BbArgs<T> A{};
     A.in = in; A.nz = nz; A.ny = ny; A.nx = nx; A.rs = rs; A.ps = ps;
     A.m = M;
@@ -312,8 +291,8 @@ int bb_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_
     const bool data = M.pred || M.nan_excluded;
     const size_t e = sizeof(T);
     bool vec = true;
-    if (data) vec = vec && sc_aligned(in, 16) && (rs * e) % 16 == 0 && (ps * e) % 16 == 0;
-    if (M.marr) vec = vec && sc_aligned(M.marr, 4) && M.mrs % 4 == 0 && M.mps % 4 == 0;
+    if (data) vec = vec && spc_aligned(in, 16) && (rs * e) % 16 == 0 && (ps * e) % 16 == 0;
+    if (M.marr) vec = vec && spc_aligned(M.marr, 4) && M.mrs % 4 == 0 && M.mps % 4 == 0;
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(bb_init_kernel, dim3(1), dim3(64), 0, st, A.box);
@@ -321,7 +300,7 @@ int bb_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_
     // about 4096 row-blocks per x tile: every block walks many rows, so the reductions and atomics stay rare
     const int64_t per_block = vec ? 4 * SC_BLOCK : SC_BLOCK;
     const unsigned gx = (unsigned)((nx + per_block - 1) / per_block);
-    const int64_t gz = sc_min(nz, 4096), gy = sc_min(ny, sc_max(1, 4096 / gz));
+    const int64_t gz = spc_min64(nz, 4096), gy = spc_min64(ny, sc_max(1, 4096 / gz));
     dim3 grid(gx, (unsigned)gy, (unsigned)gz);
     if (vec) {
         if (data) hipLaunchKernelGGL((bb_kernel<T, true, true>), grid, dim3(SC_BLOCK), 0, st, A);
@@ -334,39 +313,28 @@ int bb_run(int device, void* stream, const T* in, int64_t nz, int64_t ny, int64_
     return SPC_OK;
 }
 
-// the checks of spc_check_cube / check_cube64 without the float64 moment kernel's nz bound (nothing here depends on it)
-template <typename C>
-int sc_check_cube(const C* c) {
-    SPC_REQUIRE(c != nullptr && c->d_data != nullptr, "cube pointer is NULL");
-    SPC_REQUIRE(c->nz > 0 && c->ny > 0 && c->nx > 0, "cube shape must be positive (got %lld,%lld,%lld)",
-                (long long)c->nz, (long long)c->ny, (long long)c->nx);
-    SPC_REQUIRE(c->row_stride >= c->nx, "row_stride %lld < nx %lld", (long long)c->row_stride, (long long)c->nx);
-    SPC_REQUIRE(c->plane_stride >= c->row_stride * (c->ny - 1) + c->nx, "plane_stride too small");
-    return SPC_OK;
+template <typename T>
+int sc_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded,
+             const int64_t* start, const int64_t* step, int64_t nz_out, int64_t ny_out, int64_t nx_out, T* d_out,
+             int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask, int filled, T fill) {
+    int rc = spc_check_cube(cube);
+    if (rc) return rc;
+    SpcInclude<T> M;
+    rc = spc_include_from(mask, cube, nan_excluded, &M);
+    if (rc) return rc;
+    return sc_run<T>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M,
+                     start, step, nz_out, ny_out, nx_out, d_out, out_row_stride, out_plane_stride, d_out_mask, filled, fill);
 }
 
-int sc_mask32(const spc_mask* mask, const spc_cube_f32* cube, int nan_excluded, ScMask<float>* out) {
-    MaskDev M;
-    const int rc = spc_mask_to_dev(mask, cube, &M);
+template <typename T>
+int bb_entry(int device, void* stream, const typename SpcAbi<T>::cube* cube, const typename SpcAbi<T>::mask* mask, int nan_excluded,
+             int64_t* d_box) {
+    int rc = spc_check_cube(cube);
     if (rc) return rc;
-    out->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    out->mrs = M.row_stride; out->mps = M.plane_stride;
-    out->lim = M.lim; out->lo = M.lo; out->hi = M.hi;
-    out->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    out->nan_excluded = nan_excluded != 0;
-    return SPC_OK;
-}
-
-int sc_mask64(const spc_mask_f64* mask, const spc_cube_f64* cube, int nan_excluded, ScMask<double>* out) {
-    MaskDev64 M;
-    const int rc = mask64_to_dev(mask, cube, &M);
+    SpcInclude<T> M;
+    rc = spc_include_from(mask, cube, nan_excluded, &M);
     if (rc) return rc;
-    out->marr = (M.flags & SPC_MASK_ARRAY) ? M.arr : nullptr;
-    out->mrs = M.row_stride; out->mps = M.plane_stride;
-    out->lim = M.clim; out->lo = M.clo; out->hi = M.chi;
-    out->pred = (M.flags & ~SPC_MASK_ARRAY) != 0;
-    out->nan_excluded = nan_excluded != 0;
-    return SPC_OK;
+    return bb_run<T>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M, d_box);
 }
 
 }  // namespace
@@ -377,46 +345,26 @@ int spc_subcube_f32(int device, void* stream, const spc_cube_f32* cube, const sp
                     const int64_t* start, const int64_t* step, int64_t nz_out, int64_t ny_out, int64_t nx_out,
                     float* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask,
                     int filled, float fill) {
-    int rc = sc_check_cube(cube);
-    if (rc) return rc;
-    ScMask<float> M;
-    rc = sc_mask32(mask, cube, nan_excluded, &M);
-    if (rc) return rc;
-    return sc_run<float>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M,
-                         start, step, nz_out, ny_out, nx_out, d_out, out_row_stride, out_plane_stride, d_out_mask, filled, fill);
+    return sc_entry<float>(device, stream, cube, mask, nan_excluded, start, step, nz_out, ny_out, nx_out, d_out, out_row_stride,
+                           out_plane_stride, d_out_mask, filled, fill);
 }
 
 int spc_subcube_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                     const int64_t* start, const int64_t* step, int64_t nz_out, int64_t ny_out, int64_t nx_out,
                     double* d_out, int64_t out_row_stride, int64_t out_plane_stride, uint8_t* d_out_mask,
                     int filled, double fill) {
-    int rc = sc_check_cube(cube);
-    if (rc) return rc;
-    ScMask<double> M;
-    rc = sc_mask64(mask, cube, nan_excluded, &M);
-    if (rc) return rc;
-    return sc_run<double>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M,
-                          start, step, nz_out, ny_out, nx_out, d_out, out_row_stride, out_plane_stride, d_out_mask, filled, fill);
+    return sc_entry<double>(device, stream, cube, mask, nan_excluded, start, step, nz_out, ny_out, nx_out, d_out, out_row_stride,
+                            out_plane_stride, d_out_mask, filled, fill);
 }
 
 int spc_mask_bbox_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded,
                       int64_t* d_box) {
-    int rc = sc_check_cube(cube);
-    if (rc) return rc;
-    ScMask<float> M;
-    rc = sc_mask32(mask, cube, nan_excluded, &M);
-    if (rc) return rc;
-    return bb_run<float>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M, d_box);
+    return bb_entry<float>(device, stream, cube, mask, nan_excluded, d_box);
 }
 
 int spc_mask_bbox_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                       int64_t* d_box) {
-    int rc = sc_check_cube(cube);
-    if (rc) return rc;
-    ScMask<double> M;
-    rc = sc_mask64(mask, cube, nan_excluded, &M);
-    if (rc) return rc;
-    return bb_run<double>(device, stream, cube->d_data, cube->nz, cube->ny, cube->nx, cube->row_stride, cube->plane_stride, M, d_box);
+    return bb_entry<double>(device, stream, cube, mask, nan_excluded, d_box);
 }
 
 }  // extern "C"

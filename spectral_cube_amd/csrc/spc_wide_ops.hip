@@ -11,7 +11,7 @@
 // They are plain HBM streams (lanes along x) and NOT tuned like the float32 stencils: float64 cubes are outside
 // BASELINE.json's configurations; what matters here is that a float64 cube gives the reference's float64 values.
 #include "spc_common.h"
-#include "spc_wide.h"
+#include "spc_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,7 +29,7 @@ struct Cube64 {
 
 __device__ __forceinline__ bool inc64(const Cube64& c, const MaskDev64& m, int64_t z, int64_t y, int64_t x, double& v) {
     v = c.p[z * c.plane_stride + y * c.row_stride + x];
-    bool ok = pred64(m, v);
+    bool ok = spc_pred_valid(m, v);
     if (m.flags & SPC_MASK_ARRAY) ok = ok && m.arr[z * m.plane_stride + y * m.row_stride + x] != 0;
     return ok;
 }
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void stats64_global_kernel(const Cube64 C, con
                 const bool in = x0 + (int64_t)q * blockDim.x * VEC < C.nx;      // (VEC = 2: nx is even, both samples or neither)
 #pragma unroll
                 for (int e = 0; e < VEC; ++e)
-                    if (in && pred64(M, vv[q][e]) && ((mk[q] >> (8 * e)) & 0xffu) != 0u) rec_add(r, vv[q][e]);
+                    if (in && spc_pred_valid(M, vv[q][e]) && ((mk[q] >> (8 * e)) & 0xffu) != 0u) rec_add(r, vv[q][e]);
             }
         }
     }
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void stats64_march_kernel(const Cube64 C, cons
         }
 #pragma unroll
         for (int q = 0; q < kIn; ++q)
-            if (k0 + q < n && pred64(M, vv[q]) && mk[q] != 0u) rec_add(r, vv[q]);
+            if (k0 + q < n && spc_pred_valid(M, vv[q]) && mk[q] != 0u) rec_add(r, vv[q]);
     }
     stat_store(O, g, r);
 }
@@ -215,7 +215,7 @@ __device__ __forceinline__ void spectral_conv64_run(const Conv64Args& A, int64_t
                 const int64_t i = i0 + c0 + q;
                 if (c0 + q < nin) {                                 // (uniform)
                     const bool inr = i >= 0 && i < A.c.nz;          // (uniform) outside the cube: a valid zero
-                    const bool ok = pred64(A.m, vv[q]) && mk[q] != 0u;
+                    const bool ok = spc_pred_valid(A.m, vv[q]) && mk[q] != 0u;
                     const double v = (inr && ok) ? vv[q] : 0.0, w = inr ? (ok ? 1.0 : 0.0) : 1.0;
                     inf_seen = inf_seen || (fabs(v) == INFINITY);
                     const double* kp = A.kpad + 15 + (o0 - i + H);  // kp[u] = kern[(o0 + u) - i + H], or a padding zero
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void spectral64_ring_kernel(const SRing64Ar
         constexpr int S = decltype(slot)::value, Q = S % U;
         const double v0 = vq[S];
         const bool inr = i >= 0 && i < nz;                   // (uniform) outside the cube: a valid zero
-        const bool ok = pred64(A.m, v0) && mq[S] != 0u;
+        const bool ok = spc_pred_valid(A.m, v0) && mq[S] != 0u;
         const double v = (inr && ok) ? v0 : 0.0, w = inr ? (ok ? 1.0 : 0.0) : 1.0;
         if (A.flag) seen_inf = seen_inf || fabs(v) == INFINITY;
         ask(std::integral_constant<int, (S + kPre) % NQ>{}, i + kPre);
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_kernel(const Sp64Args A) 
                 const double kw = A.kx[A.nkx - 1 - j];           // flipped kernel, input x - H + j
                 const int64_t i = x - H + j;
                 const bool inr = i >= 0 && i < A.c.nx;
-                const bool ok = pred64(A.m, vv[q]) && mk[q] != 0u;
+                const bool ok = spc_pred_valid(A.m, vv[q]) && mk[q] != 0u;
                 const double v = (inr && ok) ? vv[q] : 0.0, w = inr ? (ok ? 1.0 : 0.0) : 1.0;
                 if (kw != 0.0) { num = fma(kw, v, num); den = fma(kw, w, den); }
             }
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds_kernel(const Sp64Args
     for (int e = t; e < 256 + 2 * H; e += 256) {
         const int64_t i = x0 - H + e, ic = min(max(i, (int64_t)0), A.c.nx - 1);
         const double v = pd[ic];
-        const bool inr = i >= 0 && i < A.c.nx, ok = pred64(A.m, v) && (!arr || pmk[ic] != 0);
+        const bool inr = i >= 0 && i < A.c.nx, ok = spc_pred_valid(A.m, v) && (!arr || pmk[ic] != 0);
         sv[e] = (inr && ok) ? v : 0.0;
         sw[e] = inr ? (ok ? 1.f : 0.f) : 1.f;                    // outside the image: a valid zero
     }
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds4_kernel(const Sp64Arg
     for (int e = t; e < kSpX4Out + 2 * H + 3; e += 256) {
         const int64_t i = x0 - H + e, ic = min(max(i, (int64_t)0), A.c.nx - 1);
         const double v = pd[ic];
-        const bool inr = i >= 0 && i < A.c.nx, ok = pred64(A.m, v) && (!arr || pmk[ic] != 0);
+        const bool inr = i >= 0 && i < A.c.nx, ok = spc_pred_valid(A.m, v) && (!arr || pmk[ic] != 0);
         sv[sp64_skew(e)] = (inr && ok) ? v : 0.0;
         sw[sp64_skew(e)] = inr ? (ok ? 1.f : 0.f) : 1.f;         // outside the image: a valid zero
     }
@@ -703,12 +703,12 @@ __global__ __launch_bounds__(256, 2) void spatial64_ring_kernel(const Ring64Args
         const unsigned m0 = mq0[Q], m1 = mq1[Q];
         f64x2* const Bw = buf[Q & 1];                        // (U is even: the buffer is the phase's parity)
         {
-            const bool ok = pred64(A.m, r0) && m0 != 0u;
+            const bool ok = spc_pred_valid(A.m, r0) && m0 != 0u;
             Bw[t] = (in0 && row_in) ? (ok ? f64x2{r0, 1.0} : f64x2{0.0, 0.0}) : f64x2{0.0, 1.0};      // outside the image: a valid zero
             if (A.flag) seen_inf = seen_inf || (ok && in0 && row_in && fabs(r0) == INFINITY);
         }
         if (wave0 && second) {                              // (a scalar branch for three of the four waves)
-            const bool ok = pred64(A.m, r1) && m1 != 0u;
+            const bool ok = spc_pred_valid(A.m, r1) && m1 != 0u;
             Bw[W + t] = (in1 && row_in) ? (ok ? f64x2{r1, 1.0} : f64x2{0.0, 0.0}) : f64x2{0.0, 1.0};
             if (A.flag) seen_inf = seen_inf || (ok && in1 && row_in && fabs(r1) == INFINITY);
         }
@@ -953,7 +953,7 @@ __global__ __launch_bounds__(256) void sort64_kernel(const Sort64Args A) {
                 const int z = z0 + q * L;
                 if (z < NZP) {
                     double v = vv[q];
-                    bool ok = col_in && z < A.c.nz && pred64(A.m, v) && mk[q] != 0u;
+                    bool ok = col_in && z < A.c.nz && spc_pred_valid(A.m, v) && mk[q] != 0u;
                     if (A.center) { v = fabs(v - cen); ok = ok && (v == v); }
                     keys[z * TS + r] = ok ? fkey64(v) : kExcl;
                 }
@@ -1090,7 +1090,7 @@ __global__ __launch_bounds__(256) void select64_kernel(const Sort64Args A) {
                 const int z = z0 + q * L;
                 if (z < NZP) {
                     double v = vv[q];
-                    bool ok = col_in && z < A.c.nz && pred64(A.m, v) && mk[q] != 0u;
+                    bool ok = col_in && z < A.c.nz && spc_pred_valid(A.m, v) && mk[q] != 0u;
                     if (A.center) { v = fabs(v - cen); ok = ok && (v == v); }
                     keys[z * TS + r] = ok ? fkey64(v) : kExcl;
                 }
@@ -1238,7 +1238,7 @@ __device__ __forceinline__ void row_load_keys(const Sort64Args& A, int64_t y, in
         for (int q = 0; q < CH; ++q) {
             const int i = i0 + q;
             double v = vv[q];
-            bool ok = col_in && (sl + LPR * i) < A.c.nz && pred64(A.m, v) && mk[q] != 0u;
+            bool ok = col_in && (sl + LPR * i) < A.c.nz && spc_pred_valid(A.m, v) && mk[q] != 0u;
             if (A.center) { v = fabs(v - cen); ok = ok && (v == v); }
             const unsigned long long k = ok ? fkey64(v) : kExcl;
             khi[i] = (unsigned)(k >> 32); klo[i] = (unsigned)k;
@@ -1576,9 +1576,10 @@ static int check_kernel_sum(const double* k, size_t n) {
 }
 
 static int cube64_args(const spc_cube_f64* cube, const spc_mask_f64* mask, Cube64* C, MaskDev64* M, bool any_order = false) {
-    int rc = any_order ? check_cube64_any_order(cube) : check_cube64(cube);
+    int rc = any_order ? spc_check_cube_any_order(cube) : spc_check_cube(cube);
+    if (!rc && !any_order) rc = spc_check_nz_f64(cube);
     if (rc) return rc;
-    rc = mask64_to_dev(mask, cube, M);
+    rc = spc_mask_to_dev(mask, cube, M);
     if (rc) return rc;
     C->p = cube->d_data; C->nz = cube->nz; C->ny = cube->ny; C->nx = cube->nx;
     C->row_stride = cube->row_stride; C->plane_stride = cube->plane_stride;
