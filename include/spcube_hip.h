@@ -507,6 +507,34 @@ int spc_stack_sum_f64(int device, void* stream, const spc_cube_f64* cube, const 
                       const int32_t* d_idx, const double* d_shift, int64_t npos, int pad_lo, int pad_hi, double* d_sum,
                       int64_t* d_count, int64_t* d_nan, void* d_workspace, size_t workspace_bytes);
 
+/* ---- stack_cube: the slabs of many lines of one cube, interpolated onto one velocity grid and averaged ----
+ * spectral_cube.analysis_utilities: stack_cube (analysis_utilities.py:321-432): spectral_slab per line (spectral_cube.py:
+ * 1823-1879), the first surviving slab as it is (:406-407), every other one through spectral_interpolate onto the first
+ * one's axis (:408-410; the Dask class, dask_spectral_cube.py:1291-1373: NaN outside the slab, NaN where a bracketing
+ * sample is NaN or excluded), then average(cutouts, axis=0) (:412).  One kernel, no cutout written.
+ * Per source s < nsrc and output channel j < n0 the HOST tables (row s, column j; the plan of ops.lerp_plan in absolute
+ * channels of the cube view) give h_lo = the lower bracketing channel, -1 = outside the slab; h_t and h_inv_dx = its weight:
+ * sample = a + (b - a) * (h_inv_dx * h_t), a / b = the samples h_lo and h_lo + 1 with excluded ones NaN (nan_excluded as
+ * for the downsample entry points), a NaN result replaced by fill (the filled data of the interpolated slab).  A source
+ * with h_exact[s] != 0 (the reference slab) contributes the FILLED sample h_lo itself: no arithmetic touches it.
+ * mode: np.nanmean (NaN where no source is finite) / np.mean / np.nansum (0 there) / np.sum (NaN where any source is NaN).
+ * Interpolation and the sum over the sources run in float64 in source order, rounded once at the store; every output
+ * voxel is owned by one lane: no atomics, two runs agree bit for bit.  d_out: (n0, ny, nx), C-contiguous, the cube's type.
+ * The tables are checked before anything is queued: nsrc >= 1, n0 >= 2, every h_lo -1 or a channel of the cube whose upper
+ * neighbour exists (SPC_ERR_INVALID); nsrc above SPC_STACK_CUBE_MAX_LINES is SPC_ERR_UNSUPPORTED.  They may be freed when
+ * the call returns (they travel as kernel arguments into d_workspace: spc_stack_cube_workspace_bytes).  No limit on an axis. */
+#define SPC_STACK_CUBE_MAX_LINES 64
+typedef enum {
+    SPC_STACK_CUBE_NANMEAN = 0, SPC_STACK_CUBE_MEAN = 1, SPC_STACK_CUBE_NANSUM = 2, SPC_STACK_CUBE_SUM = 3
+} spc_stack_cube_mode;
+size_t spc_stack_cube_workspace_bytes(int nsrc, int64_t n0);
+int spc_stack_cube_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
+                       int nsrc, const int32_t* h_lo, const double* h_t, const double* h_inv_dx, const int32_t* h_exact, int mode,
+                       int64_t n0, float* d_out, void* d_workspace, size_t workspace_bytes);
+int spc_stack_cube_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
+                       int nsrc, const int32_t* h_lo, const double* h_t, const double* h_inv_dx, const int32_t* h_exact, int mode,
+                       int64_t n0, double* d_out, void* d_workspace, size_t workspace_bytes);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

@@ -19,4 +19,4 @@ from .kernels import (Gaussian1DKernel, Gaussian2DKernel, Box1DKernel, Tophat2DK
                       CustomKernel)
 from .wcs import SimpleWCS  # noqa: F401
 from . import analysis_utilities  # noqa: F401
-from .analysis_utilities import stack_spectra, BadVelocitiesWarning  # noqa: F401
+from .analysis_utilities import stack_spectra, stack_cube, BadVelocitiesWarning  # noqa: F401

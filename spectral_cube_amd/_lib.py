@@ -35,6 +35,9 @@ RANK_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}
 RANK_FILTER_MAX_KSIZE, RANK_FILTER_MAX_KSIZE_SPATIAL = 129, 15
 # the longest padded spectrum of spc_stack_shift_* / spc_stack_sum_*
 STACK_MAX_CHANNELS = 8192
+# the most lines of spc_stack_cube_* and its spc_stack_cube_mode
+STACK_CUBE_MAX_LINES = 64
+STACK_CUBE_MODES = {"nanmean": 0, "mean": 1, "nansum": 2, "sum": 3}
 # spc_mask_program (spc_mask_eval_f32 / _f64): limits, spc_mask_opcode, spc_mask_cmp, spc_mask_elem
 MASK_PROG_MAX_SLOTS, MASK_PROG_MAX_OPERANDS, MASK_PROG_MAX_INSTR, MASK_PROG_MAX_STACK = 4, 8, 16, 8
 MOP_CMP, MOP_FINITE, MOP_LOAD, MOP_NOT, MOP_AND, MOP_OR, MOP_XOR = range(7)
@@ -207,6 +210,9 @@ SIGNATURES = {
     "spc_stack_shift_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz]),
     "spc_stack_sum_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz]),
     "spc_stack_sum_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    "spc_stack_cube_workspace_bytes": (_sz, [_i, _i64]),
+    "spc_stack_cube_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _sz]),
+    "spc_stack_cube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _sz]),
     "spc_moments_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _d, _vp, _vp, _vp]),
     "spc_moment_order_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i, _vp, _vp]),
     "spc_spectral_conv_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _i, _vp, _i64, _i64, _vp, _sz]),

@@ -454,6 +454,41 @@ def stack_sum(cube, idx, shifts, pad=(0, 0), fill=np.nan, mask=None, stream=None
     return total.get(stream), count.get(stream), nnan.get(stream)
 
 
+def stack_cube(cube, lo, t, inv_dx, exact, mode="nanmean", fill=np.nan, mask=None, out=None, stream=None, nan_excluded=False):
+    """(n0, ny, nx) DeviceArray in the cube's dtype: ``average(cutouts, axis=0)`` of stack_cube (analysis_utilities.py:
+    321-432) without a cutout.  Row s of the (S, n0) host tables *lo* / *t* / *inv_dx* is the plan of ``lerp_plan`` for source
+    s in absolute channels of *cube* (-1 = outside the slab): cutout s at output channel j is ``a + (b - a) * inv_dx * t`` of
+    the samples lo and lo + 1 (excluded ones NaN), NaN replaced by *fill*; a source with ``exact[s]`` set is its filled
+    sample lo as it is.  *mode*: nanmean / mean / nansum / sum, numpy's NaN rules, float64 in source order.  More than
+    _lib.STACK_CUBE_MAX_LINES sources raise HipUnsupported before any device work."""
+    name, dtype = _entry("stack_cube", cube)
+    lo = np.ascontiguousarray(lo, dtype=np.int32)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    inv_dx = np.ascontiguousarray(inv_dx, dtype=np.float64)
+    exact = np.ascontiguousarray(exact, dtype=np.int32).ravel()
+    if lo.ndim != 2 or t.shape != lo.shape or inv_dx.shape != lo.shape or exact.size != lo.shape[0]:
+        raise ValueError("lo, t and inv_dx must be (S, n0) tables and exact of length S (got %s, %s, %s, %s)"
+                         % (lo.shape, t.shape, inv_dx.shape, exact.shape))
+    nsrc, n0 = lo.shape
+    if nsrc > _lib.STACK_CUBE_MAX_LINES:
+        raise _lib.HipUnsupported("%d sources are above the built limit of %d (STACK_CUBE_MAX_LINES)" % (nsrc, _lib.STACK_CUBE_MAX_LINES))
+    if mode not in _lib.STACK_CUBE_MODES:
+        raise ValueError("mode must be one of %s (got %r)" % (sorted(_lib.STACK_CUBE_MODES), mode))
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    shape = (n0,) + tuple(cube.shape[1:])
+    if out is None:
+        out = DeviceArray(shape if nsrc >= 1 and 2 <= n0 <= cube.shape[0] else (1, 1, 1), dtype, cube.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype:
+        raise ValueError("preallocated output must be %s %s" % (shape, dtype))
+    ws = DeviceArray((int(_lib.load().spc_stack_cube_workspace_bytes(nsrc, n0)),), np.uint8, cube.device)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill), nsrc,
+              lo.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), inv_dx.ctypes.data_as(C.c_void_p),
+              exact.ctypes.data_as(C.c_void_p), _lib.STACK_CUBE_MODES[mode], n0, C.c_void_p(out.ptr), C.c_void_p(ws.ptr), ws.nbytes)
+    if stream is not None:                   # (the workspace goes back to the pool when this returns)
+        _lib.call("spc_stream_sync", cube.device, _sh(stream))
+    return out
+
+
 def normalize_view(view, shape):
     """(start, step, length) per axis of a tuple of three slices applied to *shape* (``slice.indices``, as numpy indexes)"""
     out = []

@@ -550,7 +550,9 @@ class SimpleWCS:
         out.header = {k: v for k, v in self.header.items() if 3 not in key_axes(k)}
         return out
 
-    def with_spectral(self, crval, cdelt, crpix=1.0, cunit=None):
+    def with_spectral(self, crval, cdelt, crpix=1.0, cunit=None, ctype=None, drop_rest=False):
+        """the same WCS with another linear spectral axis; *ctype*: also another kind of axis (CTYPE3), *drop_rest*: without a
+        rest frequency / wavelength (stack_cube: "no reference frequency", analysis_utilities.py:414-416)"""
         out = copy.deepcopy(self)
         out.crval = out.crval.copy(); out.cdelt = out.cdelt.copy(); out.crpix = out.crpix.copy()
         out.crval[2], out.cdelt[2], out.crpix[2] = crval, cdelt, crpix
@@ -561,6 +563,11 @@ class SimpleWCS:
         out.header.update(CRVAL3=float(crval), CDELT3=float(cdelt), CRPIX3=float(crpix))
         if cunit is not None:
             out.header["CUNIT3"] = cunit
+        if ctype is not None:
+            out.ctype = list(out.ctype); out.ctype[2] = ctype
+            out.header["CTYPE3"] = ctype
+        if drop_rest:
+            out.header = {k: v for k, v in out.header.items() if k not in ("RESTFRQ", "RESTFREQ", "RESTWAV")}
         return out
 
     def downsampled(self, axis, factor, shape=None):
