@@ -535,6 +535,53 @@ int spc_stack_cube_f64(int device, void* stream, const spc_cube_f64* cube, const
                        int nsrc, const int32_t* h_lo, const double* h_t, const double* h_inv_dx, const int32_t* h_exact, int mode,
                        int64_t n0, double* d_out, void* d_workspace, size_t workspace_bytes);
 
+/* ---- cube arithmetic: + - * / ** with scalars, maps, spectra and cubes, a chain of them in one pass ----
+ * SpectralCube.__add__ / __sub__ / __mul__ / __truediv__ / __pow__ (spectral_cube.py:2237-2361): _apply_everywhere
+ * (:912-942, op(filled_data, value)) for a value that is not a cube, _cube_on_cube_operation (:944-1003, op of the raw
+ * samples of both cubes) for one that is.  The reference makes one pass and one temporary per operator; here a chain of
+ * up to SPC_ARITH_MAX_STEPS operators is a program that reads the cube once and writes once.  Per voxel:
+ *     a = sample;  inc = include(a, mask)  (once, on the SOURCE sample; nan_excluded as for spc_downsample_*);  v = a
+ *     for every step:  if (step.refill) v = inc ? v : fill;   v = op(v, b)
+ *     store v
+ * which is the reference step by step: every _apply_everywhere refills the excluded voxels of its input (refill = 1; they
+ * hold op(fill, b) afterwards, whatever earlier steps left there), a cube-on-cube step reads the raw samples (refill = 0).
+ * b is the step's scalar (is_scalar != 0, d_data NULL; given as double, rounded to the sample type) or an array of the
+ * entry point's sample type with one ELEMENT stride per axis, 0 = broadcast along it; stride_x is 0 or 1.  SQUARE, SQRT,
+ * RECIP and ONE take no operand (is_scalar != 0): numpy's fast paths of ** 2, ** 0.5, ** -1 and ** 0 (x * x, sqrt(x),
+ * 1 / x, 1), to which the host maps those exponents (** 1 is no step at all, or MUL by 1 in a chain).
+ * ADD SUB MUL DIV SQUARE SQRT RECIP are single correctly rounded IEEE operations in the sample type - the unit is
+ * compiled with contraction off, a MUL followed by an ADD is never fused, division and sqrt are the IEEE ones - so a
+ * chain equals numpy's stepwise result bit for bit; POW is the device pow / powf (a few ulp from a host libm).
+ * A lane owns 4 consecutive x of a row: 16-byte loads and stores (4-byte for the mask bytes) where a row's addresses
+ * allow, sample by sample at a misaligned head, at the tail and in rows whose arrays disagree about alignment; an operand
+ * that is broadcast along x costs one load per row and lane.  64-bit indexing; rows and planes are strided over the grid:
+ * no limit on any axis.  No LDS, no atomics, no workspace.  d_out strides in elements (0 = C-contiguous).
+ * SPC_ERR_INVALID before anything is queued: a NULL pointer, n_steps outside 1 ... SPC_ARITH_MAX_STEPS, an unknown opcode,
+ * is_scalar != 0 with a d_data pointer or is_scalar == 0 without one, an array operand of an opcode that takes none, a
+ * negative stride or stride_x > 1, d_out overlapping the cube, the mask array or an operand. */
+#define SPC_ARITH_MAX_STEPS 4
+typedef enum {
+    SPC_AOP_ADD = 0, SPC_AOP_SUB = 1, SPC_AOP_MUL = 2, SPC_AOP_DIV = 3, SPC_AOP_POW = 4,
+    SPC_AOP_SQUARE = 5, SPC_AOP_SQRT = 6, SPC_AOP_RECIP = 7, SPC_AOP_ONE = 8
+} spc_arith_opcode;
+typedef struct {
+    int32_t opcode;              /* spc_arith_opcode */
+    int32_t refill;              /* != 0: excluded voxels are set to fill before the operation */
+    int32_t is_scalar;           /* != 0: the operand is `scalar` and d_data must be NULL */
+    int32_t reserved;
+    double scalar;
+    const void* d_data;          /* float (_f32) or double (_f64) */
+    int64_t stride_z, stride_y, stride_x;   /* elements, >= 0; 0 = broadcast along that axis; stride_x 0 or 1 */
+} spc_arith_step;
+typedef struct {
+    int32_t n_steps, reserved;
+    spc_arith_step steps[SPC_ARITH_MAX_STEPS];
+} spc_arith_program;
+int spc_arith_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
+                  const spc_arith_program* prog, float* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_arith_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
+                  const spc_arith_program* prog, double* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+
 /* ---- FITS payload -> float32 -------------------
  * Converts n raw big-endian FITS image samples (already in HBM) to native
  * float32: what astropy.io.fits does on the host behind

@@ -43,6 +43,12 @@ MASK_PROG_MAX_SLOTS, MASK_PROG_MAX_OPERANDS, MASK_PROG_MAX_INSTR, MASK_PROG_MAX_
 MOP_CMP, MOP_FINITE, MOP_LOAD, MOP_NOT, MOP_AND, MOP_OR, MOP_XOR = range(7)
 CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_EQ, CMP_NE = range(6)
 ELEM_F32, ELEM_F64, ELEM_U8 = range(3)
+# spc_arith_program (spc_arith_f32 / _f64): the step limit and spc_arith_opcode
+ARITH_MAX_STEPS = 4
+AOP_ADD, AOP_SUB, AOP_MUL, AOP_DIV, AOP_POW, AOP_SQUARE, AOP_SQRT, AOP_RECIP, AOP_ONE = range(9)
+ARITH_OPCODES = {"add": AOP_ADD, "sub": AOP_SUB, "mul": AOP_MUL, "div": AOP_DIV, "pow": AOP_POW,
+                 "square": AOP_SQUARE, "sqrt": AOP_SQRT, "recip": AOP_RECIP, "one": AOP_ONE}
+ARITH_UNARY = ("square", "sqrt", "recip", "one")            # the exact power forms: no operand
 
 
 class HipLibraryError(RuntimeError):
@@ -114,6 +120,17 @@ class SpcMaskProgram(C.Structure):
     _fields_ = [("n_slots", C.c_int32), ("n_operands", C.c_int32), ("n_instr", C.c_int32), ("reserved", C.c_int32),
                 ("slots", SpcMaskSlot * MASK_PROG_MAX_SLOTS), ("operands", SpcMaskOperand * MASK_PROG_MAX_OPERANDS),
                 ("instr", SpcMaskInstr * MASK_PROG_MAX_INSTR)]
+
+
+class SpcArithStep(C.Structure):
+    _fields_ = [("opcode", C.c_int32), ("refill", C.c_int32), ("is_scalar", C.c_int32), ("reserved", C.c_int32),
+                ("scalar", C.c_double), ("d_data", C.c_void_p),
+                ("stride_z", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
+
+
+class SpcArithProgram(C.Structure):
+    """spc_arith_program: a chain of + - * / ** steps run in one pass by spc_arith_f32 / _f64"""
+    _fields_ = [("n_steps", C.c_int32), ("reserved", C.c_int32), ("steps", SpcArithStep * ARITH_MAX_STEPS)]
 
 
 class SpcStatsOutputs(C.Structure):
@@ -201,6 +218,8 @@ SIGNATURES = {
     "spc_mask_bbox_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
     "spc_mask_eval_f32": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),
     "spc_mask_eval_f64": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),
+    "spc_arith_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _P(SpcArithProgram), _vp, _i64, _i64]),
+    "spc_arith_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _P(SpcArithProgram), _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _f, _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i, _i, _d, _vp, _i64, _i64]),
     "spc_rank_filter_plane_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _i, _f, _vp, _i64, _i64]),

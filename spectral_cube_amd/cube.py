@@ -194,6 +194,60 @@ def _unit_pow(a, n):
     return "(%s)%d" % (a, n) if " " in a or "/" in a else "%s%d" % (a, n)
 
 
+def _unit_div(a, b):
+    a, b = (a or "").strip(), (b or "").strip()
+    if a == b:
+        return ""
+    if not b:
+        return a
+    return "%s / %s" % (a or "1", "(%s)" % b if " " in b or "/" in b else b)
+
+
+class WCSMismatchWarning(UserWarning):
+    """spectral_cube.utils.WCSMismatchWarning: arithmetic on two cubes of one shape whose WCSs differ (spectral_cube.py:979-982)"""
+
+
+def _same_fill(a, b):
+    a, b = float(a), float(b)
+    return a == b or (a != a and b != b)
+
+
+class _ArithPending:
+    """A pending chain of arithmetic steps over ``source`` (its samples and its mask): what ``cube + a``, ``- a``, ``* a``,
+    ``/ a`` and ``** a`` return carries one, and an operator applied to such a result before anything has used it extends
+    a COPY of the chain - ``(cube - cont) / rms * 1e3`` reads the cube once and writes once (ops.arith, spc_arith_f32 /
+    _f64).  ``steps``: a tuple (never mutated: the parent result keeps its own) of ``(op, operand, refill)``; operand a
+    Python float, a host array already in the sample type and broadcastable to the cube, a DeviceArray, or the right-hand
+    SpectralCube of a cube-on-cube step."""
+
+    def __init__(self, source, steps, wide, mask, fill):
+        self.source, self.steps, self.wide, self.mask, self.fill = source, tuple(steps), bool(wide), mask, fill
+
+    def _samples(self, cube):
+        """device samples of a right-hand cube in this program's sample type"""
+        if not self.wide:
+            return cube._device_data()
+        if cube._is_wide():
+            return cube._device_data64()
+        return DeviceArray.from_numpy(cube._host_data(), self.source.device, dtype=np.float64)
+
+    def __call__(self):
+        src = self.source
+        data, mspec, view = src._operand(self.wide)
+        steps = []
+        for op, operand, refill in self.steps:
+            if isinstance(operand, SpectralCube):
+                operand = self._samples(operand)
+            elif isinstance(operand, np.ndarray):
+                operand = DeviceArray.from_numpy(operand, src.device)
+            steps.append((op, operand, refill))
+        return ops.arith(data, steps, mask=mspec, fill=self.fill, nan_excluded=_nan_term_dropped(src, view))
+
+
+# numpy's fast paths of ``x ** p`` for a scalar p (x * x, sqrt, 1 / x, a copy, ones): exact, where pow() is not
+_EXACT_POWERS = {2.0: ("square", None), 0.5: ("sqrt", None), -1.0: ("recip", None), 1.0: ("mul", 1.0), 0.0: ("one", None)}
+
+
 # downsample_axis estimators, recognised by identity (np.max is np.amax, np.min is np.amin)
 _DS_ESTIMATORS = ((np.nanmean, _lib.DS_NANMEAN), (np.nansum, _lib.DS_NANSUM), (np.nanmax, _lib.DS_NANMAX),
                   (np.nanmin, _lib.DS_NANMIN), (np.mean, _lib.DS_MEAN), (np.sum, _lib.DS_SUM), (np.max, _lib.DS_MAX),
@@ -505,6 +559,7 @@ class SpectralCube:
         # evaluated by the kernel on the data it is reading
         self._data_id = _data_id if _data_id is not None else _DataToken()
         self._mask64_cache = None
+        self._arith = None                # the _ArithPending this cube is the result of (arithmetic operators), or None
 
     # ---- construction helpers ------------------------------------------------
     @classmethod
@@ -814,6 +869,136 @@ class SpectralCube:
 
     def __le__(self, value):
         return self._cmp(operator.le, value)
+
+    # ---- arithmetic: + - * / ** (spectral_cube.py:2298-2361) -------------------------------------------
+    def _pending_arith_steps(self):
+        """number of steps of the arithmetic program this cube is the pending result of; None once it has been run (or
+        for any other cube).  For tests and for the curious: a following operator extends the program while this is
+        below _lib.ARITH_MAX_STEPS."""
+        P = self._arith_pending()
+        return len(P.steps) if P is not None else None
+
+    def _arith_pending(self):
+        P = self._arith
+        if P is None or self._dev is not None:
+            return None
+        if (self._data_id.dev64 is not None) if P.wide else (self._lazy is None):
+            return None
+        return P
+
+    def _arith_value(self, name, value):
+        """the operand of ``cube <name> value`` for a value that is not a cube, checked against the cube's unit as
+        _val_to_own_unit does for + and - (spectral_cube.py:2237-2261): (a Python float, a host array in the sample type of
+        the path, or a DeviceArray; the operand's unit string or None)"""
+        unit = getattr(value, "unit", None)
+        unit = None if unit is None else str(unit).strip()
+        if name in ("add", "sub"):
+            if unit is None:
+                if self._unit.strip():
+                    raise ValueError("Can only %s cube objects from SpectralCubes or Quantities with a unit attribute."
+                                     % ("add" if name == "add" else "subtract"))
+            elif unit != self._unit.strip():
+                if not hasattr(value, "to"):
+                    raise UnitsError("%s is not equivalent to %s" % (self._unit or "dimensionless", unit or "dimensionless"))
+                value = value.to(self._unit)
+        if isinstance(value, DeviceArray):
+            ops.arith_operand_strides(value.shape, self._shape)
+            return value, unit
+        arr = np.asarray(getattr(value, "value", value))
+        if arr.dtype.kind not in "fiub":
+            raise TypeError("cube arithmetic takes real numbers and arrays of them (got %s)" % arr.dtype)
+        if arr.ndim == 0:
+            return float(arr), unit
+        ops.arith_operand_strides(arr.shape, self._shape)      # numpy's own ValueError: a (nz,) spectrum does not broadcast
+        if self._runs_wide():
+            return np.ascontiguousarray(arr, dtype=np.float64), unit
+        _warn_if_narrowed(dtype=arr.dtype, stacklevel=5)
+        return np.ascontiguousarray(arr, dtype=np.float32), unit
+
+    def _arith_cube(self, name, other):
+        """the checks of _cube_on_cube_operation (spectral_cube.py:959-1003); the unit of the result"""
+        if tuple(other._shape) != tuple(self._shape):       # (the reference's `assert cube.shape == self.shape`; kept under -O)
+            raise AssertionError("cube shapes differ: %s and %s" % (tuple(self._shape), tuple(other._shape)))
+        a, b = self._unit.strip(), other._unit.strip()
+        if a != b:
+            raise UnitsError("%s is not equivalent to %s" % (a or "dimensionless", b or "dimensionless"))
+        if (self._wcs is None) != (other._wcs is None) or (self._wcs is not None and dict(self._wcs.header) != dict(other._wcs.header)):
+            warnings.warn("Cube WCSs do not match, but their shapes do", WCSMismatchWarning, stacklevel=4)
+        if name == "pow":
+            if a:
+                raise AssertionError("Function %r could not be applied to a pair of simple cube.  The error was: %s ** %s has "
+                                     "no unit" % (operator.pow, a, b))
+            raise NotImplementedError("cube ** cube is not built")
+        return {"mul": _unit_pow(a, 2), "div": ""}.get(name, a)
+
+    def _arith_op(self, name, value):
+        if isinstance(value, SpectralCube):
+            unit = self._arith_cube(name, value)
+            return self._arith_result((name, value, False), unit)
+        operand, ounit = self._arith_value(name, value)
+        unit = self._unit
+        if name == "mul":
+            unit = _unit_pow(unit, 2) if (ounit and ounit == unit.strip()) else _unit_mul(unit, ounit)
+        elif name == "div":
+            unit = _unit_div(unit, ounit)
+        elif name == "pow":
+            if ounit:
+                raise UnitsError("an exponent cannot carry a unit (got %s)" % ounit)
+            if not isinstance(operand, float):
+                if unit.strip():
+                    raise NotImplementedError("an array exponent on a cube with a unit (%s)" % unit)
+            else:
+                if operand.is_integer():
+                    unit = _unit_pow(unit, int(operand)) if operand != 0 else ""
+                elif operand == 0.5:
+                    unit = unit.strip() + "(1/2)" if unit.strip() else unit
+                elif unit.strip():
+                    raise NotImplementedError("%s ** %r: only integer exponents and 0.5 are built for a cube with a unit" % (unit, operand))
+                if operand in _EXACT_POWERS:
+                    name, operand = _EXACT_POWERS[operand]
+        return self._arith_result((name, operand, True), unit)
+
+    def _arith_result(self, step, unit):
+        """the pending result of one more step: the program of a pending arithmetic result is extended (in a copy) while
+        nothing has run it, mask and fill value are the ones it was planned with, it has room, and the right-hand side is
+        not itself a pending program; anything else starts a new program on this cube, which is materialised by its
+        first use.  New data token, this cube's mask, fill value, WCS, meta and beams."""
+        P = self._arith_pending()
+        right = step[1]
+        right_pending = isinstance(right, SpectralCube) and right._arith_pending() is not None
+        if (P is not None and P.mask is self._mask and _same_fill(P.fill, self._fill_value)
+                and len(P.steps) < _lib.ARITH_MAX_STEPS and not right_pending):
+            pending = _ArithPending(P.source, P.steps + (step,), P.wide, P.mask, P.fill)
+        else:
+            pending = _ArithPending(self, (step,), self._runs_wide(), self._mask, self._fill_value)
+        out = self._result_cube(pending, pending.wide)
+        out._unit = unit
+        out._arith = pending
+        return out
+
+    @warn_slow
+    def __add__(self, value):
+        return self._arith_op("add", value)
+
+    @warn_slow
+    def __sub__(self, value):
+        return self._arith_op("sub", value)
+
+    @warn_slow
+    def __mul__(self, value):
+        return self._arith_op("mul", value)
+
+    @warn_slow
+    def __truediv__(self, value):
+        return self._arith_op("div", value)
+
+    @warn_slow
+    def __pow__(self, value):
+        return self._arith_op("pow", value)
+
+    @warn_slow
+    def __floordiv__(self, value):
+        raise NotImplementedError("Floor-division (division with truncation) is not supported.")
 
     # ---- data access -----------------------------------------------------------------
     def _device_data(self):

@@ -527,6 +527,65 @@ def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_m
     return out, out_mask
 
 
+def arith_operand_strides(shape, cube_shape, strides=None):
+    """element strides (z, y, x) of an operand of *shape* broadcast against *cube_shape* by numpy's rules, 0 along a
+    broadcast axis; *strides*: the operand's own element strides per axis (C-contiguous when None).  ValueError in
+    numpy's words when the shapes do not broadcast to the cube's."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) > 3 or any(n != 1 and n != m for n, m in zip(shape[::-1], tuple(cube_shape)[::-1])):
+        raise ValueError("operands could not be broadcast together with shapes %s %s" % (tuple(cube_shape), shape))
+    if strides is None:
+        strides = [int(np.prod(shape[a + 1:], dtype=np.int64)) for a in range(len(shape))]
+    full = [0] * (3 - len(shape)) + [0 if n == 1 else int(s) for n, s in zip(shape, strides)]
+    return tuple(full)
+
+
+def arith(cube, steps, mask=None, fill=np.nan, out=None, stream=None, nan_excluded=False):
+    """A chain of + - * / ** steps over the cube in one pass (SpectralCube.__add__ ... __pow__, spectral_cube.py:2237-2361,
+    through _apply_everywhere :912-942 and _cube_on_cube_operation :944-1003): a DeviceArray of the cube's dtype.
+    *steps*: up to _lib.ARITH_MAX_STEPS tuples ``(op, operand, refill)``; op a key of _lib.ARITH_OPCODES; operand a Python
+    scalar, or a DeviceArray of the cube's dtype whose shape broadcasts to the cube's by numpy's rules (a (ny, nx) map, a
+    (nz, 1, 1) spectrum, a cube, ...), or None for the exact power forms square / sqrt / recip / one.  Per voxel the
+    include bit of *mask* is taken once on the source sample; a step with *refill* first sets the excluded voxels to
+    *fill* (the filled data the reference's _apply_everywhere starts from), then applies op.  + - * / and the exact forms
+    are single IEEE operations (no FMA): the result equals numpy's stepwise one bit for bit."""
+    name, dtype = _entry("arith", cube)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    steps = list(steps)
+    prog = _lib.SpcArithProgram()
+    prog.n_steps = len(steps)
+    if len(steps) > _lib.ARITH_MAX_STEPS:
+        raise _lib.HipInvalidArgument("an arithmetic program holds at most %d steps (got %d)" % (_lib.ARITH_MAX_STEPS, len(steps)))
+    keep = []
+    for s, (op, operand, refill) in zip(prog.steps, steps):
+        if op not in _lib.ARITH_OPCODES:
+            raise ValueError("unknown arithmetic step %r (one of %s)" % (op, sorted(_lib.ARITH_OPCODES)))
+        s.opcode, s.refill = _lib.ARITH_OPCODES[op], 1 if refill else 0
+        if isinstance(operand, DeviceArray):
+            if op in _lib.ARITH_UNARY:
+                raise ValueError("step %r takes no operand" % op)
+            if operand.dtype != dtype:
+                raise TypeError("operand of %r must be a %s DeviceArray like the cube (got %s)" % (op, dtype, operand.dtype))
+            own = None
+            if len(operand.shape) == 3 and hasattr(operand, "row_stride"):
+                own = (operand.plane_stride, operand.row_stride, 1)
+            s.stride_z, s.stride_y, s.stride_x = arith_operand_strides(operand.shape, cube.shape, own)
+            s.is_scalar, s.d_data = 0, operand.ptr
+            keep.append(operand)
+        else:
+            if operand is None and op not in _lib.ARITH_UNARY:
+                raise ValueError("step %r needs an operand" % op)
+            s.is_scalar, s.scalar, s.d_data = 1, float(0.0 if operand is None else operand), None
+    if out is None:
+        out = DeviceArray(cube.shape, dtype, cube.device)
+    elif tuple(out.shape) != tuple(cube.shape) or out.dtype != dtype:
+        raise ValueError("preallocated output must be %s %s" % (tuple(cube.shape), dtype))
+    ors, ops_ = _strides(out)
+    _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill), C.byref(prog),
+              C.c_void_p(out.ptr), ors, ops_)
+    return out
+
+
 def _bbox_result(box, device, stream):
     if stream is not None:
         _lib.call("spc_stream_sync", device, _sh(stream))
