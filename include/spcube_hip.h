@@ -93,6 +93,17 @@ typedef struct {
 /* ---- library / device management -------------------------------------- */
 int spc_abi_version(void);
 const char* spc_last_error(void);
+/* Which form spc_spatial_conv_sep_f32 tries first for a mask ARRAY, as a setting of the CALLING THREAD (like the
+ * message of spc_last_error): SPC_SPATIAL_FORM_ENV, the initial value of every thread, follows the environment switch
+ * SPC_SPATIAL_RING (1 = ring) read at each call; _SPLIT = the split form on the matrix cores (fp16 hi + lo products,
+ * float32 sums), _RING = the ring kernels (float32 multiply-adds).  A thread's setting wins over the environment and
+ * is seen by no other thread.  The setter returns the previous value, for the caller to restore; a value that is none
+ * of the three is ignored (the setting and the returned previous value are as if the call had been the getter). */
+#define SPC_SPATIAL_FORM_ENV   (-1)
+#define SPC_SPATIAL_FORM_SPLIT 0
+#define SPC_SPATIAL_FORM_RING  1
+int spc_set_masked_spatial_form(int form);
+int spc_get_masked_spatial_form(void);
 int spc_device_count(int* count);
 typedef struct {
     char name[128];
@@ -144,9 +155,13 @@ int spc_event_elapsed_ms(int device, void* start, void* stop, float* ms);
 /* ---- device scratch -----------------------------------------------------
  * Bytes of d_workspace an entry point needs for a (nz,ny,nx) cube; p0 / p1 are the
  * kernel extents or the output shape it is called with.  An upper bound that only
- * depends on these numbers (not on the data, the mask kind or environment switches),
- * so one buffer sized once serves a whole pipeline of equal-sized calls.  Contents
- * need not be preserved between calls; two calls in flight at the same time (two
+ * depends on these numbers (not on the data or the mask kind), so one buffer sized
+ * once serves a whole pipeline of equal-sized calls.  Of the environment switches
+ * (docs/DESIGN_NOTES.md lists them) two tuning hooks move a size: SPC_WS_MOMENTS
+ * grows with SPC_MOMENTS_NSPLIT, and setting it or SPC_MOMENTS_VEC makes small
+ * cubes that otherwise need none ask for scratch - size the buffer with the same
+ * environment the calls will see.  No other kind reads a switch.  Contents need
+ * not be preserved between calls; two calls in flight at the same time (two
  * streams) need two workspaces. */
 typedef enum {
     SPC_WS_MOMENTS = 0,               /* spc_moments_f32 (== spc_moments_workspace_bytes) */

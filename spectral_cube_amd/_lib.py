@@ -23,6 +23,8 @@ MASK_NONE, MASK_ARRAY, MASK_FINITE = 0, 1, 2
 MASK_GT, MASK_GE, MASK_LT, MASK_LE = 4, 8, 16, 32
 COMM_ID_BYTES = 128
 ABI_VERSION = 8
+# spc_set_masked_spatial_form / spc_get_masked_spatial_form
+SPATIAL_FORM_ENV, SPATIAL_FORM_SPLIT, SPATIAL_FORM_RING = -1, 0, 1
 MAP_MUL, MAP_SECOND_MOMENT_SUM, MAP_DIV_ADD, MAP_DIV_SUB_SQ = 0, 1, 2, 3
 # spc_ws_kind
 (WS_MOMENTS, WS_SPECTRAL_CONV, WS_SPECTRAL_CONV_MOMENTS, WS_SPATIAL_CONV_SEP, WS_SPATIAL_CONV2D, WS_RESAMPLE_BILINEAR,
@@ -152,6 +154,8 @@ _P = C.POINTER
 SIGNATURES = {
     "spc_abi_version": (_i, []),
     "spc_last_error": (C.c_char_p, []),
+    "spc_set_masked_spatial_form": (_i, [_i]),
+    "spc_get_masked_spatial_form": (_i, []),
     "spc_device_count": (_i, [_P(_i)]),
     "spc_get_device_info": (_i, [_i, _P(SpcDeviceInfo)]),
     "spc_malloc": (_i, [_i, _sz, _P(_vp)]),

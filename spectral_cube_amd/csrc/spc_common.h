@@ -12,6 +12,18 @@
 
 void spc_set_error(const char* fmt, ...);
 
+// ---- the SPC_* switches of the process environment: the one place that reads them ----------------------------
+// docs/DESIGN_NOTES.md lists every switch with its default and when it is read.  spc_switch: atoi of the value when
+// the variable is set ("" and text that is no number give 0), dflt when it is not.  A site that only asks whether a
+// variable is set passes a default that no valid value takes: spc_switch(name, -1) != -1.  A site that reads once
+// per process keeps the result in a static of its own; everything else reads per call, because the tests flip
+// switches inside one process.
+static inline const char* spc_switch_text(const char* name) { return getenv(name); }     // SPC_POOL_MAX_BYTES only: 64 bits
+static inline int spc_switch(const char* name, int dflt) {
+    const char* e = spc_switch_text(name);
+    return e ? atoi(e) : dflt;
+}
+
 #define SPC_HIP(call)                                                         \
     do {                                                                      \
         hipError_t e_ = (call);                                               \

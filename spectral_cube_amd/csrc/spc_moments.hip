@@ -430,11 +430,6 @@ int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr);
 }
 
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     Plan p;
     auto aligned = [&](int v) {
@@ -444,20 +439,20 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
                (!arr || ((m.row_stride % v == 0) && (m.plane_stride % v == 0) && (((uintptr_t)m.arr) % v == 0)));
     };
     // tuning hooks (SPC_MOMENTS_*): defaults chosen from MI355X measurements
-    int vec = env_int("SPC_MOMENTS_VEC", 4);
+    int vec = spc_switch("SPC_MOMENTS_VEC", 4);
     if (vec != 1 && vec != 2 && vec != 4) vec = 4;
     while (vec > 1 && !aligned(vec)) vec >>= 1;
     p.vec = vec;
     // MI355X sweeps at 1024^3 (tools/tune_moments.py; profiles/r01_tune_moments.log, r04_moments_issue.log)
     const bool arr_ = (m.flags & SPC_MASK_ARRAY) != 0;
     (void)arr_;
-    p.u = env_int("SPC_MOMENTS_U", ext ? 2 : 8);
+    p.u = spc_switch("SPC_MOMENTS_U", ext ? 2 : 8);
     if (p.u != 2 && p.u != 4 && p.u != 8) p.u = 4;
     const int64_t ngroups = c->ny * (c->nx / p.vec);
     const int64_t nblocks = (ngroups + kLanes - 1) / kLanes;
     // in-block z split: ZW waves share the columns when z is long enough
     // eight waves per block pay on planes up to 8 MiB (C2: 0.866 -> 0.827 ms), not on the north star's 16 MiB planes (13.06 -> 13.22 ms)
-    p.zw = env_int("SPC_MOMENTS_ZW", c->nz >= 512 && !ext && c->ny * c->nx <= (1 << 21) ? 8 : (c->nz >= 16 ? 4 : 1));
+    p.zw = spc_switch("SPC_MOMENTS_ZW", c->nz >= 512 && !ext && c->ny * c->nx <= (1 << 21) ? 8 : (c->nz >= 16 ? 4 : 1));
     if (p.zw != 1 && p.zw != 4 && p.zw != 8) p.zw = 1;
     if (p.vec != 4) { p.u = 4; if (p.zw > 4) p.zw = 4; }
     // grid z split only when the map alone cannot fill the chip (256 CUs x ~8 blocks)
@@ -465,7 +460,7 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     const int64_t target = 2048;
     if (nblocks < target && c->nz >= 256)
         nsplit = (int)std::min<int64_t>(std::min<int64_t>((target + nblocks - 1) / nblocks, c->nz / 64), 16);
-    nsplit = std::max(1, env_int("SPC_MOMENTS_NSPLIT", nsplit));
+    nsplit = std::max(1, spc_switch("SPC_MOMENTS_NSPLIT", nsplit));
     p.zchunk = (c->nz + nsplit - 1) / nsplit;
     p.nsplit = (int)((c->nz + p.zchunk - 1) / p.zchunk);
     return p;
@@ -479,10 +474,11 @@ size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
     if (nz <= 0 || ny <= 0 || nx <= 0) return 0;
     // upper bound on nsplit used by make_plan
     int64_t nsplit_max = std::max<int64_t>(1, std::min<int64_t>(nz / 64, 16));
-    const char* env = getenv("SPC_MOMENTS_NSPLIT");
-    if (env) nsplit_max = std::max<int64_t>(nsplit_max, atoi(env));
+    // (the two switches that move make_plan's split; -1: not set)
+    const int env = spc_switch("SPC_MOMENTS_NSPLIT", -1);
+    if (env != -1) nsplit_max = std::max<int64_t>(nsplit_max, env);
     const int64_t nblocks = (ny * nx / 4 + kLanes - 1) / kLanes;
-    if (!env && !getenv("SPC_MOMENTS_VEC") && (nblocks >= 2048 || nz < 256)) return 0;
+    if (env == -1 && spc_switch("SPC_MOMENTS_VEC", -1) == -1 && (nblocks >= 2048 || nz < 256)) return 0;
     return (size_t)nsplit_max * kWsFields * sizeof(double) * (size_t)(ny * nx);
 }
 
@@ -508,7 +504,7 @@ int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const sp
     Plan p = make_plan(cube, A.mask, ext);
     spc_canonical_pred(A.mask.flags, A.mask.thr_lo, A.mask.thr_hi, &A.lim, &A.lo, &A.hi);
     const bool thr = (A.mask.flags & (SPC_MASK_GT | SPC_MASK_GE | SPC_MASK_LT | SPC_MASK_LE)) != 0;
-    A.xcd_group = env_int("SPC_MOMENTS_XCD", 0);    // measured: +- 1 % either way on the real kernel (profiles/r04_moments_issue.log)
+    A.xcd_group = spc_switch("SPC_MOMENTS_XCD", 0);    // measured: +- 1 % either way on the real kernel (profiles/r04_moments_issue.log)
     A.groups_per_row = cube->nx / p.vec;
     A.ngroups = cube->ny * A.groups_per_row;
     A.nsplit = p.nsplit;

@@ -942,13 +942,12 @@ int spc_spectral_lerp_f32(int device, void* stream, const spc_cube_f32* cube, co
     int nsplit = 1;
     if (nblocks < 2048) nsplit = (int)std::max<int64_t>(1, std::min<int64_t>((2048 + nblocks - 1) / nblocks, nz_out / 16));
     A.jchunk = (nz_out + nsplit - 1) / nsplit;
-    A.nt_store = 1;
-    { const char* e = getenv("SPC_LERP_JCHUNK"); if (e && atoi(e) > 0) A.jchunk = atoi(e); e = getenv("SPC_LERP_NT"); if (e) A.nt_store = atoi(e); }
+    A.nt_store = spc_switch("SPC_LERP_NT", 1);
+    { const int jc = spc_switch("SPC_LERP_JCHUNK", 0); if (jc > 0) A.jchunk = jc; }
     nsplit = (int)((nz_out + A.jchunk - 1) / A.jchunk);
     SPC_REQUIRE(nsplit <= 65535, "too many channel groups for one launch");
     {   // short-lived blocks (see spectral_lerp_tiles_kernel): 16-byte rows, enough work to fill the chip; SPC_LERP_TILES=0 keeps the march
-        const char* e = getenv("SPC_LERP_TILES");
-        const int want = e ? atoi(e) : 1;
+        const int want = spc_switch("SPC_LERP_TILES", 1);
         constexpr int JC = 4;
         const int64_t bpr = (cube->nx / 4 + 255) / 256, groups = (nz_out + JC - 1) / JC;
         if (want && v4 && cube->nz >= 3 && groups <= 65535 && bpr * cube->ny < (1ll << 31) && bpr * cube->ny * groups >= 4096) {
@@ -1070,15 +1069,14 @@ static int bilinear_launch(int device, void* stream, const spc_cube_f32* cube, c
     A.zchunk = (nzw + nsplit - 1) / nsplit;
     nsplit = (int)((nzw + A.zchunk - 1) / A.zchunk);
     // LDS-staged pass over 32 x 32 tiles first; the gather kernel then only does flagged tiles
-    const char* env = getenv("SPC_BILINEAR_LDS");
-    const bool want = env ? atoi(env) != 0 : true;
+    const bool want = spc_switch("SPC_BILINEAR_LDS", 1) != 0;
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     const bool fits = cube->ny * cube->row_stride < (1ll << 31) &&
                       (!arr || cube->ny * A.mask.row_stride < (1ll << 31));
     A.status = nullptr;
     if (want && fits) {
-        const char* tenv = getenv("SPC_BILINEAR_TILE");
-        const int tile = tenv ? (atoi(tenv) == 32 ? 32 : 64) : ((nx_out >= 128 && ny_out >= 128) ? 64 : 32);
+        const int tenv = spc_switch("SPC_BILINEAR_TILE", -1);          // -1: not set
+        const int tile = tenv != -1 ? (tenv == 32 ? 32 : 64) : ((nx_out >= 128 && ny_out >= 128) ? 64 : 32);
         const int kStageU = tile == 64 ? BilTile<64>::kStageU : BilTile<32>::kStageU;
         A.tile_shift = tile == 64 ? 6 : 5;
         A.tiles32_x = (nx_out + tile - 1) / tile;
@@ -1092,7 +1090,7 @@ static int bilinear_launch(int device, void* stream, const spc_cube_f32* cube, c
         // tail - not cache reuse: FETCH_SIZE did not move (profiles/r01_pmc_traffic.txt).
         // (LERP: 512 input planes per block - C5 in one pass 6.6 / 6.2 / 6.17 / 6.1 ms with 64 / 128 / 256 / 512)
         A.zchunk_lds = std::min<int64_t>((nzw + ns - 1) / ns, lerp ? 512 : 256);
-        if (const char* zc = getenv("SPC_BILINEAR_ZCHUNK")) A.zchunk_lds = std::max(8, atoi(zc));
+        { const int zc = spc_switch("SPC_BILINEAR_ZCHUNK", -1); if (zc != -1) A.zchunk_lds = std::max(8, zc); }
         A.zchunk_lds = ((A.zchunk_lds + kStageU - 1) / kStageU) * kStageU;
         ns = (int)((nzw + A.zchunk_lds - 1) / A.zchunk_lds);
         SPC_WS_TAKE(d_status, ws, unsigned char, ntiles);

@@ -5,6 +5,7 @@
 #include <unordered_map>
 
 static thread_local char g_err[512] = "";
+static thread_local int g_masked_spatial_form = SPC_SPATIAL_FORM_ENV;
 
 // ---- device buffer pool behind spc_malloc / spc_free ------------------------------------------
 // Cube-sized hipMalloc calls are the slowest thing a pipeline of operators meets on this stack:
@@ -28,13 +29,13 @@ struct DevicePool {
 DevicePool g_pool[kMaxDevices];
 
 bool pool_enabled() {
-    static const bool on = [] { const char* e = getenv("SPC_POOL"); return !(e && atoi(e) == 0); }();
+    static const bool on = spc_switch("SPC_POOL", 1) != 0;
     return on;
 }
 // SPC_POOL_POISON=1 (debugging): every block spc_malloc returns is filled with 0xFF bytes (NaN as float /
 // double, -1 as integer), so that an operator relying on zeroed fresh memory fails the test-suite at once
 bool pool_poison() {
-    static const bool on = [] { const char* e = getenv("SPC_POOL_POISON"); return e && atoi(e) != 0; }();
+    static const bool on = spc_switch("SPC_POOL_POISON", 0) != 0;
     return on;
 }
 size_t pool_round(size_t bytes) {
@@ -95,6 +96,13 @@ extern "C" {
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char* spc_last_error(void) { return g_err; }
+
+int spc_get_masked_spatial_form(void) { return g_masked_spatial_form; }
+int spc_set_masked_spatial_form(int form) {
+    const int prev = g_masked_spatial_form;
+    if (form == SPC_SPATIAL_FORM_ENV || form == SPC_SPATIAL_FORM_SPLIT || form == SPC_SPATIAL_FORM_RING) g_masked_spatial_form = form;
+    return prev;
+}
 
 size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx);
 
@@ -208,7 +216,7 @@ int spc_free(int device, void* d_ptr) {
             const size_t sz = it->second;
             if (!P.cap_known) {
                 size_t fr = 0, tot = 0;
-                const char* e = getenv("SPC_POOL_MAX_BYTES");
+                const char* e = spc_switch_text("SPC_POOL_MAX_BYTES");     // a byte count: may exceed an int
                 if (e) P.cap = (size_t)strtoull(e, nullptr, 10);
                 else if (hipMemGetInfo(&fr, &tot) == hipSuccess) P.cap = tot / 2;
                 P.cap_known = true;

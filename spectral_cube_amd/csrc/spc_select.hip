@@ -361,8 +361,6 @@ __device__ __forceinline__ void count_keys(const uint32_t (&key)[KPL], uint32_t 
 //    validity test.  The launcher picks DESC when L planes and TS columns stay below 2 GiB of byte offset
 //    (sel_desc_fits); larger planes keep 64-bit per-lane addresses (clamped to the last plane).
 // cen: select on |x - cen| when CEN (mad_std).
-static inline bool spc_env_on(const char* name) { const char* e = getenv(name); return e ? atoi(e) != 0 : true; }
-static inline bool spc_env_set(const char* name) { const char* e = getenv(name); return e ? atoi(e) != 0 : false; }
 static inline bool sel_desc_fits(int ts, int64_t plane_stride, int64_t x_stride, int bt = 256) {
     const int64_t L = bt / ts;
     return (L * plane_stride + ts * x_stride) * 4 < (1ll << 31);
@@ -1283,11 +1281,11 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
     A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
     A.q = q; A.center = d_center; A.scale = scale; A.out = d_out;
     A.x_stride = 1; A.m_x_stride = 1; A.along_ray = 0;
-    { const char* ab = getenv("SPC_SELECT_ABLATE"); A.ablate = ab ? atoi(ab) : 0; }
+    A.ablate = spc_switch("SPC_SELECT_ABLATE", 0);
     // (16 neighbouring tiles of a row per XCD: a block's half - or quarter - of a 128-byte line is found in the L2 that fetched it
     //  for its neighbour.  1024^3: the clip kernel's read + write floor 4.21 -> 3.28 ms, the 256-thread selection 2.97 -> 2.65 ms;
     //  groups of 2 / 4 / 8: 3.95 / 3.54 / 3.32 - 3.6 ms; no effect on the 512-thread selection.  SPC_XCD_GROUP=0: block = tile)
-    { const char* xg = getenv("SPC_XCD_GROUP"); A.xcd_group = xg ? atoi(xg) : 16; }
+    A.xcd_group = spc_switch("SPC_XCD_GROUP", 16);
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     const bool v4 = (cube->nx % 4 == 0) && (cube->row_stride % 4 == 0) && (cube->plane_stride % 4 == 0) &&
                     ((((uintptr_t)cube->d_data) & 15) == 0) &&
@@ -1295,14 +1293,13 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
     hipStream_t st = (hipStream_t)stream;
     // rays in registers (one read of the cube): up to 128 keys per lane, nz <= 512 / 1024 / 4096 for 32 / 16 / 8 spaxels
     // per block; any strides (a y-ray view included)
-    const char* renv = getenv("SPC_SELECT_REG");
-    if ((renv ? atoi(renv) != 0 : true) && cube->nz <= 4096 && cube->ny * ((cube->nx + 7) / 8) < (1LL << 31)) {
+    if (spc_switch("SPC_SELECT_REG", 1) != 0 && cube->nz <= 4096 && cube->ny * ((cube->nx + 7) / 8) < (1LL << 31)) {
         // Blocks of 512 threads (round 3): the lanes of a wave cover 64 / 32 / 16 / 8 ADJACENT spaxels for rays of up to 512 /
         // 1024 / 2048 / 4096 samples - a plane's samples of a block are one 256 / 128 / 64 / 32-byte run.  With 256 threads
         // (16 spaxels, 64-byte runs at 1024 channels) the one read of the cube ran at 2.1 TB/s and made up 2.0 of the 2.9 ms
         // at 1024^3 (timing-only ablation, tools/bench_select_ablate.py); 32 spaxels: 0.92 ms.  SPC_SELECT_BT=256: the former table.
         {
-            const char* be = getenv("SPC_SELECT_BT");
+            const int bt = spc_switch("SPC_SELECT_BT", 0);
             // (rays of up to 256 samples keep the 256-thread table - 32 spaxels per block already, and the per-ray costs of the
             //  descent dominate: 2.26 against 2.46 ms at 256 x 2048 x 2048 - and so do rays above 2048 samples with a mask ARRAY,
             //  whose 8 spaxels per block make 8-byte runs of mask bytes either way: 4.1 against 5.1 ms at 4096 x 512 x 512)
@@ -1312,11 +1309,11 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
             // on a ray of 100 samples it is most of the pass (0.8 - 1.1 ms per pass at 100 x 2048 x 4096 against 0.25 ms for
             // the same bytes in rays of 1024): 2 lanes per ray up to 128 samples, 4 up to 256, 64 keys each - and 128 / 64
             // adjacent spaxels per block.  SPC_SELECT_SHORT=0: the former table.
-            if (cube->nz <= 256 && !(be && atoi(be) != 0) && spc_env_on("SPC_SELECT_SHORT")) {
+            if (cube->nz <= 256 && bt == 0 && spc_switch("SPC_SELECT_SHORT", 1) != 0) {
                 const int64_t nzr = cube->nz;
                 const int tss = nzr <= 128 ? 128 : 64;
                 const int kpls = nzr <= 32 ? 16 : (nzr <= 64 ? 32 : 64);
-                const bool descs = sel_desc_fits(tss, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 256) && spc_env_on("SPC_SELECT_DESC");
+                const bool descs = sel_desc_fits(tss, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 256) && spc_switch("SPC_SELECT_DESC", 1) != 0;
                 dim3 grids((unsigned)(cube->ny * ((cube->nx + tss - 1) / tss)));
 #define SPC_LAUNCH_SHORT(TS_, K_)                                                                                                    \
                 do {                                                                                                                \
@@ -1333,11 +1330,11 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
                 SPC_LAUNCH_CHECK();
                 return SPC_OK;
             }
-            if (!(be && atoi(be) == 256) && !keep256) {
+            if (bt != 256 && !keep256) {
                 const int64_t nzr = cube->nz;
                 const int ts2 = nzr <= 512 ? 64 : (nzr <= 1024 ? 32 : (nzr <= 2048 ? 16 : 8));
                 const int kpl2 = 64;
-                const bool desc2 = sel_desc_fits(ts2, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 512) && spc_env_on("SPC_SELECT_DESC");
+                const bool desc2 = sel_desc_fits(ts2, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 512) && spc_switch("SPC_SELECT_DESC", 1) != 0;
                 dim3 grid2((unsigned)(cube->ny * ((cube->nx + ts2 - 1) / ts2)));
 #define SPC_LAUNCH_BT(TS_, K_)                                                                                                       \
                 do {                                                                                                                \
@@ -1360,7 +1357,7 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
         // (descriptor loads: measured no gain for the selection - 3.64 against 3.25 ms with a uint8 mask, 2.61 against 2.65 ms
         //  without, 1024^3 - its time is in the digit passes; they pay for the clip kernel: 10.1 against 10.8 ms, mad_std 28.3
         //  against 31.9 ms.  SPC_SELECT_DESC=1 switches them on here.)
-        const bool desc = sel_desc_fits(ts, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1) && spc_env_set("SPC_SELECT_DESC");
+        const bool desc = sel_desc_fits(ts, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1) && spc_switch("SPC_SELECT_DESC", 0) != 0;
         const int lanes = 256 / ts;
         const int need = (int)((cube->nz + lanes - 1) / lanes);
         const int kpl = need <= 16 ? 16 : (need <= 32 ? 32 : (need <= 64 ? 64 : 128));   // 128: 2049 - 4096 channels, 8 spaxels per block
@@ -1383,8 +1380,7 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
         SPC_LAUNCH_CHECK();
         return SPC_OK;
     }
-    const char* env = getenv("SPC_SELECT_RADIX16");
-    if (v4 && cube->nz <= 65535 && (env ? atoi(env) != 0 : true)) {
+    if (v4 && cube->nz <= 65535 && spc_switch("SPC_SELECT_RADIX16", 1) != 0) {
         const int64_t n = cube->ny * (cube->nx / 4);
         dim3 grid((unsigned)((n + 255) / 256));
         if (arr) hipLaunchKernelGGL(select16_axis0_kernel<true>, grid, dim3(256), 0, st, A);
@@ -1510,7 +1506,7 @@ extern "C" int spc_percentile_axis2_f32(int device, void* stream, const spc_cube
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     hipStream_t st = (hipStream_t)stream;
     const int ts = A.nz <= 512 ? 32 : (A.nz <= 1024 ? 16 : 8);
-    const bool desc = sel_desc_fits(ts, 1, std::max(A.x_stride, arr ? A.m_x_stride : 0)) && spc_env_set("SPC_SELECT_DESC");
+    const bool desc = sel_desc_fits(ts, 1, std::max(A.x_stride, arr ? A.m_x_stride : 0)) && spc_switch("SPC_SELECT_DESC", 0) != 0;
     const int lanes = 256 / ts;
     const int need = (int)((A.nz + lanes - 1) / lanes);
     const int kpl = need <= 16 ? 16 : (need <= 32 ? 32 : (need <= 64 ? 64 : 128));
@@ -1561,8 +1557,8 @@ extern "C" int spc_sigma_clip_axis0_f32(int device, void* stream, const spc_cube
     // (16 neighbouring tiles of a row per XCD: a block's half - or quarter - of a 128-byte line is found in the L2 that fetched it
     //  for its neighbour.  1024^3: the clip kernel's read + write floor 4.21 -> 3.28 ms, the 256-thread selection 2.97 -> 2.65 ms;
     //  groups of 2 / 4 / 8: 3.95 / 3.54 / 3.32 - 3.6 ms; no effect on the 512-thread selection.  SPC_XCD_GROUP=0: block = tile)
-    { const char* xg = getenv("SPC_XCD_GROUP"); A.xcd_group = xg ? atoi(xg) : 16; }
-    { const char* ce = getenv("SPC_SELECT_COMPACT"); A.compact = ce ? atoi(ce) : 2; }   // 0: off, 1: packed rays through the block's loop, 2: every wave on its own
+    A.xcd_group = spc_switch("SPC_XCD_GROUP", 16);
+    A.compact = spc_switch("SPC_SELECT_COMPACT", 2);   // 0: off, 1: packed rays through the block's loop, 2: every wave on its own
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     hipStream_t st = (hipStream_t)stream;
     // 256-thread blocks for the median forms: with 512 threads (wider runs per plane, see spc_percentile_axis0_f32) the read +
@@ -1571,14 +1567,13 @@ extern "C" int spc_sigma_clip_axis0_f32(int device, void* stream, const spc_cube
     // slowest of 32 rays): 10.4 against 8.6 ms for astropy's defaults.  Without a descent (centre = mean, spread = std) or
     // with a single iteration the wider blocks win: 2.3 - 3.4 against 4.2 ms.  SPC_SIGMA_BT=256 / 512 forces either.
     {
-        const char* be = getenv("SPC_SIGMA_BT");
-        const int force = be ? atoi(be) : 0;
+        const int force = spc_switch("SPC_SIGMA_BT", 0);
         const bool wide = force == 512 || (force != 256 && (A.cen_mean || A.maxiters == 1));
         const bool wide_ok = cube->nz > 512 && cube->nz <= 1024 && !A.spread_mad &&
                              sel_desc_fits(32, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 512);
         // neither forced nor decided by the form: the mask decides (clip_probe_kernel), given a workspace word to decide in
         if (!wide && wide_ok && force == 0 && A.compact >= 2 && d_workspace != nullptr && workspace_bytes >= sizeof(int) &&
-            cube->ny * cube->nx >= 4 * kProbeRays && spc_env_on("SPC_SIGMA_PROBE")) {
+            cube->ny * cube->nx >= 4 * kProbeRays && spc_switch("SPC_SIGMA_PROBE", 1) != 0) {
             int* d_max = static_cast<int*>(d_workspace);
             SPC_HIP(hipMemsetAsync(d_max, 0, sizeof(int), st));
             if (arr) hipLaunchKernelGGL(clip_probe_kernel<true>, dim3(kProbeRays), dim3(256), 0, st, A, d_max);
@@ -1594,7 +1589,7 @@ extern "C" int spc_sigma_clip_axis0_f32(int device, void* stream, const spc_cube
         }
     }
     // short rays: few lanes per ray (see spc_percentile_axis0_f32): 2 for 65 .. 128 samples, 4 up to 256
-    if (cube->nz > 64 && cube->nz <= 256 && !A.spread_mad && spc_env_on("SPC_SIGMA_SHORT") &&
+    if (cube->nz > 64 && cube->nz <= 256 && !A.spread_mad && spc_switch("SPC_SIGMA_SHORT", 1) != 0 &&
         sel_desc_fits(cube->nz <= 128 ? 128 : 64, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1, 256)) {
         const int tss = cube->nz <= 128 ? 128 : 64;
         dim3 grids((unsigned)(cube->ny * ((cube->nx + tss - 1) / tss)));
@@ -1609,7 +1604,7 @@ extern "C" int spc_sigma_clip_axis0_f32(int device, void* stream, const spc_cube
         return SPC_OK;
     }
     const int ts = cube->nz <= 512 ? 32 : (cube->nz <= 1024 ? 16 : 8);
-    const bool desc = sel_desc_fits(ts, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1) && spc_env_on("SPC_SELECT_DESC");
+    const bool desc = sel_desc_fits(ts, std::max(cube->plane_stride, arr ? A.mask.plane_stride : 0), 1) && spc_switch("SPC_SELECT_DESC", 1) != 0;
     const int lanes = 256 / ts;
     const int need = (int)((cube->nz + lanes - 1) / lanes);
     const int kpl = need <= 16 ? 16 : (need <= 32 ? 32 : (need <= 64 ? 64 : 128));

@@ -454,9 +454,8 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
     if (rc) return rc;
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const char* env = getenv("SPC_CONV2D_TILED");
     // (the tiled kernel's static row/output masks assume at least 9 rows of taps)
-    const bool tiled = (env ? atoi(env) != 0 : true) && nky >= 9 && nky <= kT2MaxK && nkx <= kT2MaxK &&
+    const bool tiled = spc_switch("SPC_CONV2D_TILED", 1) != 0 && nky >= 9 && nky <= kT2MaxK && nkx <= kT2MaxK &&
                        (cube->ny + kT2Y - 1) / kT2Y <= 65535;
     // tiled: transposed columns padded with 7 zeros on both sides, kT[jx][7 + jy] = k[jy][jx]
     const int n = tiled ? nkx * (nky + 14) : nky * nkx;
@@ -480,9 +479,8 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_conv2d_tiled_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             }
             // masks that only reject non-finite samples: the all-valid pass first, then the flagged tiles
-            const char* fenv = getenv("SPC_CONV_FAST");
             A.status = nullptr;
-            if ((fenv ? atoi(fenv) != 0 : true) && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
+            if (spc_switch("SPC_CONV_FAST", 1) != 0 && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
                 double sumf = 0.0;                      // the denominator the general kernel accumulates: float32 taps
                 for (int i = 0; i < nky * nkx; ++i) sumf += (double)(float)h_kernel[i];
                 A.inv_ksum = (float)(1.0 / sumf);
@@ -533,8 +531,10 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     // a mask ARRAY (and nothing but the array / isfinite) with a kernel of up to 29 non-negative taps: the split form on the
     // matrix cores first (spc_spatial_split.hip); whatever it does not take stays with the ring kernels below
     if (mask && (mask->flags & SPC_MASK_ARRAY) && !(mask->flags & ~(uint32_t)(SPC_MASK_ARRAY | SPC_MASK_FINITE)) && std::max(nky, nkx) <= 65 && d_out) {
-        const char* ring = getenv("SPC_SPATIAL_RING");
-        if (!(ring && atoi(ring) == 1)) {
+        // the calling thread's setting first (spc_set_masked_spatial_form); the environment only where it has none
+        const int form = spc_get_masked_spatial_form();
+        const bool ring = form == SPC_SPATIAL_FORM_ENV ? spc_switch("SPC_SPATIAL_RING", 0) == 1 : form == SPC_SPATIAL_FORM_RING;
+        if (!ring) {
             rc = spc_spatial_conv_split_store(device, stream, cube, mask, h_ky, nky, h_kx, nkx, d_out, out_row_stride, out_plane_stride);
             if (rc != SPC_ERR_UNSUPPORTED) return rc;
         }
@@ -608,8 +608,7 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     // speculative all-valid fast pass: 8-byte aligned rows, a mask that rejects exactly the
     // non-finite samples (none / isfinite), whole columns per block
-    const char* env = getenv("SPC_CONV_FAST");
-    const bool want = env ? atoi(env) != 0 : true;
+    const bool want = spc_switch("SPC_CONV_FAST", 1) != 0;
     const bool al = (cube->nx % 2 == 0) && (cube->row_stride % 2 == 0) && (cube->plane_stride % 2 == 0) &&
                     (((uintptr_t)cube->d_data) % 8 == 0) && (A.out_row_stride % 4 == 0) &&
                     (A.out_plane_stride % 4 == 0) && (((uintptr_t)d_out) % 16 == 0);
@@ -619,7 +618,7 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     // cancel to den == 0 over a valid centre, and then astropy's filled-centre rule needs the lookup
     A.centre_zero = (A.ky[R / 2] * A.kx[R / 2] == 0.f) ? 1 : 0;
     for (int i = 0; i < R; ++i) if (A.ky[i] < 0.f || A.kx[i] < 0.f) A.centre_zero = 1;
-    { const char* xe = getenv("SPC_XCD_SWIZZLE"); A.xcd_swizzle = xe ? (atoi(xe) != 0) : 1; }
+    A.xcd_swizzle = spc_switch("SPC_XCD_SWIZZLE", 1) != 0;
     canonical_pred(A);
     // (the 49- and 65-tap rings - 35 to 65 taps - have an all-valid kernel for isotropic kernels only: two sets of
     // that many weights do not fit the SGPR file)

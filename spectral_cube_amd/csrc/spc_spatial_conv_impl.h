@@ -765,8 +765,7 @@ int launch_sep(const SpArgs& A, hipStream_t st, dim3 grid, bool arr) {
     // non-isotropic kernels only come in the PRED flavour (a superset: absent bounds are NaN)
 #ifdef SPC_ABLATE
     if constexpr (R == 29) {
-        const char* ab = getenv("SPC_SPATIAL_ABLATE");
-        const int abl = ab ? atoi(ab) : 0;
+        const int abl = spc_switch("SPC_SPATIAL_ABLATE", 0);
         if (abl && iso && !pred && arr) {
             switch (abl) {
                 case 1: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 1>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
@@ -787,11 +786,10 @@ int launch_sep(const SpArgs& A, hipStream_t st, dim3 grid, bool arr) {
 #endif
     if constexpr (R == 29) {
         // grouped pipeline; planes of 2 GiB and more keep the round-2 kernel
-        const char* gk = getenv("SPC_SPATIAL_GROUPED");
         // 0: round-2 kernel, 256 / 512: threads per block.  Measured at 512 x 2048^2 with a uint8 mask (same box): round-2
         // kernel 9.01 ms, 256 threads 8.29 ms, 512 threads 8.76 ms (less halo and fewer idle x-pass lanes, but barriers
         // over 8 waves and two blocks per CU)
-        const int want = gk ? atoi(gk) : 256;
+        const int want = spc_switch("SPC_SPATIAL_GROUPED", 256);
         // (byte offsets inside a plane stay below 2 GiB, like the spectral kernels: larger planes keep 64-bit addressing)
         const bool fits = (uint64_t)A.plane_stride * 4 < (1ull << 31) && (uint64_t)A.out_plane_stride * 4 < (1ull << 31) &&
                           (!arr || (uint64_t)A.mask.plane_stride < (1ull << 31));

@@ -759,8 +759,7 @@ __global__ __launch_bounds__(256) void spatial_moment_finish_kernel(const float*
 }
 
 inline bool use_form2(const spc_cube_f32* cube, const MaskDev& md) {
-    const char* env = getenv("SPC_SPATIAL_MFMA_FORM");
-    if (env && atoi(env) == 1) return false;
+    if (spc_switch("SPC_SPATIAL_MFMA_FORM", 3) == 1) return false;
     if ((cube->nx & 15) || (cube->row_stride & 3) || (cube->plane_stride & 3) || (((uintptr_t)cube->d_data) & 15)) return false;
     if ((md.flags & SPC_MASK_ARRAY) && (md.row_stride != cube->row_stride || md.plane_stride != cube->plane_stride || (((uintptr_t)md.arr) & 3))) return false;
     return true;
@@ -806,7 +805,7 @@ static int mfma_entry(int device, void* stream, const spc_cube_f32* cube, const 
     rc = spc_mask_to_dev(mask, cube, &md);
     if (rc) return rc;
 #define SPC_UNSUPPORTED(...) do { spc_set_error(__VA_ARGS__); return SPC_ERR_UNSUPPORTED; } while (0)
-    const int form = [] { const char* e = getenv("SPC_SPATIAL_MFMA_FORM"); return e ? atoi(e) : 3; }();
+    const int form = spc_switch("SPC_SPATIAL_MFMA_FORM", 3);
     const int nsum = (d_m1 || d_m2) ? 3 : (d_m0 ? 1 : 0);
     // ---- the split form (round 5) first: up to 33 taps per axis (three 16-wide Toeplitz blocks cover offsets of -16 .. 16), or up
     // to 65 (five blocks: half the output columns per wave)
@@ -947,8 +946,8 @@ extern "C" int spc_spatial_conv_sep_mfma_moments_f32(int device, void* stream, c
 // goes on with the ring kernel.
 int spc_spatial_conv_split_store(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, const double* h_ky, int nky,
                                  const double* h_kx, int nkx, float* d_out, int64_t out_row_stride, int64_t out_plane_stride) {
-    const char* e = getenv("SPC_SPATIAL_MFMA_FORM");
-    if (e && atoi(e) != 3 && atoi(e) != 0) { spc_set_error("split form switched off"); return SPC_ERR_UNSUPPORTED; }
+    const int form = spc_switch("SPC_SPATIAL_MFMA_FORM", 3);
+    if (form != 3 && form != 0) { spc_set_error("split form switched off"); return SPC_ERR_UNSUPPORTED; }
     return mfma_entry(device, stream, cube, mask, h_ky, nky, h_kx, nkx, d_out, out_row_stride, out_plane_stride, 0.0, nullptr, 0, nullptr, 0,
                       nullptr, 0.0, nullptr, nullptr, true);
 }

@@ -323,8 +323,7 @@ __global__ __launch_bounds__(256) void moment_weights_kernel(const double* cen, 
 // d_status (one byte per 128 columns) and d_w (3 nz doubles) come out of the caller's workspace
 int try_weighted_moments(ConvArgs& A, const spc_cube_f32* cube, const double* h_kernel, int ntaps,
                          hipStream_t st, unsigned char* d_status, double* d_w) {
-    const char* env = getenv("SPC_FUSE_ALGEBRAIC");
-    if (env && atoi(env) == 0) return 0;
+    if (spc_switch("SPC_FUSE_ALGEBRAIC", 1) == 0) return 0;
     const bool ext = A.mo.d_argmax || A.mo.d_argmin || A.mo.d_vmax || A.mo.d_vmin;
     const bool al = (cube->nx % 4 == 0) && (cube->row_stride % 4 == 0) && (cube->plane_stride % 4 == 0) &&
                     ((((uintptr_t)cube->d_data) & 15) == 0);
@@ -339,7 +338,7 @@ int try_weighted_moments(ConvArgs& A, const spc_cube_f32* cube, const double* h_
     WmArgs W{};
     W.cube = A.cube; W.nz = A.nz; W.ny = A.ny; W.nx = A.nx; W.row_stride = A.row_stride; W.plane_stride = A.plane_stride;
     W.w = d_w; W.dv = A.dv; W.m1_add = A.m1_add; W.mo = A.mo; W.mo_row_stride = A.mo_row_stride; W.status = d_status;
-    static const int wm_u = [] { const char* e = getenv("SPC_WMOM_U"); return e ? atoi(e) : 8; }();      // tuning hook
+    static const int wm_u = spc_switch("SPC_WMOM_U", 8);      // tuning hook
     if (wm_u == 4) hipLaunchKernelGGL(weighted_moments_kernel<4>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
     else hipLaunchKernelGGL(weighted_moments_kernel<8>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
     A.status = d_status;
@@ -360,8 +359,7 @@ int launch_ring_raw(int R, const ConvArgs& A, hipStream_t st, int fast, bool fus
 // (all-valid fast kernel, vec spaxels per lane), then redo only the dirty tiles.  d_status: one byte
 // per 128 columns from the caller's workspace.
 int launch_ring(int R, ConvArgs& A, hipStream_t st, int vec, bool fuse, unsigned char* d_status) {
-    const char* env = getenv("SPC_CONV_FAST");
-    const bool want = env ? atoi(env) != 0 : true;
+    const bool want = spc_switch("SPC_CONV_FAST", 1) != 0;
     const bool fast = want && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0 && A.zchunk >= A.nz;
     A.status = nullptr;
     if (!fast) return launch_ring_raw(R, A, st, 0, fuse);
@@ -373,8 +371,7 @@ int launch_ring(int R, ConvArgs& A, hipStream_t st, int vec, bool fuse, unsigned
 
 // two spaxels per lane need 8-byte aligned rows everywhere (SPC_CONV_VEC=1 forces one)
 int pick_vec(const spc_cube_f32* c, const MaskDev& m, const float* out, int64_t out_row, int64_t out_plane) {
-    const char* env = getenv("SPC_CONV_VEC");
-    if (env && atoi(env) == 1) return 1;
+    if (spc_switch("SPC_CONV_VEC", 0) == 1) return 1;
     bool ok = (c->nx % 2 == 0) && (c->row_stride % 2 == 0) && (c->plane_stride % 2 == 0) &&
               (((uintptr_t)c->d_data) % 8 == 0);
     if (m.flags & SPC_MASK_ARRAY)
@@ -445,7 +442,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         nsplit = std::max(nsplit, 1);
     }
     A.zchunk = (cube->nz + nsplit - 1) / nsplit;
-    { const char* sd = getenv("SPC_SPECTRAL_SKIP_DEAD"); A.skip_dead = sd ? atoi(sd) : 1; }
+    A.skip_dead = spc_switch("SPC_SPECTRAL_SKIP_DEAD", 1);
     nsplit = (int)((cube->nz + A.zchunk - 1) / A.zchunk);
     dim3 grid((unsigned)nblocks, (unsigned)nsplit);
     hipStream_t st = (hipStream_t)stream;
@@ -456,8 +453,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
     }
     // no ring for this kernel: runs-of-16 kernel for 17 taps or more, per-output tap loop below that
     // (taps in the workspace, written there by kernel-argument uploads: nothing waits)
-    const char* wenv = getenv("SPC_CONV_WIDE");
-    const bool wide = (wenv ? atoi(wenv) != 0 : true) && ntaps >= 17;
+    const bool wide = spc_switch("SPC_CONV_WIDE", 1) != 0 && ntaps >= 17;
     const int npad = wide ? ntaps + 30 : ntaps;
     std::vector<double> hk((size_t)npad, 0.0);
     for (int i = 0; i < ntaps; ++i) hk[(wide ? 15 : 0) + i] = h_kernel[i];
@@ -471,8 +467,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         bool sym = (ntaps & 1) && ntaps <= 65 && h_kernel[ntaps / 2] != 0.0;
         for (int i = 0; sym && i < ntaps / 2; ++i) sym = h_kernel[i] == h_kernel[ntaps - 1 - i];
         const bool fits = wide && sym && ring_fits(Rf, cube, mask, A.out_row_stride, A.out_plane_stride);
-        const char* fenv = getenv("SPC_CONV_FAST");
-        if (fits && (fenv ? atoi(fenv) != 0 : true) && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
+        if (fits && spc_switch("SPC_CONV_FAST", 1) != 0 && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
             rc = fill_common(A, cube, mask, h_kernel, ntaps, Rf);            // taps centred in the ring, kernel sum
             if (rc) return rc;
             SPC_WS_TAKE(d_status, ws, unsigned char, (ncols + 127) / 128);
@@ -488,8 +483,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         // non-negative taps (an empty window then means an invalid centre sample: NaN, which is what 0 / 0 gives)
         bool nonneg = true;
         for (int i = 0; i < ntaps; ++i) nonneg = nonneg && h_kernel[i] >= 0.0;
-        const char* renv = getenv("SPC_SPECTRAL_RING_WIDE");
-        if (fits && nonneg && (renv ? atoi(renv) != 0 : true)) {
+        if (fits && nonneg && spc_switch("SPC_SPECTRAL_RING_WIDE", 1) != 0) {
             unsigned char* keep_status = A.status;
             rc = fill_common(A, cube, mask, h_kernel, ntaps, Rf);
             if (rc) return rc;
@@ -503,18 +497,15 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         dim3 wgrid((unsigned)nblocks, (unsigned)((cube->nz + A.zchunk - 1) / A.zchunk));
         // no ring pass ran (asymmetric kernel or more than 65 taps) and the mask only rejects non-finite samples: the
         // numerator-only form first
-        {
-            const char* fenv = getenv("SPC_CONV_FAST");
-            if (!A.status && (fenv ? atoi(fenv) != 0 : true) && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
-                SPC_WS_TAKE(d_status, ws, unsigned char, (ncols + 127) / 128);
-                SPC_HIP(spc_flags_clear(d_status, (size_t)((ncols + 127) / 128), st));
-                A.status = d_status;
-                double ks = 0.0;
-                for (int i = 0; i < ntaps; ++i) ks += h_kernel[i];
-                A.ksum = ks;
-                hipLaunchKernelGGL((spectral_conv_wide_kernel<false, true>), wgrid, dim3(256), 0, st, A, d_k, ntaps);
-                SPC_LAUNCH_CHECK();
-            }
+        if (!A.status && spc_switch("SPC_CONV_FAST", 1) != 0 && (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) == 0) {
+            SPC_WS_TAKE(d_status, ws, unsigned char, (ncols + 127) / 128);
+            SPC_HIP(spc_flags_clear(d_status, (size_t)((ncols + 127) / 128), st));
+            A.status = d_status;
+            double ks = 0.0;
+            for (int i = 0; i < ntaps; ++i) ks += h_kernel[i];
+            A.ksum = ks;
+            hipLaunchKernelGGL((spectral_conv_wide_kernel<false, true>), wgrid, dim3(256), 0, st, A, d_k, ntaps);
+            SPC_LAUNCH_CHECK();
         }
         if (A.mask.flags & SPC_MASK_ARRAY) hipLaunchKernelGGL((spectral_conv_wide_kernel<true, false>), wgrid, dim3(256), 0, st, A, d_k, ntaps);
         else hipLaunchKernelGGL((spectral_conv_wide_kernel<false, false>), wgrid, dim3(256), 0, st, A, d_k, ntaps);
@@ -572,7 +563,7 @@ int spc_spectral_conv_moments_f32(int device, void* stream, const spc_cube_f32* 
         if (worst <= 1e-13 * std::max(span, 1e-300)) { A.cen_linear = 1; A.cen_c0 = c0; A.cen_dc = dc; }
     }
     A.zchunk = cube->nz;
-    { const char* sd = getenv("SPC_SPECTRAL_SKIP_DEAD"); A.skip_dead = sd ? atoi(sd) : 1; }
+    A.skip_dead = spc_switch("SPC_SPECTRAL_SKIP_DEAD", 1);
     const int vec = pick_vec(cube, A.mask, nullptr, 0, 0);
     if (try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w)) {
         SPC_LAUNCH_CHECK();

@@ -715,8 +715,7 @@ __global__ __launch_bounds__(256) void stats_finish_kernel(const double* partial
 }
 
 int env_blocks() {
-    const char* e = getenv("SPC_STATS_BLOCKS");              // tuning hook; 2048 = 8 blocks per CU
-    const int v = e ? atoi(e) : 2048;
+    const int v = spc_switch("SPC_STATS_BLOCKS", 2048);      // tuning hook; 2048 = 8 blocks per CU
     return v > 0 ? std::min(v, 4095) : 2048;                 // (the workspace holds 4096 records: one is the finished one)
 }
 
@@ -942,7 +941,7 @@ int spc_map_conv2d_f64(int device, void* stream, const double* d_in, int64_t ny,
     SPC_WS_TAKE(d_k, ws, double, k.size());
     SPC_HIP(spc_table_upload(d_k, k.data(), sizeof(double) * k.size(), st));
     // an outer product of at most 33 x 33 taps (the centre row and column reproduce every tap to 1e-14 of the largest): two 1-D passes
-    if (nky <= kMsMaxK && nkx <= kMsMaxK && nky * nkx >= nky + nkx && getenv("SPC_MAP_CONV_DIRECT") == nullptr) {
+    if (nky <= kMsMaxK && nkx <= kMsMaxK && nky * nkx >= nky + nkx && spc_switch("SPC_MAP_CONV_DIRECT", -1) == -1) {
         const int hy = nky / 2, hx = nkx / 2;
         const double c = k[(size_t)hy * nkx + hx];
         double kmax = 0.0, dev = 0.0;

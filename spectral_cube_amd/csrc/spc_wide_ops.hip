@@ -1509,13 +1509,13 @@ static int sort64_launch(Sort64Args& A, const spc_cube_f64* cube, bool clip, hip
     int nzp = 2;
     while (nzp < cube->nz) nzp <<= 1;
     // (SPC_SELECT64: 0 = the order statistics from sorted rays as in round 5; the clip loop always sorts)
-    static const bool radix = [] { const char* e = getenv("SPC_SELECT64"); return e ? atoi(e) != 0 : true; }();
+    static const bool radix = spc_switch("SPC_SELECT64", 1) != 0;
     const bool sel = !clip && radix;
     A.nzp = nzp; A.ts = sel ? std::min(kSelRays64, kSelKeys64 / nzp) : std::min(64, kSortKeys / nzp);
     const int64_t nb = ((cube->nx + A.ts - 1) / A.ts) * cube->ny;
     SPC_REQUIRE(nb < (1LL << 31), "map too large for one launch");
     // (SPC_SELECT64 = 2, the default: rays of up to 1024 samples keep their keys in registers; 1: the keys in LDS for every length)
-    static const int radix_form = [] { const char* e = getenv("SPC_SELECT64"); return e ? atoi(e) : 2; }();
+    static const int radix_form = spc_switch("SPC_SELECT64", 2);
     if (clip && radix_form >= 2 && cube->nz <= 1024 && !A.spread_mad) {      // (stdfunc = mad_std: a second descent over |x - median| - the sorted form below)
         const int64_t nbr = ((cube->nx + 15) / 16) * cube->ny;
         SPC_REQUIRE(nbr < (1LL << 31), "map too large for one launch");
@@ -1723,7 +1723,7 @@ int spc_spectral_conv_f64(int device, void* stream, const spc_cube_f64* cube, co
     A.out_plane_stride = out_plane_stride ? out_plane_stride : cube->ny * A.out_row_stride;
     A.gate = nullptr;
     // up to 33 taps, none negative, centre positive: the ring form (SPC_SPECTRAL64_RING=0: the runs of 16)
-    const bool ring_on = [] { const char* e = getenv("SPC_SPECTRAL64_RING"); return e ? atoi(e) != 0 : true; }();      // (read per call: the tests compare both forms in one process)
+    const bool ring_on = spc_switch("SPC_SPECTRAL64_RING", 1) != 0;      // (read per call: the tests compare both forms in one process)
     bool ring = ring_on && ntaps <= 33 && h_kernel[ntaps / 2] > 0.0;
     for (int i = 0; ring && i < ntaps; ++i) ring = h_kernel[i] >= 0.0;
     if (ring) {
@@ -1804,7 +1804,7 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
     }
     // symmetric factors of up to 33 taps, none negative, centre taps positive: the one-kernel ring form (SPC_SPATIAL64_RING=0: the
     // two-pass forms)
-    const bool ring_on = [] { const char* e = getenv("SPC_SPATIAL64_RING"); return e ? atoi(e) != 0 : true; }();     // (read per call: the tests compare both forms in one process)
+    const bool ring_on = spc_switch("SPC_SPATIAL64_RING", 1) != 0;     // (read per call: the tests compare both forms in one process)
     bool ring = ring_on && nky <= 33 && nkx <= 33 && h_ky[nky / 2] > 0.0 && h_kx[nkx / 2] > 0.0;
     for (int i = 0; ring && i < nky / 2; ++i) ring = h_ky[i] == h_ky[nky - 1 - i] && h_ky[i] >= 0.0;
     for (int i = 0; ring && i < nkx / 2; ++i) ring = h_kx[i] == h_kx[nkx - 1 - i] && h_kx[i] >= 0.0;
@@ -1831,7 +1831,7 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
     for (int64_t z0 = 0; z0 < cube->nz; z0 += planes) {
         A.z0 = z0;
         const unsigned gz = (unsigned)std::min<int64_t>(planes, cube->nz - z0);
-        static const int tiled = [] { const char* e = getenv("SPC_SPATIAL64_LDS"); return e ? atoi(e) : 2; }();
+        static const int tiled = spc_switch("SPC_SPATIAL64_LDS", 2);
         // (SPC_SPATIAL64_LDS: 0 = the untiled passes, 1 = LDS tiles with one output per thread (round 5), 2 = four outputs per thread)
         rc = over_rows([&](unsigned gy) {
             if (tiled == 2 && nkx / 2 <= kSpX4Halo)

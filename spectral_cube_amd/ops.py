@@ -646,7 +646,7 @@ def separable_factors(kernel2d, rtol=1e-12):
 
 
 MASKED_SPATIAL_ARITHMETIC = ("f16-split", "f32")
-_arith_lock = threading.Lock()
+_SPATIAL_FORM = {"f16-split": _lib.SPATIAL_FORM_SPLIT, "f32": _lib.SPATIAL_FORM_RING}
 
 
 class masked_spatial_arithmetic:
@@ -654,7 +654,8 @@ class masked_spatial_arithmetic:
     policy): "f16-split" (default) = every product on the fp16 matrix instruction with the samples, the taps and the x-pass
     result split hi + lo, float32 accumulation - 1e-6 of the data range against astropy's float64, inside the 1e-5 contract;
     "f32" = the ring kernels, float32 multiply-adds on the vector ALU - 2.5e-7 of the range, 1.2 - 1.5 x the time.
-    (The library reads SPC_SPATIAL_RING per call; this sets it for the calls made inside the scope, one scope at a time.)"""
+    A setting of the calling thread (spc_set_masked_spatial_form): it holds for the library calls this thread makes inside
+    the scope, wins over SPC_SPATIAL_RING in the environment, nests, and no other thread sees it."""
 
     def __init__(self, name):
         if name is not None and name not in MASKED_SPATIAL_ARITHMETIC:
@@ -662,21 +663,13 @@ class masked_spatial_arithmetic:
         self.name = name
 
     def __enter__(self):
-        if self.name is None:
-            return self
-        _arith_lock.acquire()
-        self._old = os.environ.get("SPC_SPATIAL_RING")
-        os.environ["SPC_SPATIAL_RING"] = "1" if self.name == "f32" else "0"
+        if self.name is not None:
+            self._old = _lib.load().spc_set_masked_spatial_form(_SPATIAL_FORM[self.name])
         return self
 
     def __exit__(self, *exc):
-        if self.name is None:
-            return False
-        if self._old is None:
-            os.environ.pop("SPC_SPATIAL_RING", None)
-        else:
-            os.environ["SPC_SPATIAL_RING"] = self._old
-        _arith_lock.release()
+        if self.name is not None:
+            _lib.load().spc_set_masked_spatial_form(self._old)
         return False
 
 

@@ -28,6 +28,7 @@ int main(int argc, char** argv) {
     void* lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
     if (!lib) { fprintf(stderr, "dlopen failed: %s\n", dlerror()); return 2; }
     SYM(spc_abi_version); SYM(spc_last_error); SYM(spc_device_count); SYM(spc_get_device_info);
+    SYM(spc_set_masked_spatial_form); SYM(spc_get_masked_spatial_form);
     SYM(spc_malloc); SYM(spc_free); SYM(spc_host_alloc); SYM(spc_host_free);
     SYM(spc_memcpy_h2d); SYM(spc_memcpy_d2h); SYM(spc_memcpy_d2d); SYM(spc_memcpy3d_h2d); SYM(spc_memcpy3d_d2d); SYM(spc_memset);
     SYM(spc_stream_create); SYM(spc_stream_destroy); SYM(spc_stream_sync); SYM(spc_device_sync);

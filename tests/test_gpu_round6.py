@@ -407,3 +407,94 @@ def test_cube_level_arithmetic_of_the_masked_spatial_stencil_is_selectable(gpu, 
     e0[~m.any(axis=0)] = np.nan
     assert not called
     assert_close(m0, e0, atol=1e-5 * np.nanmax(np.abs(e0)), what="moment0 of the float32-arithmetic smooth")
+
+
+# ---- the arithmetic of the masked spatial stencil as a setting of the calling thread (spc_set_masked_spatial_form behind
+# ops.masked_spatial_arithmetic): the same bits as the environment switch it replaces in the Python layer, ahead of that
+# switch, and invisible to other threads.  One cube for all: more than one 96-column tile and more than one 16-row band of
+# the split form; what the two forms give for it is computed once, by plain calls steered through the environment
+@pytest.fixture(scope="module")
+def forms(gpu):
+    d, m = _case((3, 40, 200), 41, valid=0.8)
+    cube, mk = _dev(d, m)
+    spec = ops.MaskSpec(_lib.MASK_ARRAY, array=mk)
+    kernels = {9: Gaussian2DKernel(1.0).array, 29: K8}
+    ref = {}
+    with pytest.MonkeyPatch.context() as mp:
+        mp.delenv("SPC_SPATIAL_RING", raising=False)
+        for n, k in kernels.items():
+            ref["split", n] = ops.spatial_conv(cube, k, mask=spec).get()
+        mp.setenv("SPC_SPATIAL_RING", "1")
+        for n, k in kernels.items():
+            ref["ring", n] = ops.spatial_conv(cube, k, mask=spec).get()
+    for n, k in kernels.items():
+        assert k.shape == (n, n) and (k >= 0).all()
+        exp = O.spatial_smooth(d, m, k)
+        for form in ("split", "ring"):
+            assert_close(ref[form, n], exp.astype(np.float32), atol=1e-5 * np.nanmax(np.abs(exp)), what="%s form, %d taps" % (form, n))
+        assert not np.array_equal(ref["split", n], ref["ring", n], equal_nan=True), "both forms took the same kernel (%d taps)" % n
+    return cube, spec, kernels, ref
+
+
+def _same_bits(got, exp):
+    return np.array_equal(got, exp, equal_nan=True)
+
+
+def test_arithmetic_scope_gives_the_bits_of_the_environment_switch(forms, monkeypatch):
+    cube, spec, kernels, ref = forms
+    monkeypatch.delenv("SPC_SPATIAL_RING", raising=False)
+    for n, k in kernels.items():
+        with ops.masked_spatial_arithmetic("f32"):
+            got = ops.spatial_conv(cube, k, mask=spec).get()
+        assert _same_bits(got, ref["ring", n]), n
+        with ops.masked_spatial_arithmetic("f16-split"):
+            got = ops.spatial_conv(cube, k, mask=spec).get()
+        assert _same_bits(got, ref["split", n]), n
+        got = ops.spatial_conv(cube, k, mask=spec, arithmetic="f32").get()          # the argument goes through the scope
+        assert _same_bits(got, ref["ring", n]), n
+
+
+def test_arithmetic_scope_wins_over_the_environment_switch(forms, monkeypatch):
+    cube, spec, kernels, ref = forms
+    for n, k in kernels.items():
+        monkeypatch.setenv("SPC_SPATIAL_RING", "1")
+        with ops.masked_spatial_arithmetic("f16-split"):
+            got = ops.spatial_conv(cube, k, mask=spec).get()
+        assert _same_bits(got, ref["split", n]), n
+        monkeypatch.setenv("SPC_SPATIAL_RING", "0")
+        with ops.masked_spatial_arithmetic("f32"):
+            got = ops.spatial_conv(cube, k, mask=spec).get()
+        assert _same_bits(got, ref["ring", n]), n
+
+
+def test_arithmetic_scope_does_not_leak_into_another_thread(forms, monkeypatch):
+    """while this thread sits inside the "f32" scope, a second thread's plain call (its own stream) takes the default form;
+    the scope used to switch the whole process over, and to hold a lock against the other thread's own scope"""
+    import threading
+    from spectral_cube_amd.device import Stream
+    cube, spec, kernels, ref = forms
+    monkeypatch.delenv("SPC_SPATIAL_RING", raising=False)
+    box = {}
+
+    def other():
+        try:
+            s = Stream()
+            for n, k in kernels.items():
+                box["plain", n] = ops.spatial_conv(cube, k, mask=spec, stream=s).get(stream=s)
+            with ops.masked_spatial_arithmetic("f16-split"):                          # (a scope of its own does not wait for ours)
+                box["scoped", 29] = ops.spatial_conv(cube, kernels[29], mask=spec, stream=s).get(stream=s)
+        except BaseException as exc:           # noqa: B902 - reported by the test's thread
+            box["error"] = exc
+
+    s = Stream()
+    with ops.masked_spatial_arithmetic("f32"):
+        t = threading.Thread(target=other, daemon=True)
+        t.start()
+        mine = {n: ops.spatial_conv(cube, k, mask=spec, stream=s).get(stream=s) for n, k in kernels.items()}
+        t.join(60.0)
+        assert not t.is_alive(), "the second thread did not finish"
+    assert "error" not in box, box.get("error")
+    for n in kernels:
+        assert _same_bits(box["plain", n], ref["split", n]), n
+        assert _same_bits(mine[n], ref["ring", n]), n
+    assert _same_bits(box["scoped", 29], ref["split", 29])
