@@ -550,6 +550,40 @@ int spc_stack_cube_f64(int device, void* stream, const spc_cube_f64* cube, const
                        int nsrc, const int32_t* h_lo, const double* h_t, const double* h_inv_dx, const int32_t* h_exact, int mode,
                        int64_t n0, double* d_out, void* d_workspace, size_t workspace_bytes);
 
+/* ---- mosaic_cubes: many cubes reprojected onto one sky grid and averaged where they overlap, in one pass ----
+ * spectral_cube.cube_utils: mosaic_cubes (cube_utils.py:810-856): per cube, in list order, SpectralCube.reproject onto the
+ * common header (:826-836; reproject_interp of the FILLED data, order 0 | 1), weight += the 2-D footprint (:839-840),
+ * final += nan_to_num(filled data of the reprojected cube) in float64 (:843-845; NaN -> 0, +-inf -> +-DBL_MAX, and the
+ * cube's fill value outside its footprint), then final /= weight (:848-852; 0 / 0 = NaN where no cube reaches).
+ * One kernel: no reprojected cube is written, every output value is stored once, by the one lane that owns it (no atomics:
+ * two runs agree bit for bit).  The value a source gives at an output voxel has the bits of spc_resample_bilinear_f32 / _f64
+ * with the same mask, fill, maps and order; the sum and the division run in float64, rounded once at the store.
+ * h_sources: a HOST table of nsrc descriptors (any nsrc >= 1: it travels as kernel arguments into d_workspace,
+ * spc_mosaic_workspace_bytes, and may be freed when the call returns).  Per source: the cube view (nz channels, like the
+ * output), its mask (flags = 0: none) and fill value, and its float64 (ny_out, nx_out) DEVICE maps d_xs / d_ys of source pixel
+ * coordinates (spc_wcs_pixel_map_f64; -1e30 or a non-finite entry = not on the source).  d_out: (nz, ny_out, nx_out),
+ * C-contiguous, the cubes' type.  d_weight: optional int32 (ny_out, nx_out), the number of sources that reach each pixel.
+ * No limit on an axis or on nsrc. */
+typedef struct {
+    spc_cube_f32 cube;
+    spc_mask mask;
+    float fill;
+    const double* d_xs;
+    const double* d_ys;
+} spc_mosaic_source_f32;
+typedef struct {
+    spc_cube_f64 cube;
+    spc_mask_f64 mask;
+    double fill;
+    const double* d_xs;
+    const double* d_ys;
+} spc_mosaic_source_f64;
+size_t spc_mosaic_workspace_bytes(int nsrc);
+int spc_mosaic_f32(int device, void* stream, int nsrc, const spc_mosaic_source_f32* h_sources, int64_t nz, int64_t ny_out,
+                   int64_t nx_out, int order, float* d_out, int32_t* d_weight, void* d_workspace, size_t workspace_bytes);
+int spc_mosaic_f64(int device, void* stream, int nsrc, const spc_mosaic_source_f64* h_sources, int64_t nz, int64_t ny_out,
+                   int64_t nx_out, int order, double* d_out, int32_t* d_weight, void* d_workspace, size_t workspace_bytes);
+
 /* ---- cube arithmetic: + - * / ** with scalars, maps, spectra and cubes, a chain of them in one pass ----
  * SpectralCube.__add__ / __sub__ / __mul__ / __truediv__ / __pow__ (spectral_cube.py:2237-2361): _apply_everywhere
  * (:912-942, op(filled_data, value)) for a value that is not a cube, _cube_on_cube_operation (:944-1003, op of the raw

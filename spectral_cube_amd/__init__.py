@@ -20,3 +20,5 @@ from .kernels import (Gaussian1DKernel, Gaussian2DKernel, Box1DKernel, Tophat2DK
 from .wcs import SimpleWCS  # noqa: F401
 from . import analysis_utilities  # noqa: F401
 from .analysis_utilities import stack_spectra, stack_cube, BadVelocitiesWarning  # noqa: F401
+from . import cube_utils  # noqa: F401
+from .cube_utils import combine_headers, mosaic_cubes  # noqa: F401

@@ -104,6 +104,16 @@ class SpcCelestialWcs(C.Structure):
                 ("pv1", C.c_double), ("plane0", C.c_double * 2), ("sip_a", C.c_double * 55), ("sip_b", C.c_double * 55)]
 
 
+class SpcMosaicSource(C.Structure):
+    """spc_mosaic_source_f32: one cube of spc_mosaic_f32 with its mask, fill value and pixel maps"""
+    _fields_ = [("cube", SpcCube), ("mask", SpcMask), ("fill", C.c_float), ("d_xs", C.c_void_p), ("d_ys", C.c_void_p)]
+
+
+class SpcMosaicSource64(C.Structure):
+    """spc_mosaic_source_f64"""
+    _fields_ = [("cube", SpcCube), ("mask", SpcMask64), ("fill", C.c_double), ("d_xs", C.c_void_p), ("d_ys", C.c_void_p)]
+
+
 class SpcMaskSlot(C.Structure):
     _fields_ = [("d_data", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
 
@@ -236,6 +246,9 @@ SIGNATURES = {
     "spc_stack_cube_workspace_bytes": (_sz, [_i, _i64]),
     "spc_stack_cube_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _sz]),
     "spc_stack_cube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _sz]),
+    "spc_mosaic_workspace_bytes": (_sz, [_i]),
+    "spc_mosaic_f32": (_i, [_i, _vp, _i, _P(SpcMosaicSource), _i64, _i64, _i64, _i, _vp, _vp, _vp, _sz]),
+    "spc_mosaic_f64": (_i, [_i, _vp, _i, _P(SpcMosaicSource64), _i64, _i64, _i64, _i, _vp, _vp, _vp, _sz]),
     "spc_moments_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _d, _vp, _vp, _vp]),
     "spc_moment_order_spatial_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i, _vp, _vp]),
     "spc_spectral_conv_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _i, _vp, _i64, _i64, _vp, _sz]),

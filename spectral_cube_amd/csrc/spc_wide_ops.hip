@@ -888,7 +888,8 @@ __global__ __launch_bounds__(256) void bilinear64_kernel(const Bil64Args A) {
         anyv = anyv || (r == r);
         po[z * A.out_plane_stride] = r;
     }
-    if (A.any_valid && __any(anyv) && lane == 0) atomicOr(A.any_valid, 1u);
+    // (the lanes outside the output or the source have returned: the first lane still here reports, lane 0 may be gone)
+    if (A.any_valid && __any(anyv) && lane == __ffsll((long long)__ballot(1)) - 1) atomicOr(A.any_valid, 1u);
 }
 __global__ __launch_bounds__(256) void scale64_kernel(double* p, int64_t n, double f) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -489,6 +489,56 @@ def stack_cube(cube, lo, t, inv_dx, exact, mode="nanmean", fill=np.nan, mask=Non
     return out
 
 
+def mosaic(cubes, maps, masks, fills, order, weights=None, out=None, stream=None):
+    """(nz, ny_out, nx_out) DeviceArray in the cubes' dtype: the co-added mosaic of mosaic_cubes (cube_utils.py:810-856) in
+    one kernel.  *cubes*: S DeviceArrays of one dtype (float32 or float64) and one number of channels; *maps*: per cube its
+    ``(xs, ys)`` float64 (ny_out, nx_out) DeviceArrays of source pixel coordinates (``wcs_pixel_map``); *masks*: per cube a
+    MaskSpec or None; *fills*: per cube the fill value that replaces excluded voxels (and that the cube contributes outside
+    its footprint, NaN counting as 0).  *order*: 1 bilinear, 0 nearest neighbour.  Per output voxel: the float64 sum, in list
+    order, of nan_to_num of what ``resample_bilinear`` gives for each cube (the same bits), divided by the number of cubes
+    whose footprint holds the pixel (NaN where none does), rounded once.  *weights*: optional int32 (ny_out, nx_out)
+    DeviceArray that receives that number."""
+    cubes, maps = list(cubes), list(maps)
+    nsrc = len(cubes)
+    if nsrc < 1:
+        raise ValueError("an empty list of cubes")
+    masks = [None] * nsrc if masks is None else list(masks)
+    fills = list(fills)
+    if not (len(maps) == len(masks) == len(fills) == nsrc):
+        raise ValueError("cubes, maps, masks and fills must have one entry per cube")
+    if int(order) not in (0, 1):
+        raise ValueError("order must be 1 (bilinear) or 0 (nearest neighbour), got %r" % (order,))
+    first = cubes[0]
+    name, dtype = _entry("mosaic", first)
+    dev, nz = first.device, first.shape[0]
+    shape_yx = tuple(maps[0][0].shape)
+    wide = dtype == _F64
+    tab = ((_lib.SpcMosaicSource64 if wide else _lib.SpcMosaicSource) * nsrc)()
+    for s, (cube, (xs, ys), mask, fill) in enumerate(zip(cubes, maps, masks, fills)):
+        if cube.dtype != dtype or len(cube.shape) != 3 or cube.shape[0] != nz:
+            raise TypeError("every cube must be a %s DeviceArray with %d channels (cube %d: %s %s)"
+                            % (dtype.name, nz, s, cube.dtype, cube.shape))
+        for m in (xs, ys):
+            if not isinstance(m, DeviceArray) or m.dtype != np.float64 or tuple(m.shape) != shape_yx or len(shape_yx) != 2:
+                raise ValueError("maps must be pairs of float64 DeviceArrays of one (ny_out, nx_out) shape (cube %d)" % s)
+        tab[s].cube, tab[s].mask = _cube_c(cube), _mask_c(mask, cube)
+        tab[s].fill = float(fill)
+        tab[s].d_xs, tab[s].d_ys = xs.ptr, ys.ptr
+    shape = (nz,) + shape_yx
+    if out is None:
+        out = DeviceArray(shape, dtype, dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or getattr(out, "_is_view", False):
+        raise ValueError("preallocated output must be a contiguous %s %s" % (shape, dtype))
+    if weights is not None and (tuple(weights.shape) != shape_yx or weights.dtype != np.int32):
+        raise ValueError("weights must be an int32 %s DeviceArray" % (shape_yx,))
+    ws = DeviceArray((int(_lib.load().spc_mosaic_workspace_bytes(nsrc)),), np.uint8, dev)
+    _lib.call(name, dev, _sh(stream), nsrc, tab, nz, shape_yx[0], shape_yx[1], int(order), C.c_void_p(out.ptr),
+              C.c_void_p(weights.ptr) if weights is not None else None, C.c_void_p(ws.ptr), ws.nbytes)
+    if stream is not None:                   # (the workspace goes back to the pool when this returns)
+        _lib.call("spc_stream_sync", dev, _sh(stream))
+    return out
+
+
 def normalize_view(view, shape):
     """(start, step, length) per axis of a tuple of three slices applied to *shape* (``slice.indices``, as numpy indexes)"""
     out = []
