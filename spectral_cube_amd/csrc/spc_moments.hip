@@ -9,7 +9,7 @@
 // Mapping: x is the fastest axis, so one lane owns VEC consecutive spaxels and
 // marches over z; a wave reads 64*VEC*4 B contiguous per plane (1 KiB for
 // VEC=4).  All sums are carried in fp64 registers (the reference computes in
-// fp64; one-pass moment 2 from raw sums needs it).  The cube is read exactly
+// fp64; one-pass moment 2 from raw sums needs it).  The cube is read at most
 // once: 4 B/voxel (+1 B/voxel with a uint8 mask array).
 //
 // Parallelism: blockDim = (64, ZW): the ZW waves of a block take interleaved
@@ -163,8 +163,14 @@ __device__ __forceinline__ unsigned vget(const uint16_t& v, int i) { return (v >
 __device__ __forceinline__ unsigned vget(const uint32_t& v, int i) { return (v >> (8 * i)) & 0xffu; }
 __device__ __forceinline__ unsigned vget(const unsigned char& v, int) { return v; }
 
-template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED>
+// MF (mask first; ARR and VEC = 4 only, SPC_MOMENTS_MASK_FIRST=0 turns it off): the mask dwords of a batch of U planes are
+// loaded one batch ahead, and a lane issues the 16-byte load of its four samples only where its mask dword is not zero; the
+// other lanes hold 0.f, which acc_add would have selected anyway (ok is false there whatever the sample is).  A 128-byte
+// line of the cube in which the mask includes nothing is then never requested.  Everything after the loads is the same
+// code in the same order, so the maps are bit-identical for every input, NaN and Inf under excluded voxels included.
+template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false>
 __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
+    static_assert(!MF || (ARR && VEC == 4), "mask-first is the 16-byte lane form with a mask array");
     using F = typename VecT<VEC>::F;
     using M = typename VecT<VEC>::M;
     const int lane = threadIdx.x;
@@ -201,44 +207,119 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     if (live) {
         int64_t z = zb + w;
         // main loop: U planes (stride ZW) in flight per lane
-        for (; z + (int64_t)(U - 1) * ZW < ze; z += (int64_t)U * ZW) {
-            F v[U];
-            M m[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t zz = z + (int64_t)u * ZW;
-                v[u] = __builtin_nontemporal_load(reinterpret_cast<const F*>(p + zz * A.plane_stride));
-                if (ARR) m[u] = __builtin_nontemporal_load(reinterpret_cast<const M*>(pm + zz * A.mask.plane_stride));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t zz = z + (int64_t)u * ZW;
-                const double c = cenp[zz];                       // uniform index: a scalar load
+        if constexpr (MF) {
+            // one plane of a lane: its VEC samples and mask bytes into the sums
+            auto add_plane = [&](const F& v, const M& m, int64_t zz) {
+                const double c = cenp[zz];                           // uniform index: a scalar load
                 const double c2 = c * c;
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
-                    const float val = vget(v[u], i);
+                    const float val = vget(v, i);
                     bool ok = mom_pred<PRED>(val, lim, lo, hi);
-                    if (ARR) ok = ok && (vget(m[u], i) != 0);
+                    if (ARR) ok = ok && (vget(m, i) != 0);
                     acc_add<EXT>(acc[i], val, ok, c, c2, (int)zz);
+                }
+            };
+            // two carried pointers, made opaque once per batch, and every address of a batch the one before plus the uniform
+            // plane step (left to itself the loop optimiser keeps 2 U pointers in registers: 124 VGPRs instead of 80)
+            const int64_t dstep = (int64_t)ZW * A.plane_stride, mstep = (int64_t)ZW * A.mask.plane_stride;
+            // (pointers to global memory by type: one that went through the asm statement as a plain pointer is loaded from with
+            //  flat_load, which also counts in lgkmcnt, where the scalar loads of the coordinates wait)
+            typedef const float __attribute__((address_space(1))) gfloat;
+            typedef const uint8_t __attribute__((address_space(1))) gbyte;
+            typedef const F __attribute__((address_space(1))) GF;
+            typedef const M __attribute__((address_space(1))) GM;
+            gfloat* pz = (gfloat*)(p + z * A.plane_stride);      // the samples of plane z ...
+            gbyte* qz = (gbyte*)(pm + z * A.mask.plane_stride);  // ... and the first mask that has not been asked for yet
+            bool more = z + (int64_t)(U - 1) * ZW < ze;
+            M m[U];                                              // the masks of the batch that starts at z
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u, qz += mstep) m[u] = __builtin_nontemporal_load((GM*)qz);
+            }
+            while (more) {
+                // every mask of the batch is waited for here, before the first load it decides: the loads of the samples then
+                // go out back to back (waited for one by one, the last mask would be waited for behind the samples already asked for)
+                M all = m[0];
+#pragma unroll
+                for (int u = 1; u < U; ++u) all |= m[u];
+                asm volatile("" : "+v"(pz), "+v"(qz) : "v"(all));
+                F v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u, pz += dstep) {
+                    v[u] = F{};
+                    if (m[u] != 0) v[u] = __builtin_nontemporal_load((GF*)pz);
+                }
+                more = z + (int64_t)(2 * U - 1) * ZW < ze;       // wave-uniform
+                // the next batch's mask of plane u goes out as soon as this batch's has been used, into the same register
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    add_plane(v[u], m[u], z + (int64_t)u * ZW);
+                    if (more) { m[u] = __builtin_nontemporal_load((GM*)qz); qz += mstep; }
+                }
+                z += (int64_t)U * ZW;
+            }
+            // tail
+            for (; z < ze; z += ZW, pz += dstep, qz += mstep) {
+                F v{};
+                const M mt = *(GM*)qz;
+                if (mt != 0) v = *(GF*)pz;
+                add_plane(v, mt, z);
+            }
+        } else {
+            for (; z + (int64_t)(U - 1) * ZW < ze; z += (int64_t)U * ZW) {
+                F v[U];
+                M m[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t zz = z + (int64_t)u * ZW;
+                    v[u] = __builtin_nontemporal_load(reinterpret_cast<const F*>(p + zz * A.plane_stride));
+                    if (ARR) m[u] = __builtin_nontemporal_load(reinterpret_cast<const M*>(pm + zz * A.mask.plane_stride));
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t zz = z + (int64_t)u * ZW;
+                    const double c = cenp[zz];                       // uniform index: a scalar load
+                    const double c2 = c * c;
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        const float val = vget(v[u], i);
+                        bool ok = mom_pred<PRED>(val, lim, lo, hi);
+                        if (ARR) ok = ok && (vget(m[u], i) != 0);
+                        acc_add<EXT>(acc[i], val, ok, c, c2, (int)zz);
+                    }
+                }
+            }
+            // tail
+            for (; z < ze; z += ZW) {
+                const F v = *reinterpret_cast<const F*>(p + z * A.plane_stride);
+                M m = 0;
+                if (ARR) m = *reinterpret_cast<const M*>(pm + z * A.mask.plane_stride);
+                const double c = cenp[z];
+                const double c2 = c * c;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const float val = vget(v, i);
+                    bool ok = mom_pred<PRED>(val, lim, lo, hi);
+                    if (ARR) ok = ok && (vget(m, i) != 0);
+                    acc_add<EXT>(acc[i], val, ok, c, c2, (int)z);
                 }
             }
         }
-        // tail
-        for (; z < ze; z += ZW) {
-            const F v = *reinterpret_cast<const F*>(p + z * A.plane_stride);
-            M m = 0;
-            if (ARR) m = *reinterpret_cast<const M*>(pm + z * A.mask.plane_stride);
-            const double c = cenp[z];
-            const double c2 = c * c;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float val = vget(v, i);
-                bool ok = mom_pred<PRED>(val, lim, lo, hi);
-                if (ARR) ok = ok && (vget(m, i) != 0);
-                acc_add<EXT>(acc[i], val, ok, c, c2, (int)z);
-            }
-        }
+    }
+    // where the lane's results go.  MF: worked out again from the lane number instead of being kept through the march: seven
+    // registers, which the march needs to stay at the waves per SIMD of the loop that loads everything (<4,4,8,sums>: 85 -> 79
+    // VGPRs, six waves)
+    int64_t og = g, oy = y, ox = x;
+    bool olive = live;
+    if constexpr (MF) {
+        int ln = threadIdx.x;
+        asm volatile("" : "+v"(ln));
+        og = blk * kLanes + ln;
+        olive = og < A.ngroups;
+        const int64_t ogg = olive ? og : 0;
+        oy = ogg / A.groups_per_row;
+        ox = (ogg - oy * A.groups_per_row) * VEC;
     }
     if (EXT < kCount) {
 #pragma unroll
@@ -278,12 +359,12 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
         }
     }
 
-    if (w == 0 && live) {
+    if (w == 0 && olive) {
         const int64_t ncols = A.ngroups * VEC;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-            if (A.nsplit == 1) finalize(A, acc[i], y, x + i);
-            else ws_store(A, acc[i], split, g * VEC + i, ncols);
+            if (A.nsplit == 1) finalize(A, acc[i], oy, ox + i);
+            else ws_store(A, acc[i], split, og * VEC + i, ncols);
         }
     }
 }
@@ -398,12 +479,20 @@ __global__ __launch_bounds__(256) void moment_order_v4_kernel(const OrdArgs A) {
     }
 }
 
-struct Plan { int vec, zw, u, nsplit; int64_t zchunk; };
+struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; };
 
 template <int VEC, int ZW, int U, bool ARR, int EXT>
-int launch_main(const MomArgs& A, hipStream_t st, bool thresholds) {
+int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first) {
     dim3 block(kLanes, ZW);
     dim3 grid((unsigned)((A.ngroups + kLanes - 1) / kLanes), (unsigned)A.nsplit);
+    if constexpr (ARR && VEC == 4) {
+        if (mask_first) {
+            if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true>), grid, block, 0, st, A);
+            else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true>), grid, block, 0, st, A);
+            SPC_LAUNCH_CHECK();
+            return SPC_OK;
+        }
+    }
     if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1>), grid, block, 0, st, A);
     else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0>), grid, block, 0, st, A);
     SPC_LAUNCH_CHECK();
@@ -411,23 +500,30 @@ int launch_main(const MomArgs& A, hipStream_t st, bool thresholds) {
 }
 
 // 16-byte lanes: ZW in {1, 4, 8}, U in {2, 4, 8}; the narrower lanes (odd nx, unaligned views): ZW in {1, 4}, U = 4
+// Mask-first forms (launch_main): their register counts rest on three things that a compiler change can undo - the empty asm
+// statements on the carried pointers and on the lane number, and the global address space of the pointers (see the kernel) -
+// so check -Rpass-analysis=kernel-resource-usage after one (profiles/moments_mask_first_bench.txt has the table: <4,4,8,sums,0>
+// 79 VGPRs, six waves per SIMD).  Two groups of mask-first forms hold a wave per SIMD fewer than the loop that loads everything
+// and are not what make_plan picks: U = 8 with extrema (all eight 16-byte loads stay live across the branches: 131 - 134 VGPRs;
+// make_plan takes U = 2 with extrema) and <4,1,8,count,0> (81 VGPRs; ZW = 1 is for cubes of fewer than 16 planes).  They are
+// reached through SPC_MOMENTS_U / SPC_MOMENTS_ZW only.
 template <bool ARR, int EXT>
 int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     if (p.vec == 4) {
         switch (p.zw * 16 + p.u) {
-            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr);
-            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr);
-            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr);
-            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr);
-            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr);
-            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr);
-            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr);
-            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr);
-            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr);
+            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first);
+            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
+            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first);
+            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first);
+            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first);
+            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first);
+            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first);
+            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first);
+            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first);
         }
     }
-    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr);
-    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr);
+    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
+    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
 }
 
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
@@ -446,6 +542,7 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     // MI355X sweeps at 1024^3 (tools/tune_moments.py; profiles/r01_tune_moments.log, r04_moments_issue.log)
     const bool arr_ = (m.flags & SPC_MASK_ARRAY) != 0;
     (void)arr_;
+    p.mask_first = spc_switch("SPC_MOMENTS_MASK_FIRST", 1) != 0;   // 0: the loop that loads every sample (16-byte lanes with a mask array)
     p.u = spc_switch("SPC_MOMENTS_U", ext ? 2 : 8);
     if (p.u != 2 && p.u != 4 && p.u != 8) p.u = 4;
     const int64_t ngroups = c->ny * (c->nx / p.vec);
