@@ -419,10 +419,10 @@ size_t spc_ws_spatial_conv_sep(int64_t nz, int64_t ny, int64_t nx, int64_t nky, 
     const int R = pick_ring((int)std::max(nky, nkx));
     if (R) {                                                    // tile flags of the speculative pass: strips x channels
         const int64_t nstrips = (nx + fast_txo(65) - 1) / fast_txo(65);      // the narrowest strips of any ring
-        return spc_ws_round((size_t)(nstrips * nz)) + 256;
+        return spc_ws_round((size_t)(nstrips * nz)) + spc_ws_round(sizeof(float) * (size_t)(nkx * (nky + 14))) + 512;   // (+ the taps of the per-output kernel)
     }
     const int64_t nyp = std::max<int64_t>(nky, 17);
-    return spc_ws_round(sizeof(float) * (size_t)(nyp + 30 + nkx)) +
+    return spc_ws_round(sizeof(float) * (size_t)(nkx * (nky + 14))) + spc_ws_round(sizeof(float) * (size_t)(nyp + 30 + nkx)) +
            spc_ws_round(sizeof(float2v) * (size_t)(wide_chunk_planes(nz, ny * nx) * ny * nx)) + 512;
 }
 
@@ -433,17 +433,18 @@ size_t spc_ws_spatial_conv2d(int64_t nz, int64_t ny, int64_t nx, int64_t nky, in
 
 extern "C" {
 
-int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
-                           const double* h_kernel, int nky, int nkx, float* d_out,
-                           int64_t out_row_stride, int64_t out_plane_stride, void* d_workspace, size_t workspace_bytes) {
+// allow_tiled = false: the per-output kernel whatever the size (it skips zero taps; see spc_spatial_conv_sep_f32)
+static int conv2d_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                      const double* h_kernel, int nky, int nkx, float* d_out,
+                      int64_t out_row_stride, int64_t out_plane_stride, void* d_workspace, size_t workspace_bytes, bool allow_tiled) {
     int rc = spc_check_cube(cube);
     if (rc) return rc;
     if ((rc = check_kernel(h_kernel, nky, "y")) || (rc = check_kernel(h_kernel, nkx, "x"))) return rc;
     if (cube->nz > 65535 && d_out)
         return over_plane_slabs(cube, mask, d_out, out_row_stride, out_plane_stride,
                                 [&](const spc_cube_f32* c, const spc_mask* m, float* o, int64_t ors, int64_t ops) {
-                                    return spc_spatial_conv2d_f32(device, stream, c, m, h_kernel, nky, nkx, o, ors, ops,
-                                                                  d_workspace, workspace_bytes);
+                                    return conv2d_f32(device, stream, c, m, h_kernel, nky, nkx, o, ors, ops,
+                                                      d_workspace, workspace_bytes, allow_tiled);
                                 });
     double sum = 0.0;
     for (int i = 0; i < nky * nkx; ++i) sum += h_kernel[i];
@@ -455,7 +456,7 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
     SPC_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     // (the tiled kernel's static row/output masks assume at least 9 rows of taps)
-    const bool tiled = spc_switch("SPC_CONV2D_TILED", 1) != 0 && nky >= 9 && nky <= kT2MaxK && nkx <= kT2MaxK &&
+    const bool tiled = allow_tiled && spc_switch("SPC_CONV2D_TILED", 1) != 0 && nky >= 9 && nky <= kT2MaxK && nkx <= kT2MaxK &&
                        (cube->ny + kT2Y - 1) / kT2Y <= 65535;
     // tiled: transposed columns padded with 7 zeros on both sides, kT[jx][7 + jy] = k[jy][jx]
     const int n = tiled ? nkx * (nky + 14) : nky * nkx;
@@ -510,6 +511,13 @@ int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, c
     return SPC_OK;
 }
 
+int spc_spatial_conv2d_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                           const double* h_kernel, int nky, int nkx, float* d_out,
+                           int64_t out_row_stride, int64_t out_plane_stride, void* d_workspace, size_t workspace_bytes) {
+    return conv2d_f32(device, stream, cube, mask, h_kernel, nky, nkx, d_out, out_row_stride, out_plane_stride, d_workspace,
+                      workspace_bytes, true);
+}
+
 int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                              const double* h_ky, int nky, const double* h_kx, int nkx, float* d_out,
                              int64_t out_row_stride, int64_t out_plane_stride, void* d_workspace, size_t workspace_bytes) {
@@ -528,6 +536,21 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     const double sum = sy * sx;
     SPC_REQUIRE(!(sum < 1e-8 && sum > -1e-8) && sum >= 1e-8,
                 "The kernel can't be normalized, because its sum is close to zero");
+    // A kernel with a zero tap under a mask that lets +-inf through: the ring, split and wide forms multiply every tap, and
+    // 0 * inf is NaN where astropy's restatement (the oracle), the float64 kernels and the per-output kernel - which all skip
+    // zero taps - give a finite value.  Such kernels (rare among outer products) take the per-output kernel.
+    {
+        bool zero_tap = false;
+        for (int i = 0; i < nky; ++i) zero_tap = zero_tap || h_ky[i] == 0.0;
+        for (int i = 0; i < nkx; ++i) zero_tap = zero_tap || h_kx[i] == 0.0;
+        if (zero_tap && !(mask && (mask->flags & SPC_MASK_FINITE)) && d_out) {
+            std::vector<double> k2((size_t)nky * nkx);
+            for (int j = 0; j < nky; ++j)
+                for (int i = 0; i < nkx; ++i) k2[(size_t)j * nkx + i] = h_ky[j] * h_kx[i];
+            return conv2d_f32(device, stream, cube, mask, k2.data(), nky, nkx, d_out, out_row_stride, out_plane_stride, d_workspace,
+                              workspace_bytes, false);
+        }
+    }
     // a mask ARRAY (and nothing but the array / isfinite) with a kernel of up to 29 non-negative taps: the split form on the
     // matrix cores first (spc_spatial_split.hip); whatever it does not take stays with the ring kernels below
     if (mask && (mask->flags & SPC_MASK_ARRAY) && !(mask->flags & ~(uint32_t)(SPC_MASK_ARRAY | SPC_MASK_FINITE)) && std::max(nky, nkx) <= 65 && d_out) {
@@ -618,6 +641,8 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     // cancel to den == 0 over a valid centre, and then astropy's filled-centre rule needs the lookup
     A.centre_zero = (A.ky[R / 2] * A.kx[R / 2] == 0.f) ? 1 : 0;
     for (int i = 0; i < R; ++i) if (A.ky[i] < 0.f || A.kx[i] < 0.f) A.centre_zero = 1;
+    A.top_clamp = 1;
+    for (int i = 0; i < R; ++i) if (A.ky[i] < 0.f || A.kx[i] < 0.f) A.top_clamp = 0;
     A.xcd_swizzle = spc_switch("SPC_XCD_SWIZZLE", 1) != 0;
     canonical_pred(A);
     // (the 49- and 65-tap rings - 35 to 65 taps - have an all-valid kernel for isotropic kernels only: two sets of

@@ -31,9 +31,20 @@ struct SpArgs {
                                               // and the look-up of the centre sample - global loads in a divergent branch, 59 -> 90 ms
                                               // at C4 with a signal mask whose all-invalid regions are full of empty windows - is skipped
     float pred_lim, pred_lo, pred_hi;         // canonical predicate: |v| <= lim && !(v <= lo) && !(v >= hi)
+    int top_clamp;                            // every tap is >= 0: the quotient is a weighted mean (see sp_quot)
     alignas(8) float ky[kMaxTaps + 1];        // padded to RY, centred (read pairwise as 64-bit scalars)
     alignas(8) float kx[kMaxTaps + 1];        // padded to RX, centred
 };
+
+// num / den of a window through the hardware reciprocal.  With non-negative taps (*clamp*) the quotient is a weighted mean of
+// the valid samples and cannot exceed the largest of them: a window that holds FLT_MAX alone gives FLT_MAX, but the rounded
+// k * max * (1 / k) can land one step above it, which float32 writes as inf - taken back to FLT_MAX while the numerator is
+// finite (an infinite valid sample makes the numerator infinite and the output stays infinite; 0 * 1/0 stays NaN)
+__device__ __forceinline__ float sp_quot(float num, float den, int clamp) {
+    float q = num * __builtin_amdgcn_rcpf(den);
+    if (clamp && __builtin_fabsf(q) > 3.402823466e+38f && __builtin_fabsf(num) <= 3.402823466e+38f) q = __builtin_copysignf(3.402823466e+38f, q);
+    return q;
+}
 
 // Workgroups are dealt round-robin to the 8 XCDs (block b -> XCD b % 8), each with its own L2.  With (strip, plane)
 // taken straight from blockIdx, the 4 - 5 strips of a plane - which share 28 halo columns with their neighbours and
@@ -459,7 +470,7 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
     #pragma unroll
                 for (int k = 0; k < kRun; ++k) {
                     if (r[k].y != 0.f || !A.centre_zero) {
-                        res[k] = r[k].x * __builtin_amdgcn_rcpf(r[k].y);      // (den = 0: 0 * inf = NaN)
+                        res[k] = sp_quot(r[k].x, r[k].y, A.top_clamp);      // (den = 0: 0 * inf = NaN)
                     } else {
                         // empty window -> (filled) centre sample, like astropy
                         res[k] = NAN;
@@ -669,7 +680,7 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
                 bool empty = false;
 #pragma unroll
                 for (int k = 0; k < kRun; ++k) {
-                    res[k] = r[k].x * __builtin_amdgcn_rcpf(r[k].y);      // den = 0 (empty window): 0 * inf = NaN
+                    res[k] = sp_quot(r[k].x, r[k].y, A.top_clamp);      // den = 0 (empty window): 0 * inf = NaN
                     empty = empty || (r[k].y == 0.f);
                 }
                 if (A.centre_zero && __any(empty)) {

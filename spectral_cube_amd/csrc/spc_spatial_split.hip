@@ -548,6 +548,11 @@ __global__ __launch_bounds__(NSUM == 3 ? 512 : kThreads, NSUM == 3 ? 1 : 2) void
                     val.y = __builtin_fmaf(pn.y, escale * __builtin_amdgcn_rcpf(pd.y), 0.f);
                     val.z = __builtin_fmaf(pn.z, escale * __builtin_amdgcn_rcpf(pd.z), 0.f);
                     val.w = __builtin_fmaf(pn.w, escale * __builtin_amdgcn_rcpf(pd.w), 0.f);
+                    // (non-negative taps: a weighted mean cannot exceed FLT_MAX; a quotient rounded above it, from a finite
+                    // numerator, is FLT_MAX - see sp_quot in spc_spatial_conv_impl.h)
+#define SPC_SPLIT_TOP(c_) if (__builtin_fabsf(val.c_) > 3.402823466e+38f && __builtin_fabsf(pn.c_) <= 3.402823466e+38f) val.c_ = __builtin_copysignf(3.402823466e+38f, val.c_);
+                    SPC_SPLIT_TOP(x) SPC_SPLIT_TOP(y) SPC_SPLIT_TOP(z) SPC_SPLIT_TOP(w)
+#undef SPC_SPLIT_TOP
                     const int yo = plane_row(16 * i + lm), xo = xw + 16 * n + 4 * lg;
                     const bool inside = (yo < ny) & (xo < nx);
                     if (STORE && inside) {

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void spectral_conv_generic_kernel(const ConvAr
                 ok = inc && (v == v);
                 if (!ok) v = 0.f;
             }
+            if (kern[j] == 0.0) continue;     // a zero tap adds nothing, under an infinite sample too (0 * inf), as in the float64 kernels
             num = fma(kern[j], (double)v, num);
             den = fma(kern[j], ok ? 1.0 : 0.0, den);
         }
@@ -483,7 +484,12 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         // non-negative taps (an empty window then means an invalid centre sample: NaN, which is what 0 / 0 gives)
         bool nonneg = true;
         for (int i = 0; i < ntaps; ++i) nonneg = nonneg && h_kernel[i] >= 0.0;
-        if (fits && nonneg && spc_switch("SPC_SPECTRAL_RING_WIDE", 1) != 0) {
+        // (the ring multiplies the zero taps that pad a shorter kernel, and 0 * inf is NaN: a kernel that does not fill its
+        // ring, under a mask that lets +-inf through, leaves its flagged tiles to the runs-of-16 kernel below, which multiplies
+        // no padding - a zero tap inside the kernel it still does)
+        bool fills = ntaps == Rf;
+        for (int i = 0; i < ntaps; ++i) fills = fills && h_kernel[i] != 0.0;
+        if (fits && nonneg && (fills || (A.mask.flags & SPC_MASK_FINITE)) && spc_switch("SPC_SPECTRAL_RING_WIDE", 1) != 0) {
             unsigned char* keep_status = A.status;
             rc = fill_common(A, cube, mask, h_kernel, ntaps, Rf);
             if (rc) return rc;

@@ -22,6 +22,17 @@
 
 namespace {
 
+// The quotient of a stencil window.  With non-negative taps it is a weighted mean of the valid samples and cannot exceed the
+// largest of them: a window that holds DBL_MAX alone gives DBL_MAX, but k * max / k can round one step above it, which the
+// type writes as inf.  A finite numerator never gives an infinite quotient here (a window with an infinite valid sample has
+// an infinite numerator and stays infinite; 0 / 0 stays NaN).  Signed taps whose true quotient lies beyond DBL_MAX come out
+// as DBL_MAX too.
+__device__ __forceinline__ double quot_top(double num, double den) {
+    double q = num / den;
+    if (fabs(q) > 1.7976931348623157e308 && fabs(num) <= 1.7976931348623157e308) q = copysign(1.7976931348623157e308, q);
+    return q;
+}
+
 struct Cube64 {
     const double* p;
     int64_t nz, ny, nx, row_stride, plane_stride;
@@ -329,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void spectral64_ring_kernel(const SRing64Ar
             sd[Q + r] = fma(A.k[r], w, sd[Q + r]);
         }
         const int o = i - H;                                 // the output that has seen its last input
-        if (o >= oa && o < ob) po[(int64_t)o * A.out_plane_stride] = sd[Q] != 0.0 ? sn[Q] / sd[Q] : NAN;
+        if (o >= oa && o < ob) po[(int64_t)o * A.out_plane_stride] = sd[Q] != 0.0 ? quot_top(sn[Q], sd[Q]) : NAN;
         if (Q == U - 1) {
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
@@ -437,7 +448,7 @@ __global__ __launch_bounds__(256) void spatial64_ypass_kernel(const Sp64Args A) 
         }
     }
     double res;
-    if (den != 0.0) res = num / den;
+    if (den != 0.0) res = quot_top(num, den);
     else { double cv; res = inc64(A.c, A.m, z, y, x, cv) ? cv : NAN; }
     A.out[z * A.out_plane_stride + y * A.out_row_stride + x] = res;
 }
@@ -510,7 +521,7 @@ __global__ __launch_bounds__(256) void spatial64_ypass_lds_kernel(const Sp64Args
             if (kw != 0.0) { const f64x2 tv = tile[(ro + j) * 64 + col]; num = fma(kw, tv.x, num); den = fma(kw, tv.y, den); }
         }
         double res;
-        if (den != 0.0) res = num / den;
+        if (den != 0.0) res = quot_top(num, den);
         else { double cv; res = inc64(A.c, A.m, z, y, x, cv) ? cv : NAN; }
         A.out[z * A.out_plane_stride + y * A.out_row_stride + x] = res;
     }
@@ -606,7 +617,7 @@ __global__ __launch_bounds__(256) void spatial64_ypass_lds4_kernel(const Sp64Arg
         const int64_t y = y0 + 4 * rg + q;
         if (y >= A.c.ny) break;
         double res;
-        if (den[q] != 0.0) res = num[q] / den[q];
+        if (den[q] != 0.0) res = quot_top(num[q], den[q]);
         else { double cv; res = inc64(A.c, A.m, z, y, x, cv) ? cv : NAN; }
         A.out[z * A.out_plane_stride + y * A.out_row_stride + x] = res;
     }
@@ -726,7 +737,7 @@ __global__ __launch_bounds__(256, 2) void spatial64_ring_kernel(const Ring64Args
         if (y >= ya && y < yb && x < nx) {
             // (no tap negative, centre taps positive: an empty window means an invalid centre sample - NaN, no second look at the cube,
             //  and no load behind a branch)
-            po[(int64_t)y * A.out_row_stride] = sd[Q] != 0.0 ? sn[Q] / sd[Q] : NAN;
+            po[(int64_t)y * A.out_row_stride] = sd[Q] != 0.0 ? quot_top(sn[Q], sd[Q]) : NAN;
         }
         // x pass of row u.  Left alone the compiler asks for all R pairs at once - 132 registers beside the ring's 144 - and
         // sends a part of the ring to scratch (a sched_barrier does not hold the reads back: they are hoisted before the
@@ -796,7 +807,7 @@ __global__ __launch_bounds__(256) void spatial64_direct_kernel(const Sp64Args A)
         }
     }
     double res;
-    if (den != 0.0) res = num / den;
+    if (den != 0.0) res = quot_top(num, den);
     else { double cv; res = inc64(A.c, A.m, z, y, x, cv) ? cv : NAN; }
     A.out[z * A.out_plane_stride + y * A.out_row_stride + x] = res;
 }
