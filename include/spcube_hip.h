@@ -637,13 +637,33 @@ int spc_arith_f64(int device, void* stream, const spc_cube_f64* cube, const spc_
  * spectral_cube/io/fits.py:63-172 (read_data_fits) / :171-260 (load_fits_cube).
  * bitpix in {8, 16, 32, 64, -32, -64}.  Scaling follows astropy: BITPIX 8/16 in
  * float32 (raw * BSCALE + BZERO), 32/64 in float64 then rounded, floating types
- * in their own precision; has_blank/blank: integer BLANK value -> NaN. */
+ * in their own precision; has_blank/blank: integer BLANK value -> NaN.
+ * The multiply and the add are two roundings; the multiply is left out for
+ * BSCALE 1 and the add for BZERO 0, as astropy leaves them out (-1 * 0 stays -0).
+ * BITPIX 32/64 reach float32 through float64 also when unscaled (two roundings:
+ * the reference's cube of an integer image is float64).  BITPIX 64 with BSCALE 1,
+ * BZERO 2^63 is converted as the uint64 it means, in one rounding, as astropy does.
+ * An unscaled BITPIX -32 image comes back bit for bit (NaN payloads, -0, denormals),
+ * which makes the call its own inverse (the writers use it).
+ * Where this follows the FITS standard and astropy 4.3.1 does not:
+ *   1. BLANK = 0 blanks (astropy tests the truth of the value and skips it);
+ *   2. BLANK on a pseudo-unsigned image (BSCALE 1, BZERO 2^15 / 2^31 / 2^63, or
+ *      -128 for BITPIX 8) blanks: BLANK is a value of the raw integers and is
+ *      compared with them whenever bitpix > 0 (astropy returns the unsigned
+ *      array and forgets BLANK).
+ * (A third one, up to three roundings for BITPIX 64 with BZERO 2^63, is gone: see
+ * above.)  has_blank is ignored for bitpix < 0, as astropy ignores the card.
+ * d_raw and d_out must be aligned to their own sample size (1 / 2 / 4 / 8 bytes
+ * for d_raw, 4 for d_out) and need no more: 16-byte aligned pairs of an
+ * unscaled BITPIX -32 image take a faster path, nothing else depends on it.
+ * Refused (SPC_ERR_INVALID, nothing written): another bitpix, NULL, n < 0. */
 int spc_fits_to_f32(int device, void* stream, const void* d_raw, int bitpix,
                     double bscale, double bzero, int has_blank, int64_t blank,
                     int64_t n, float* d_out);
 
 /* The wide sample types in their own precision: bitpix in {-64, 32, 64} -> native float64 (what astropy hands the
- * reference for such an image, spectral_cube/io/fits.py:63-172); feeds spc_moments_f64. */
+ * reference for such an image, spectral_cube/io/fits.py:63-172); feeds spc_moments_f64.  Scaling, BLANK, the uint64 of
+ * BZERO 2^63 and the alignment rule (d_raw 4 / 8 bytes, d_out 8) as above; any other bitpix is refused. */
 int spc_fits_to_f64(int device, void* stream, const void* d_raw, int bitpix,
                     double bscale, double bzero, int has_blank, int64_t blank,
                     int64_t n, double* d_out);

@@ -1020,6 +1020,135 @@ def case_fits_files():
     print("fits files ok")
 
 
+def fits_edge_vectors():
+    """{BITPIX: the raw edge samples of case_fits_decode_edges}: the ends of every range, byte-asymmetric patterns (a wrong
+    swap width, a missing sign extension), the float32 / float64 integer limits and rounding ties, every class of IEEE value"""
+    f4 = lambda *bits: np.array(bits, dtype=np.uint32).view(np.float32)          # noqa: E731
+    f8 = lambda *bits: np.array(bits, dtype=np.uint64).view(np.float64)          # noqa: E731
+    i32, i64 = np.iinfo(np.int32), np.iinfo(np.int64)
+    tie = 2 ** 62 + 2 ** 38 + 1            # float64 drops the 1, float32 then sits on a tie: two roundings give 2**62
+    return {
+        8: np.array([0, 1, 127, 128, 254, 255], dtype=np.uint8),
+        16: np.array([-32768, -32767, -256, -255, -1, 0, 1, 255, 256, 0x0102, 32767], dtype=np.int16),
+        32: np.array([i32.min, i32.min + 1, -1, 0, 1, 2 ** 24, 2 ** 24 + 1, 2 ** 24 + 3, 0x01020304, i32.max], dtype=np.int32),
+        64: np.array([i64.min, i64.min + 1, -1, 0, 1, 2 ** 53, 2 ** 53 + 1, tie, -tie, 2 ** 39 + 1, 0x0102030405060708, i64.max],
+                     dtype=np.int64),
+        # +-0, smallest / largest denormal, smallest normal, +-max, +-inf, quiet NaN, NaNs with payloads (one signalling), a pattern
+        -32: f4(0x00000000, 0x80000000, 0x00000001, 0x007fffff, 0x00800000, 0x7f7fffff, 0xff7fffff, 0x7f800000, 0xff800000,
+                0x7fc00000, 0x7fc00001, 0x7f800001, 0xffc12345, 0x01020304),
+        # the same in double; +-1e39 (inf in float32), 1e-46 (0), 1e-40 (a float32 denormal), 1 + 2**-24 (on a float32 tie)
+        # and 1 + 2**-24 + 2**-52 (just above it)
+        -64: np.concatenate([f8(0x0000000000000000, 0x8000000000000000, 0x0000000000000001, 0x000fffffffffffff, 0x0010000000000000,
+                                0x7fefffffffffffff, 0xffefffffffffffff, 0x7ff0000000000000, 0xfff0000000000000, 0x7ff8000000000000,
+                                0x7ff8000000000001, 0x7ff0000000000001, 0xfff8123456789abc, 0x0102030405060708),
+                             np.array([1e39, -1e39, 1e-46, 1e-40, 1.0 + 2.0 ** -24, 1.0 + 2.0 ** -24 + 2.0 ** -52])]),
+    }
+
+
+def case_fits_decode_edges():
+    """FITS decode at every BITPIX, scaling, BLANK and edge value (tests/golden/fits_decode_edges.npz).  Every file is one
+    edge vector of fits_edge_vectors repeated from sample 2 of a (3, 5, 7) cube on (so that it spans 4-sample groups at
+    every phase; 105 samples leave a ragged end), written by astropy with one scaling and one BLANK setting.
+    Stored per file: the bytes, astropy's array as it comes, the expected float32 cube and - BITPIX -64 / 32 / 64 - the
+    expected float64 cube.  Expected = astropy's array made float (BITPIX 32 / 64 through float64: np.result_type(dtype, 0.0),
+    masks.py:225; the uint64 of BSCALE 1, BZERO 2**63 in one rounding) and, on the files where astropy 4.3.1 leaves the FITS
+    standard (`BLANK = 0`, BLANK on a pseudo-unsigned image: meta["astropy_deviates"]), NaN where the raw sample is BLANK.
+    Asserted here: oracle_np.fits_decode(astropy_quirks=True) is astropy on every file, fits_decode() on every other file and
+    the expected cubes everywhere - bit for bit, NaN payloads of unscaled float images included."""
+    import io
+    import json
+    shape, start = (3, 5, 7), 2
+    n = int(np.prod(shape))
+    vectors = fits_edge_vectors()
+    scalings = [("none", None), ("s0125", (0.0125, 3.5)), ("s1em4", (1e-4, -2.0)), ("s01", (0.1, 0.0)), ("z725", (1.0, 7.25)),
+                ("neg", (-1.0, 0.0))]
+    files = []                                                 # (name, bitpix, scaling, blank)
+    for bitpix in (8, 16, 32, 64):
+        present = int(vectors[bitpix][-1] if bitpix == 8 else vectors[bitpix][0])       # 255 / the most negative value
+        per = list(scalings) + [("zm128", (1.0, -128.0))] if bitpix == 8 else \
+            list(scalings) + [("unsigned", (1.0, 2.0 ** (bitpix - 1)))]
+        for tag, sc in per:
+            files.append(("b%d_%s" % (bitpix, tag), bitpix, sc, None))
+        for tag, sc in (scalings[0], scalings[1]):
+            files.append(("b%d_%s_blank" % (bitpix, tag), bitpix, sc, present))
+            files.append(("b%d_%s_blank0" % (bitpix, tag), bitpix, sc, 0))
+        if bitpix != 8:
+            files.append(("b%d_unsigned_blank" % bitpix, bitpix, (1.0, 2.0 ** (bitpix - 1)), present))
+    for bitpix in (-32, -64):
+        for tag, sc in scalings + [("s03", (0.3, 1.7))]:
+            files.append(("f%d_%s" % (-bitpix, tag), bitpix, sc, None))
+        for tag, sc in (scalings[0], scalings[1]):
+            # a BLANK card on a float image is ignored, also where a sample's bit pattern read as an integer equals it
+            files.append(("f%d_%s_blankcard" % (-bitpix, tag), bitpix, sc, 0x01020304 if bitpix == -32 else 0x0102030405060708))
+
+    def bits(a):
+        a = np.ascontiguousarray(a)
+        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+    def same(a, b, exact_nan, what):
+        """bit for bit; NaNs that went through arithmetic (scaled, blanked) only have to be NaNs"""
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype)
+        ok = bits(a) == bits(b)
+        if not exact_nan:
+            ok |= np.isnan(a) & np.isnan(b)
+        assert ok.all(), (what, a[~ok][:4], b[~ok][:4])
+
+    store, meta = {}, {}
+    for name, bitpix, sc, blank in files:
+        vec = vectors[bitpix]
+        raw = np.roll(np.resize(vec, n), start)                  # the vector from sample 2 on, repeated to the end
+        raw = raw.reshape(shape)
+        hdu = fits.PrimaryHDU(data=raw.copy())
+        if sc is not None:
+            hdu.header["BSCALE"], hdu.header["BZERO"] = sc
+            if sc[1] == 2.0 ** (abs(bitpix) - 1):               # as written in the field: integers (20 characters do not
+                hdu.header["BSCALE"], hdu.header["BZERO"] = 1, 2 ** (bitpix - 1)        # hold 2**63 as a float)
+        if blank is not None:
+            hdu.header["BLANK"] = blank
+        buf = io.BytesIO()
+        hdu.writeto(buf, output_verify="ignore")
+        file_bytes = buf.getvalue()
+        with fits.open(io.BytesIO(file_bytes), do_not_scale_image_data=True) as hl:
+            off = -(-len(hl[0].header.tostring()) // 2880) * 2880
+        payload = file_bytes[off:off + raw.nbytes]
+        assert payload == raw.astype(raw.dtype.newbyteorder(">")).tobytes(), name        # the file holds the raw samples as they are
+        with fits.open(io.BytesIO(file_bytes)) as hl:
+            data = np.array(hl[0].data)
+        bscale, bzero = sc if sc is not None else (1.0, 0.0)
+        unsigned = bitpix > 8 and sc == (1.0, 2.0 ** (bitpix - 1))
+        deviates = bitpix > 0 and blank is not None and (blank == 0 or unsigned)
+        wide = bitpix in (-64, 32, 64)
+
+        def as_float(arr, out):
+            if out is np.float32 and bitpix in (32, 64) and not (bitpix == 64 and unsigned):
+                return arr.astype(np.float64).astype(np.float32)
+            return arr.astype(out)
+
+        exact_nan = bitpix < 0 and sc is None
+        for out in (np.float32, np.float64) if wide else (np.float32,):
+            from_astropy = as_float(data, out)
+            quirk = O.fits_decode(payload, bitpix, shape, bscale, bzero, blank if bitpix > 0 else None, out_dtype=out, astropy_quirks=True)
+            same(quirk, from_astropy, exact_nan, name + ": fits_decode(astropy_quirks=True) against astropy")
+            exp = from_astropy.copy()
+            if deviates:
+                exp[raw == blank] = np.nan                      # the FITS standard: BLANK is a value of the raw integers
+                assert np.isnan(exp).sum() > np.isnan(from_astropy).sum(), name
+            mine = O.fits_decode(payload, bitpix, shape, bscale, bzero, blank if bitpix > 0 else None, out_dtype=out)
+            same(mine, exp, exact_nan, name + ": fits_decode against the expectation")
+            store[name + ("_f32" if out is np.float32 else "_f64")] = exp
+        store[name + "_file"] = np.frombuffer(file_bytes, dtype=np.uint8)
+        store[name + "_astropy"] = data
+        meta[name] = dict(bitpix=bitpix, bscale=bscale, bzero=bzero, blank=blank if bitpix > 0 else None, blank_card=blank,
+                          astropy_deviates=bool(deviates), data_offset=off)
+    store["meta"] = np.array(json.dumps(meta))
+    store["start"] = np.array(start)
+    for bitpix, vec in vectors.items():
+        store["vector_%s" % (("b%d" % bitpix) if bitpix > 0 else ("f%d" % -bitpix))] = vec
+    np.savez_compressed(os.path.join(OUT, "fits_decode_edges.npz"), **store)
+    print("fits decode edges ok: %d files, %d where astropy leaves the standard" % (len(meta), sum(m["astropy_deviates"] for m in meta.values())))
+
+
 def case_moments_f64():
     """wide sources.  A BITPIX = -64 cube whose line sits on a baseline float32 cannot resolve
     (1000 K + a 2 mK .. 1 K line: one float32 ulp at 1000 is 61 uK), and a BITPIX = 32 cube with BSCALE / BZERO (astropy
@@ -1279,7 +1408,7 @@ def case_beams_cube():
 
 if __name__ == "__main__":
     cases = [case_beams_cube, case_moment_cube, case_c1, case_adv_argmax, case_smooth, case_interp, case_kernels,
-             case_wcs, case_wcs_frames, case_wcs_fk4, case_wcs_projections, case_wcs_strict, case_bilinear_scipy, case_reproject_glue_scipy, case_reproject_spline_scipy, case_statistics, case_fits_files, case_moments_f64, case_wide_ops,
+             case_wcs, case_wcs_frames, case_wcs_fk4, case_wcs_projections, case_wcs_strict, case_bilinear_scipy, case_reproject_glue_scipy, case_reproject_spline_scipy, case_statistics, case_fits_files, case_fits_decode_edges, case_moments_f64, case_wide_ops,
              case_order_statistics, case_sigma_clip]
     only = set(sys.argv[1:])                 # e.g. `gen_golden.py case_reproject_glue_scipy` regenerates one fixture
     for fn in cases:

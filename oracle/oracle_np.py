@@ -520,31 +520,54 @@ def reduce(data, include, op, axis=None, ddof=0):
 # --------------------------------------------------------------------------
 # FITS payload decoding
 # --------------------------------------------------------------------------
-def fits_decode(raw, bitpix, shape, bscale=1.0, bzero=0.0, blank=None):
+def fits_decode(raw, bitpix, shape, bscale=1.0, bzero=0.0, blank=None, out_dtype=np.float32, astropy_quirks=False):
     """What ``astropy.io.fits`` hands to ``read_data_fits`` (spectral_cube/io/
-    fits.py:63-172) for an image HDU, as float32: big-endian payload -> native;
-    BSCALE/BZERO applied in float32 for BITPIX 8/16, float64 for 32/64 and in
-    the file's own precision for floating types; integer BLANK -> NaN when the
-    data are scaled (astropy ``_ImageBaseHDU._get_scaled_image_data``).
-    gen_golden pins this against astropy reading real files."""
+    fits.py:63-172) for an image HDU, as the cube's float32 (or, out_dtype=
+    np.float64 for BITPIX -64 / 32 / 64, in the file's own precision):
+    big-endian payload -> native; the multiply by BSCALE (when it is not 1) and
+    the add of BZERO (when it is not 0) are two roundings, in float32 for
+    BITPIX 8/16, float64 for 32/64 and the file's own precision for floating
+    types; BITPIX 32/64 reach float32 THROUGH float64 also when unscaled (the
+    reference's cube of an integer image is np.result_type(dtype, 0.0),
+    masks.py:225); BITPIX 64 with BSCALE 1, BZERO 2**63 is the uint64 the
+    file means, rounded once; integer BLANK -> NaN.
+    gen_golden pins this against astropy reading real files
+    (case_fits_files, case_fits_decode_edges).
+
+    The FITS standard is followed where astropy 4.3.1 leaves it:
+    BLANK acts on the raw integer whenever BITPIX > 0 - also ``BLANK = 0``
+    (astropy tests ``if self._blank:``) and on the pseudo-unsigned images
+    BSCALE 1, BZERO 2**15 / 2**31 / 2**63 (and BZERO -128 of BITPIX 8), where
+    astropy hands out an unsigned array and forgets BLANK.
+    astropy_quirks=True reproduces astropy on these."""
     dt = {8: ">u1", 16: ">i2", 32: ">i4", 64: ">i8", -32: ">f4", -64: ">f8"}[bitpix]
+    out_dtype = np.dtype(out_dtype).type
+    if out_dtype is np.float64 and bitpix not in (-64, 32, 64):
+        raise ValueError("float64 output is for BITPIX -64 / 32 / 64")
     a = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape))).reshape(shape)
-    scaled = (bscale != 1.0) or (bzero != 0.0)
     if bitpix < 0:
         v = a.astype(a.dtype.newbyteorder("="))
-        if scaled:
-            v = v * v.dtype.type(bscale) + v.dtype.type(bzero)
-        return v.astype(np.float32)
-    if not scaled and blank is None:
-        return a.astype(np.float32)
+        with np.errstate(all="ignore"):                    # (signalling NaNs, float64 beyond float32's range)
+            if bscale != 1.0:
+                v = v * v.dtype.type(bscale)
+            if bzero != 0.0:
+                v = v + v.dtype.type(bzero)
+            return v.astype(out_dtype)
+    pseudo = bscale == 1.0 and bzero == {8: -128.0, 16: 2.0 ** 15, 32: 2.0 ** 31, 64: 2.0 ** 63}[bitpix]
+    if astropy_quirks and (pseudo or blank == 0):
+        blank = None
     work = np.float32 if bitpix in (8, 16) else np.float64
-    v = a.astype(work)
-    if scaled:
-        v *= work(bscale)
-        v += work(bzero)
+    if bitpix == 64 and pseudo:
+        v = (a.astype(np.int64).view(np.uint64) ^ np.uint64(1 << 63)).astype(out_dtype)     # one rounding
+    else:
+        v = a.astype(work)
+        if bscale != 1.0:
+            v *= work(bscale)
+        if bzero != 0.0:
+            v += work(bzero)
     if blank is not None:
         v[a == blank] = np.nan
-    return v.astype(np.float32)
+    return v.astype(out_dtype)
 
 
 # --------------------------------------------------------------------------

@@ -7,7 +7,11 @@
 //                      file's own precision;
 //   BITPIX 8 / 16    : float32(raw) * float32(BSCALE) + float32(BZERO)   (astropy scales these
 //   BITPIX 32 / 64   : float64(raw) * BSCALE + BZERO, rounded to float32  in float32 / float64)
-//   BLANK (integer types) -> NaN.
+//   BITPIX 64, BSCALE 1, BZERO 2^63 : the uint64 the file means, rounded once;
+//   BLANK (integer types) -> NaN, compared with the raw integer (the FITS standard: also BLANK = 0 and on the
+//   pseudo-unsigned images, where astropy 4.3.1 forgets it).
+// The multiply and the add are astropy's two in-place operations: two roundings, each left out where it is the identity
+// (BSCALE 1, BZERO 0) - x + 0 would make a +0 of the -0 that -1 * 0 is.
 #include "spc_common.h"
 #include <algorithm>
 
@@ -18,54 +22,58 @@ struct FitsArgs {
     float* out;
     int64_t n;
     int bitpix;
-    int scaled;          // BSCALE != 1 or BZERO != 0
+    int scaled;          // bit 0: BSCALE != 1 (multiply), bit 1: BZERO != 0 (add)
+    int unsigned64;      // BITPIX 64, BSCALE 1, BZERO 2^63
     double bscale, bzero;
     int has_blank;
     int64_t blank;
 };
+
+// two statements, two roundings (-ffp-contract=on fuses within one expression only)
+template <typename T>
+__device__ __forceinline__ T fits_scale(const FitsArgs& A, T v) {
+    if (A.scaled & 1) v *= (T)A.bscale;
+    if (A.scaled & 2) v += (T)A.bzero;
+    return v;
+}
 
 __device__ __forceinline__ float fits_one(const FitsArgs& A, int64_t i) {
     switch (A.bitpix) {
         case -32: {
             const uint32_t w = __builtin_bswap32(reinterpret_cast<const uint32_t*>(A.raw)[i]);
             float v = __uint_as_float(w);
-            if (A.scaled) { v *= (float)A.bscale; v += (float)A.bzero; }
-            return v;
+            return fits_scale(A, v);
         }
         case -64: {
             const uint64_t w = __builtin_bswap64(reinterpret_cast<const uint64_t*>(A.raw)[i]);
             double v = __longlong_as_double((long long)w);
-            if (A.scaled) { v *= A.bscale; v += A.bzero; }
-            return (float)v;
+            return (float)fits_scale(A, v);
         }
         case 8: {
             const uint8_t r = A.raw[i];
             if (A.has_blank && (int64_t)r == A.blank) return NAN;
             float v = (float)r;
-            if (A.scaled) { v *= (float)A.bscale; v += (float)A.bzero; }
-            return v;
+            return fits_scale(A, v);
         }
         case 16: {
             const uint16_t w = reinterpret_cast<const uint16_t*>(A.raw)[i];
             const int16_t r = (int16_t)((w >> 8) | (w << 8));
             if (A.has_blank && (int64_t)r == A.blank) return NAN;
             float v = (float)r;
-            if (A.scaled) { v *= (float)A.bscale; v += (float)A.bzero; }
-            return v;
+            return fits_scale(A, v);
         }
         case 32: {
             const int32_t r = (int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(A.raw)[i]);
             if (A.has_blank && (int64_t)r == A.blank) return NAN;
             double v = (double)r;
-            if (A.scaled) { v *= A.bscale; v += A.bzero; }
-            return (float)v;
+            return (float)fits_scale(A, v);
         }
         default: {   // 64
             const int64_t r = (int64_t)__builtin_bswap64(reinterpret_cast<const uint64_t*>(A.raw)[i]);
             if (A.has_blank && r == A.blank) return NAN;
+            if (A.unsigned64) return (float)((uint64_t)r ^ 0x8000000000000000ull);
             double v = (double)r;
-            if (A.scaled) { v *= A.bscale; v += A.bzero; }
-            return (float)v;
+            return (float)fits_scale(A, v);
         }
     }
 }
@@ -105,7 +113,8 @@ extern "C" int spc_fits_to_f32(int device, void* stream, const void* d_raw, int 
     FitsArgs A{};
     A.raw = (const uint8_t*)d_raw; A.out = d_out; A.n = n; A.bitpix = bitpix;
     A.bscale = bscale; A.bzero = bzero;
-    A.scaled = (bscale != 1.0 || bzero != 0.0) ? 1 : 0;
+    A.scaled = (bscale != 1.0 ? 1 : 0) | (bzero != 0.0 ? 2 : 0);
+    A.unsigned64 = (bitpix == 64 && bscale == 1.0 && bzero == 9223372036854775808.0) ? 1 : 0;
     A.has_blank = (has_blank && bitpix > 0) ? 1 : 0;      // BLANK is only defined for integer images
     A.blank = blank;
     const int64_t per_block = 256 * 4 * 4;
@@ -130,10 +139,10 @@ __global__ __launch_bounds__(256) void fits_to_f64_kernel(const FitsArgs A, doub
             const int64_t r = A.bitpix == 32 ? (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(A.raw)[i])
                                              : (int64_t)__builtin_bswap64(reinterpret_cast<const uint64_t*>(A.raw)[i]);
             if (A.has_blank && r == A.blank) { out[i] = nan; continue; }
+            if (A.unsigned64) { out[i] = (double)((uint64_t)r ^ 0x8000000000000000ull); continue; }
             v = (double)r;
         }
-        if (A.scaled) { v *= A.bscale; v += A.bzero; }
-        out[i] = v;
+        out[i] = fits_scale(A, v);
     }
 }
 }  // namespace
@@ -148,7 +157,8 @@ extern "C" int spc_fits_to_f64(int device, void* stream, const void* d_raw, int 
     FitsArgs A{};
     A.raw = (const uint8_t*)d_raw; A.out = nullptr; A.n = n; A.bitpix = bitpix;
     A.bscale = bscale; A.bzero = bzero;
-    A.scaled = (bscale != 1.0 || bzero != 0.0) ? 1 : 0;
+    A.scaled = (bscale != 1.0 ? 1 : 0) | (bzero != 0.0 ? 2 : 0);
+    A.unsigned64 = (bitpix == 64 && bscale == 1.0 && bzero == 9223372036854775808.0) ? 1 : 0;
     A.has_blank = (has_blank && bitpix > 0) ? 1 : 0;
     A.blank = blank;
     const unsigned nblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 1023) / 1024));
