@@ -704,6 +704,22 @@ typedef struct spc_stats_outputs {
 int spc_stats_axis_f32(int device, void* stream, const spc_cube_f32* cube,
                        const spc_mask* mask, int axis, const spc_stats_outputs* out);
 
+/* The second pass of std (nanstd, dask_spectral_cube.py:699-710): d_m2 = sum (x - mean)^2 of every ray along *axis*
+ * about that ray's OWN mean d_sum / d_count, from the count and sum maps spc_stats_axis_* wrote for the same cube, mask
+ * and axis (same shapes; d_m2 may not alias them).  sumsq / n - mean^2 loses (mean / sigma)^2 ulps on a pedestal, this
+ * about n ulps.  NaN for a ray without included samples.  Rays merge as m2_a + m2_b + (mean_a - mean_b)^2 n_a n_b / n. */
+int spc_stats_m2_axis_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int axis,
+                          const int32_t* d_count, const double* d_sum, double* d_m2);
+int spc_stats_m2_axis_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int axis,
+                          const int32_t* d_count, const double* d_sum, double* d_m2);
+/* The same pass about ONE centre for every ray (the mean of the whole cube, from spc_stats_global_*): d_s1 = sum (x - center),
+ * d_s2 = sum (x - center)^2 per ray along *axis*, 0 for a ray without included samples.  The caller adds the rays:
+ * sum (x - mean)^2 of the cube = S2 - S1^2 / npts. */
+int spc_stats_dev_axis_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int axis,
+                           double center, double* d_s1, double* d_s2);
+int spc_stats_dev_axis_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int axis,
+                           double center, double* d_s1, double* d_s2);
+
 /* argmax / argmin along a SPATIAL axis (BaseSpectralCube.argmax / argmin with axis = 1 or 2,
  * spectral_cube/spectral_cube.py:793-819; axis 0 is an output of spc_moments_f32): nanargmax of
  * the data filled with -inf (argmin: +inf) - excluded and NaN samples take the fill, the first

@@ -276,6 +276,10 @@ SIGNATURES = {
     "spc_fits_to_f64": (_i, [_i, _vp, _vp, _i, _d, _d, _i, _i64, _i64, _vp]),
     "spc_stats_global_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(_d), _vp, _sz]),
     "spc_stats_axis_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _P(SpcStatsOutputs)]),
+    "spc_stats_m2_axis_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _vp, _vp]),
+    "spc_stats_m2_axis_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp, _vp, _vp]),
+    "spc_stats_dev_axis_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _d, _vp, _vp]),
+    "spc_stats_dev_axis_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _vp, _vp]),
     "spc_comm_unique_id": (_i, [_P(C.c_uint8)]),
     "spc_comm_init": (_i, [_i, _P(C.c_uint8), _i, _i, _P(_vp)]),
     "spc_comm_destroy": (_i, [_vp]),

@@ -5,7 +5,9 @@
 // spc_stats_axis_f32 replaces the per-axis nan-reductions behind sum / mean / std / max /
 // min (dask_spectral_cube.py:641-767; NumPy class spectral_cube.py:578-791).  The reference
 // makes one pass per statistic (and nanstd two); here every statistic of a call comes out of
-// ONE read of the cube, accumulated in float64.
+// ONE read of the cube, accumulated in float64 - but for std, which like nanstd takes a second
+// read for its squared deviations (spc_stats_m2.hip): the sum of squares of this pass serves
+// statistics() (sumsq, rms, the reference's textbook sigma) and the bounds of the sigma clip.
 //
 //   global : the cube is a linear stream - 16-byte loads, grid-stride, per-thread
 //            accumulators, wave + LDS reduction, one partial record per block; the (few

@@ -1513,11 +1513,13 @@ class SpectralCube:
 
     # ---- statistics / nan-reductions -----------------------------
     def _reduce(self, op, axis, ddof=0):
-        """sum / mean / std / max / min (dask_spectral_cube.py:641-767): every statistic of a
-        call comes out of ONE pass over the cube (the reference: one pass per statistic, two
-        for nanstd)."""
-        need = {"sum": ("count", "sum"), "mean": ("count", "sum"), "std": ("count", "sum", "sumsq"),
-                "max": ("count", "max"), "min": ("count", "min")}[op]
+        """sum / mean / std / max / min (dask_spectral_cube.py:641-767): sum / mean / max / min come
+        out of ONE pass over the cube (the reference: one pass per statistic); std takes two,
+        like the reference's nanstd (_reduce_std)."""
+        axis = self._reduced_axes(axis)
+        if op == "std":
+            return self._reduce_std(axis, ddof)
+        need = {"sum": ("count", "sum"), "mean": ("count", "sum"), "max": ("count", "max"), "min": ("count", "min")}[op]
         if axis is None:
             if self._stream_source() is not None:
                 from . import streaming
@@ -1526,18 +1528,11 @@ class SpectralCube:
                 data, mask, _ = self._operand()
                 st = ops.stats_global(data, mask=mask)
             n = st["npts"]
-            vals = {"count": np.float64(n), "sum": np.float64(st["sum"]), "sumsq": np.float64(st["sumsq"]),
-                    "max": np.float64(st["max"]), "min": np.float64(st["min"])}
-        elif isinstance(axis, (tuple, list)):
+            vals = {"count": np.float64(n), "sum": np.float64(st["sum"]), "max": np.float64(st["max"]), "min": np.float64(st["min"])}
+        elif isinstance(axis, tuple):
             # two axes at once (e.g. the mean spectrum, axis=(1, 2)): one device pass removes the first
             # of them, the small (5 statistics x one map) remainder is finished on the host
-            axes = sorted(set(int(a) for a in axis))
-            if len(axes) == 3:
-                return self._reduce(op, None, ddof)
-            if len(axes) == 1:
-                return self._reduce(op, axes[0], ddof)
-            if len(axes) != 2 or any(a not in (0, 1, 2) for a in axes):
-                raise ValueError("axis must be None, 0, 1, 2 or a tuple of these")
+            axes = list(axis)
             if axes == [1, 2] and not (self._stream_source() is None and self._wide_resident()):
                 # per channel (spectra): one dedicated pass, nz records (a float64 cube: its rows on the device, the rest here)
                 if self._stream_source() is not None:
@@ -1554,24 +1549,76 @@ class SpectralCube:
                 warnings.simplefilter("ignore", RuntimeWarning)
                 vals = {"count": part["count"].sum(axis=second)}
                 for k in need:
-                    if k in ("sum", "sumsq"):
+                    if k == "sum":
                         vals[k] = np.nansum(part[k], axis=second)
                     elif k == "max":
                         vals[k] = np.nanmax(np.where(part["count"] > 0, part[k], -np.inf), axis=second)
                     elif k == "min":
                         vals[k] = np.nanmin(np.where(part["count"] > 0, part[k], np.inf), axis=second)
-            axis = tuple(axes)
         else:
-            if axis not in (0, 1, 2):
-                raise ValueError("axis must be None, 0, 1 or 2")
             r = self._stats_axis_maps(axis, need)
             vals = {k: r[k].get().astype(np.float64) for k in need}
         return self._finish_reduce(op, vals, axis, ddof)
 
-    def _stats_axis_maps(self, axis, need):
-        if self._stream_source() is not None:          # out of core: strips (axis 0) or slabs of planes (axis 1 / 2)
+    @staticmethod
+    def _reduced_axes(axis):
+        """None (all three), one of 0 / 1 / 2, or a sorted pair of them"""
+        if isinstance(axis, (tuple, list)):
+            axes = sorted(set(int(a) for a in axis))
+            if any(a not in (0, 1, 2) for a in axes) or not axes:
+                raise ValueError("axis must be None, 0, 1, 2 or a tuple of these")
+            return None if len(axes) == 3 else axes[0] if len(axes) == 1 else tuple(axes)
+        if axis is not None and axis not in (0, 1, 2):
+            raise ValueError("axis must be None, 0, 1 or 2")
+        return axis
+
+    def _reduce_std(self, axis, ddof):
+        """nanstd is two-pass in the reference (the mean, then the deviations), and so is this: per ray along ONE axis the
+        device gives count, sum and m2 = sum (x - mean)^2 about the ray's own mean (a second read, csrc/spc_stats_m2.hip);
+        a second axis, or all three, merges those rays here (distributed.merge_m2).  sumsq / n - mean^2 - the formula of
+        statistics()['sigma'], which is the reference's there - loses (mean / sigma)^2 ulps: noise or 0 on a pedestal."""
+        from .distributed import merge_m2
+        need = ("count", "sum", "m2")
+        src = self._stream_source()
+        if src is not None and self._is_wide():
             from . import streaming
-            return streaming.stats_axis(self, axis, need)
+            if streaming.wide_source(self) is None:
+                self._note_narrowed()              # a wide FITS image streams as float32: std of THOSE samples, said once
+        if axis is None and src is None:
+            # resident, the whole cube: ONE mean, known after the single pass of statistics(); the second pass sums the
+            # deviations about it per ray of the longest axis, the rays are added here - nothing to merge
+            data, mask, _ = self._operand()
+            st = ops.stats_global(data, mask=mask)
+            n = st["npts"]
+            q = np.nan
+            if n > 0:
+                first = max((0, 1, 2), key=lambda a: (self._shape[a], a))
+                s1, s2 = ops.stats_dev_axis(data, first, st["sum"] / n, mask=mask)
+                s1, s2 = float(s1.get().sum()), float(s2.get().sum())
+                q = max(s2 - s1 * s1 / n, 0.0) if s2 == s2 else np.nan
+            vals = {"count": np.float64(n), "sum": np.float64(st["sum"]), "m2": np.float64(q)}
+        elif axis is None or isinstance(axis, tuple):
+            # the device reduces the LONGEST of the axes (the fewest rays come back: what is merged here is the cube over
+            # that axis - (4096, 4096, 4) along x would leave 16 M rows of 4 samples), the host the rest
+            over = (0, 1, 2) if axis is None else axis
+            first = max(over, key=lambda a: (self._shape[a], a))
+            r = self._stats_axis_maps(first, need, wide=True)
+            if axis is None:
+                second = None
+            else:
+                other = over[0] if over[1] == first else over[1]
+                second = other - (1 if other > first else 0)           # its place in the map that has lost `first`
+            n, s, q = merge_m2(*(r[k].get() for k in need), axis=second)
+            vals = {"count": n, "sum": s, "m2": q}
+        else:
+            r = self._stats_axis_maps(axis, need, wide=True)
+            vals = {k: r[k].get().astype(np.float64) for k in need}
+        return self._finish_reduce("std", vals, axis, ddof)
+
+    def _stats_axis_maps(self, axis, need, wide=False):
+        if self._stream_source() is not None:          # out of core: strips (axis 0) or slabs of planes (axis 1 / 2)
+            from . import streaming                    # (*wide*: float64 strips of a float64 host array - std asks for them)
+            return streaming.stats_axis(self, axis, need, wide=wide)
         data, mask, _ = self._operand()
         return ops.stats_axis(data, axis, mask=mask, want=need)
 
@@ -1583,8 +1630,7 @@ class SpectralCube:
             elif op == "mean":
                 out = np.where(n > 0, vals["sum"] / n, np.nan)
             elif op == "std":
-                var = (vals["sumsq"] - vals["sum"] * vals["sum"] / n) / (n - ddof)
-                out = np.where((n > 0) & (n - ddof > 0), np.sqrt(np.maximum(var, 0.0)), np.nan)
+                out = np.where((n > 0) & (n - ddof > 0), np.sqrt(vals["m2"] / (n - ddof)), np.nan)
             else:
                 out = np.where(n > 0, vals[op], np.nan)
         if axis is None:

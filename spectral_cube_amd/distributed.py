@@ -364,6 +364,28 @@ def combine_statistics(parts):
     return out
 
 
+def merge_m2(count, total, m2, axis=None):
+    """(count, sum, m2) of populations merged along *axis* (None: all of them), m2 = sum (x - mean)^2 about each one's OWN
+    mean - the records std is made of (ops.stats_axis with "m2"): rays of a map merged into a spectrum or one number, the
+    strips of a cube.  m2 = sum m2_i + sum n_i (mean_i - mean)^2 (Chan, Golub & LeVeque 1983, the pairwise update summed): no
+    sumsq - sum^2 / n, which is lost on a pedestal.  An empty population (count 0, NaN sums) adds nothing.  The element-wise
+    Float64 with numpy's pairwise sums, but for mean_i - mean, which is formed in long double: the quotient sum_i / n_i rounded
+    to float64 would move it by eps64 |mean| - 1e-8 of the result for counts near 2^30 with a spread of 17, whose sums are exact.
+    An error e of the merged mean itself enters as -N e^2 only (sum n_i (mean_i - mean) = -N e by the definition of the mean)."""
+    count, total, m2 = np.asarray(count), np.asarray(total, np.float64), np.asarray(m2, np.float64)
+    live = count > 0
+    n = count.astype(np.float64)
+    s = np.where(live, total, 0.0)
+    nn, ss = n.sum(axis=axis, keepdims=True), s.sum(axis=axis, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dev = (s.astype(np.longdouble) / np.maximum(n, 1.0) - ss / nn).astype(np.float64)
+        dev *= dev
+        dev *= n
+        dev += m2
+    q = np.where(live, dev, 0.0).sum(axis=axis)
+    return n.sum(axis=axis), ss.sum(axis=axis), q
+
+
 def sharded_statistics(strip_stats, transport):
     """statistics() of a row-sharded cube: every rank passes the record of ITS strip (ops.stats_global on
     the device, one pass), five numbers per rank travel through the rendezvous transport."""

@@ -1051,7 +1051,7 @@ def resample_spline(cube, xs, ys, order, stream=None, want_footprint=True, out=N
 
 # ---- statistics ----------------------------------------------
 STAT_KEYS = ("count", "min", "max", "sum", "sumsq")
-_STAT_DTYPES = {"count": np.int32, "min": np.float32, "max": np.float32, "sum": np.float64, "sumsq": np.float64}
+_STAT_DTYPES = {"count": np.int32, "min": np.float32, "max": np.float32, "sum": np.float64, "sumsq": np.float64, "m2": np.float64}
 
 
 def stats_global(cube, mask=None, stream=None):
@@ -1082,14 +1082,20 @@ def stats_planes(cube, mask=None, stream=None):
 def stats_axis(cube, axis, mask=None, want=STAT_KEYS, stream=None, out=None):
     """count / min / max / sum / sumsq maps along *axis* in ONE pass (the nan-reductions behind
     sum / mean / std / max / min, dask_spectral_cube.py:641-767).  Returns DeviceArrays
-    (*out*: dict of preallocated ones, reused); min / max have the cube's dtype."""
+    (*out*: dict of preallocated ones, reused); min / max have the cube's dtype.
+
+    ``"m2"`` in *want* (not one of the five of the single pass): sum (x - mean)^2 of every ray about its OWN mean, from a
+    second read of the cube (csrc/spc_stats_m2.hip) - what std is made of: sumsq / n - mean^2 is lost on a pedestal.
+    Comes with count and sum, which it is computed from."""
     if axis not in (0, 1, 2):
         raise ValueError("axis must be 0, 1 or 2")
     name, dtype = _entry("stats_axis", cube)
     types = dict(_STAT_DTYPES, min=dtype, max=dtype)
     shp = tuple(n for i, n in enumerate(cube.shape) if i != axis)
     res = {}
-    for k in want:
+    m2 = "m2" in want
+    want = tuple(k for k in want if k != "m2") + (tuple(k for k in ("count", "sum") if k not in want) if m2 else ())
+    for k in want + (("m2",) if m2 else ()):
         a = out.get(k) if out else None
         if a is None:
             a = DeviceArray(shp, types[k], cube.device)
@@ -1101,7 +1107,23 @@ def stats_axis(cube, axis, mask=None, want=STAT_KEYS, stream=None, out=None):
         setattr(o, "d_" + k, res[k].ptr)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis), C.byref(o))
+    if m2:
+        _lib.call(_entry("stats_m2_axis", cube)[0], cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis),
+                  C.c_void_p(res["count"].ptr), C.c_void_p(res["sum"].ptr), C.c_void_p(res["m2"].ptr))
     return res
+
+
+def stats_dev_axis(cube, axis, center, mask=None, stream=None):
+    """(s1, s2) DeviceArrays: sum (x - center) and sum (x - center)^2 of every ray along *axis* about ONE number - the second
+    pass of the whole cube's std, whose mean stats_global gave (csrc/spc_stats_m2.hip)"""
+    if axis not in (0, 1, 2):
+        raise ValueError("axis must be 0, 1 or 2")
+    shp = tuple(n for i, n in enumerate(cube.shape) if i != axis)
+    s1, s2 = DeviceArray(shp, np.float64, cube.device), DeviceArray(shp, np.float64, cube.device)
+    c, m = _cube_c(cube), _mask_c(mask, cube)
+    _lib.call(_entry("stats_dev_axis", cube)[0], cube.device, _sh(stream), C.byref(c), C.byref(m), int(axis), float(center),
+              C.c_void_p(s1.ptr), C.c_void_p(s2.ptr))
+    return s1, s2
 
 
 def map_conv2d(dmap, kernel2d, stream=None, out=None):

@@ -381,14 +381,31 @@ class StripPipeline:
             self.copy.synchronize()
 
 
-def _mask_terms(cube):
-    """device terms of the cube's mask, array term kept on the HOST (strips of it travel with the data)"""
+def wide_source(cube):
+    """the float64 form of a streamed cube's source, or None: a host array, a memory map or a dask array of a wide dtype can
+    be staged as float64 strips (8 bytes per sample) for the reductions that need the samples as they are - std on a
+    pedestal.  A FITS source decodes to float32 on the device and has no such form (std then warns: PrecisionWarning)"""
+    from .cube import _is_wide_dtype
+    src = cube._stream_source()
+    if isinstance(src, (NdarraySource, DaskSource)) and src.out_dtype == np.float32 and _is_wide_dtype(src.data.dtype):
+        return type(src)(src.data, np.float64)
+    return None
+
+
+def _mask_terms(cube, wide=False):
+    """device terms of the cube's mask, array term kept on the HOST (strips of it travel with the data); *wide*: lowered for
+    float64 strips (thresholds keep their float64 value)"""
     if cube._mask is None:
         return None
-    cached = getattr(cube, "_stream_terms", None)
+    slot = "_stream_terms64" if wide else "_stream_terms"
+    cached = getattr(cube, slot, None)
     if cached is not None and cached[0] is cube._mask:        # (an inverted / composite boolean mask materialises a host
         return cached[1]                                      # array: once per cube, not once per caller)
-    terms = cube._mask._device_terms(cube)
+    if wide:
+        from .cube import _WideView
+        terms = cube._mask._device_terms(_WideView(cube))
+    else:
+        terms = cube._mask._device_terms(cube)
     if terms is None:
         raise NotImplementedError("a streamed (out-of-core) cube takes masks made of isfinite / threshold comparisons on "
                                   "the cube itself and boolean arrays; this mask needs the whole cube on the host")
@@ -398,7 +415,7 @@ def _mask_terms(cube):
     lo = float(lo) if flags & (_lib.MASK_GT | _lib.MASK_GE) else 0.0
     hi = float(hi) if flags & (_lib.MASK_LT | _lib.MASK_LE) else 0.0
     try:
-        cube._stream_terms = (cube._mask, (flags, lo, hi, m))
+        setattr(cube, slot, (cube._mask, (flags, lo, hi, m)))
     except AttributeError:
         pass
     return flags, lo, hi, m
@@ -408,17 +425,19 @@ class Strips:
     """(y0, y1, data strip, MaskSpec or None) of a streamed cube on `stream`; data and the mask's array term come
     through two pipelines in lockstep"""
 
-    def __init__(self, cube, stream, rows=None, halo=0, axis=1, out_factor=1.0, window=None):
+    def __init__(self, cube, stream, rows=None, halo=0, axis=1, out_factor=1.0, window=None, wide=False):
         from . import ops
         self.ops = ops
-        src = whole = cube._stream_source()
+        src = whole = (wide_source(cube) if wide else None) or cube._stream_source()
+        wide = whole.out_dtype == np.float64
         if window is not None:             # (z0, z1, y0, y1): only that range of channels and rows is staged (a cut)
             src = WindowSource(whole, *window)
-        self.terms = _mask_terms(cube)
+        self.terms = _mask_terms(cube, wide)
         has_arr = self.terms is not None and self.terms[3] is not None
         if rows is None:
-            rows = (plan_rows(src.shape, hbm_budget(cube.device), mask_array=has_arr, max_strip_mb=getattr(src, "max_strip_mb", 0)) if axis == 1 else
-                    plan_planes(src.shape, hbm_budget(cube.device), mask_array=has_arr, out_factor=out_factor))
+            budget = hbm_budget(cube.device) // (2 if wide else 1)           # (the plans count 4 bytes per sample)
+            rows = (plan_rows(src.shape, budget, mask_array=has_arr, max_strip_mb=getattr(src, "max_strip_mb", 0)) if axis == 1 else
+                    plan_planes(src.shape, budget, mask_array=has_arr, out_factor=out_factor))
         self.rows = rows
         self.data = StripPipeline(src, cube.device, rows, stream, halo=halo, axis=axis)
         self.mask = None
@@ -852,33 +871,38 @@ def map_slabs(cube, fn, out_yx, sink, planes=None, stats=None):
         stats.update(bytes_in=st.bytes, bytes_out=w.bytes, slabs=n, planes=st.rows)
 
 
-def slab_maps(cube, fn, names, width, dtypes, planes=None):
+def slab_maps(cube, fn, names, width, dtypes, planes=None, wide=False):
     """{name: (nz, width) DeviceArray}: maps whose FIRST axis is the spectral one (statistics along y or x of a streamed
     cube), assembled on the device slab by slab: fn(slab, mask spec, stream, {name: rows z0:z1 of the map}, z0, z1)."""
     nz = cube._shape[0]
     maps = {k: DeviceArray((nz, width), dtypes[k], cube.device) for k in names}
     compute = Stream(cube.device)
-    for z0, z1, dev, mspec in Strips(cube, compute, planes, axis=0, out_factor=0.0):
+    for z0, z1, dev, mspec in Strips(cube, compute, planes, axis=0, out_factor=0.0, wide=wide):
         fn(dev, mspec, compute, {k: _rows_view(maps[k], z0, z1) for k in names}, z0, z1)
     compute.synchronize()
     return maps
 
 
-def stats_axis(cube, axis, want):
+def stats_axis(cube, axis, want, wide=False):
     """ops.stats_axis of a streamed cube: along the spectral axis strip by strip (every spaxel whole), along y or x
-    slab by slab (every image plane whole); the maps are assembled on the device"""
+    slab by slab (every image plane whole); the maps are assembled on the device.  Every ray is whole in its strip, so
+    "m2" (the second pass of std) needs nothing merged here.  *wide*: float64 strips where the source has them
+    (wide_source): std of a float64 array on a pedestal is not that of its float32 copy"""
     from . import ops
     nz, ny, nx = cube._shape
     dt = ops._STAT_DTYPES
+    wide = wide and wide_source(cube) is not None
+    if wide and ("min" in want or "max" in want):
+        raise ValueError("float64 strips serve count / sum / m2 only")
     if axis == 0:
         maps = {k: DeviceArray((ny, nx), dt[k], cube.device) for k in want}
         compute = Stream(cube.device)
-        for y0, y1, dev, mspec in Strips(cube, compute):
+        for y0, y1, dev, mspec in Strips(cube, compute, wide=wide):
             ops.stats_axis(dev, 0, mask=mspec, want=want, stream=compute, out={k: _rows_view(maps[k], y0, y1) for k in want})
         compute.synchronize()
         return maps
     return slab_maps(cube, lambda dev, mspec, stream, out, z0, z1: ops.stats_axis(dev, axis, mask=mspec, want=want, stream=stream, out=out),
-                     want, nx if axis == 1 else ny, dt)
+                     want, nx if axis == 1 else ny, dt, wide=wide)
 
 
 def stats_planes(cube):

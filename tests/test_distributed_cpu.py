@@ -381,3 +381,47 @@ def test_bench_refuses_to_time_the_host_fallback_when_every_rank_has_a_device():
     assert p.returncode == 0, p.stderr
     p = _bench(["--gpus", "2"], SPC_BENCH_DRYRUN="1", SPC_BENCH_DRYRUN_STITCH="rccl", SPC_BENCH_DRYRUN_DEVICES="2")
     assert p.returncode == 0, p.stderr
+
+
+def test_merge_m2_combines_populations_far_from_zero():
+    """distributed.merge_m2: the (count, sum, m2) records of std - m2 about each population's OWN mean - merged along an axis
+    or all together equal the two-pass std of the union to 1e-10 on a 1000 K baseline with mK noise (where sumsq - sum^2 / n of
+    the combined sums is off by 1e-4; 1e-10: the records are float64, a sum rounded to eps64 moves its mean by eps64 |mean| and
+    the merged m2 by 2 eps64 (|mean| / sigma) / sqrt(N) = 2e-11 at |mean| / sigma = 1e6, N = 200), on populations with baselines of their own, with empty populations (NaN sums) among them"""
+    from far_from_zero import ref_std, textbook_std
+    from spectral_cube_amd.distributed import merge_m2
+    rng = np.random.default_rng(5)
+    base = np.array([1000.0, 1000.0, -1e6, 3.0, 1000.0, 2.0 ** 30])[None, :, None]
+    x = base * (1.0 + 1e-6 * rng.standard_normal((40, 6, 7)))
+    x[rng.random(x.shape) < 0.3] = np.nan
+    x[:, 1, 2] = np.nan                                              # an empty population
+    x[1:, 4, 3] = np.nan                                             # a population of one
+    ok = ~np.isnan(x)
+    cnt = ok.sum(axis=0)
+    wide = np.where(ok, x, 0).astype(np.longdouble)
+    with np.errstate(all="ignore"):
+        tot = np.where(cnt > 0, wide.sum(axis=0), np.nan).astype(np.float64)
+        m2 = np.where(cnt > 0, ((wide - wide.sum(axis=0) / cnt) ** 2 * ok).sum(axis=0), np.nan).astype(np.float64)
+        for axis, of in ((None, (0, 1, 2)), (0, (0, 1)), (1, (0, 2))):
+            n, s, q = merge_m2(cnt, tot, m2, axis=axis)
+            exp = ref_std(x, of, 1)
+            got = np.where(n > 1, np.sqrt(q / (n - 1)), np.nan)
+            assert np.array_equal(n, ok.sum(axis=of)) and np.array_equal(np.isnan(got), np.isnan(exp))
+            fin = ~np.isnan(exp)
+            assert np.all(np.abs(got - exp)[fin] <= 1e-10 * np.abs(exp)[fin]), axis
+            assert np.all(np.abs(s - np.nansum(x, axis=of)) <= 1e-12 * np.nansum(np.abs(x), axis=of))
+    # the columns that hold the 1000 K populations alone: the merged record is right where the textbook formula is not
+    col = x[:, [0, 1, 4], :1]
+    n, s, q = merge_m2(cnt[[0, 1, 4], :1], tot[[0, 1, 4], :1], m2[[0, 1, 4], :1])
+    exp = ref_std(col, None, 0)
+    assert abs(np.sqrt(q / n) - exp) <= 1e-10 * exp and abs(textbook_std(col, None, 0) - exp) > 1e-7 * exp
+    # counts near 2^30 with a spread of 17: the sums are exact integers, and a quotient sum_i / n_i rounded to float64 (eps64
+    # |mean| = 2e-7 against deviations of 17 / sqrt(n_i)) would cost 1e-8 of the result
+    c = 2.0 ** 30 + rng.integers(-30, 30, size=(33, 5, 7), endpoint=True).astype(np.float64)
+    own = c.mean(axis=2, keepdims=True, dtype=np.longdouble)
+    n, s, q = merge_m2(np.full((33, 5), 7, np.int32), c.sum(axis=2), (((c - own) ** 2).sum(axis=2)).astype(np.float64), axis=1)
+    exp = ref_std(c, (1, 2), 0)
+    assert np.all(np.abs(np.sqrt(q / n) - exp) <= 1e-10 * exp)
+    # nothing at all
+    n, s, q = merge_m2(np.zeros((2, 3), np.int32), np.full((2, 3), np.nan), np.full((2, 3), np.nan))
+    assert n == 0 and q == 0

@@ -575,6 +575,7 @@ def test_float64_cube_stays_float64_through_the_other_operators(gpu, tmp_path, s
     import warnings as W
     from spectral_cube_amd import PrecisionWarning, SpectralCube, io_fits
     from conftest import golden
+    from far_from_zero import ref_std
     g, g0 = golden("wide_ops.npz"), golden("moments_f64.npz")
     path = str(tmp_path / "f64.fits")
     with open(path, "wb") as f:
@@ -615,6 +616,12 @@ def test_float64_cube_stays_float64_through_the_other_operators(gpu, tmp_path, s
             for op in ("sum", "mean", "max", "min"):
                 for ax in (None, 0, 1, 2):
                     close(getattr(c, op)(axis=ax), g["%s_ax%s_%s" % (op, "N" if ax is None else ax, tag)], "%s axis %s %s" % (op, ax, tag))
+            # std: two-pass like the reference's nanstd, against the long-double reference of far_from_zero.py (on this 1000 K
+            # baseline sumsq / n - mean^2 is the 1e-6 of 'sigma' above)
+            fz = np.where(g["include_" + tag].astype(bool), g["data"], np.nan)
+            for ddof in (0, 1):
+                for ax in (None, 0, 1, 2):
+                    close(c.std(axis=ax, ddof=ddof), ref_std(fz, ax, ddof), "std axis %s ddof %d %s" % (ax, ddof, tag), rtol=1e-9)
             close(c.mean(axis=(1, 2)), np.asarray(O.reduce(g["data"], g["include_" + tag].astype(bool), "mean", axis=(1, 2))), "mean spectrum " + tag)
             # the chain: moments of the smoothed cube, float64 all the way
             for order in (0, 1):
