@@ -267,8 +267,9 @@ class DeviceArray:
         nz, ny, nx = self.shape
         if not (0 <= y0 <= y1 <= ny):
             raise ValueError("row range out of bounds")
+        # (rows of a view start y0 ROW STRIDES on: the same as y0 * nx unless the view is a window in x of a wider parent)
         v = DeviceArray((nz, y1 - y0, nx), self.dtype, self.device,
-                        ptr=self.ptr + y0 * nx * self.dtype.itemsize, owner=self)
+                        ptr=self.ptr + y0 * getattr(self, "row_stride", nx) * self.dtype.itemsize, owner=self)
         v.row_stride = getattr(self, "row_stride", nx)
         v.plane_stride = getattr(self, "plane_stride", ny * nx)
         v.nbytes = 0            # not a contiguous buffer: upload()/get() are not available

@@ -34,8 +34,11 @@ class MaskSpec:
             if self.array is None:
                 raise ValueError("MASK_ARRAY set without an array")
             m.d_array = self.array.ptr
-            m.row_stride = getattr(self.array, "row_stride", 0)
-            m.plane_stride = getattr(self.array, "plane_stride", 0)
+            # always the array's OWN strides: 0 would mean "the cube's" on the C side, which walks a contiguous mask
+            # with the strides of a rows() / planes() view of a larger cube
+            shp = self.array.shape
+            m.row_stride = getattr(self.array, "row_stride", shp[-1])
+            m.plane_stride = getattr(self.array, "plane_stride", shp[-2] * shp[-1] if len(shp) >= 2 else shp[-1])
         return m
 
     def rows(self, y0, y1):
@@ -231,11 +234,11 @@ def sigma_clip_axis0_f64(cube, sigma=3.0, sigma_lower=None, sigma_upper=None, ma
     return out
 
 
-def narrow_f64(cube, stream=None):
-    """float32 copy of a float64 DeviceArray (for the operators without a float64 form)"""
-    out = DeviceArray(cube.shape, np.float32, cube.device)
+def narrow_f64(cube, stream=None, out=None):
+    """float32 copy of a float64 DeviceArray (for the operators without a float64 form); *out* may be a strided view"""
+    out = _out_cube(out, cube.shape, np.float32, cube.device)
     c = _cube_c(cube, _F64)
-    _lib.call("spc_narrow_f64_to_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(out.ptr), 0, 0)
+    _lib.call("spc_narrow_f64_to_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(out.ptr), *_strides(out))
     return out
 
 
@@ -309,14 +312,13 @@ def spectral_conv(cube, kernel1d, mask=None, out=None, stream=None):
     spectral_smooth (dask_spectral_cube.py:880-917); the result has the cube's dtype (the Dask class keeps the chunk
     dtype, dask_spectral_cube.py:829)."""
     name, dtype = _entry("spectral_conv", cube)
-    if out is None:
-        out = DeviceArray(cube.shape, dtype, cube.device)
+    out = _out_cube(out, cube.shape, dtype, cube.device)
     k, kp = _kern(kernel1d)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     # (the float64 kernel sizes its scratch by its own kind)
     ws, wsn = workspace(cube.device, stream, _lib.WS_SPECTRAL_CONV_F64 if dtype == _F64 else _lib.WS_SPECTRAL_CONV, *cube.shape, len(k))
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), kp, len(k),
-              C.c_void_p(out.ptr), 0, 0, ws, wsn)
+              C.c_void_p(out.ptr), *_strides(out), ws, wsn)
     return out
 
 
@@ -331,6 +333,20 @@ def downsample_shape(shape, axis, factor, truncate):
 
 def _strides(arr):
     return getattr(arr, "row_stride", 0), getattr(arr, "plane_stride", 0)
+
+
+def _out_cube(out, shape, dtype, device):
+    """*out* when the caller preallocated it (checked as _given checks; it may be a strided view of a larger array, whose
+    strides travel with it), else a new DeviceArray"""
+    return _given({"out": out} if out is not None else None, "out", shape, dtype, device)
+
+
+def _contiguous_out(out, shape, dtype, device):
+    """_out_cube for the entries that address their output as one contiguous block (their C entry takes no output strides,
+    or the wrapper offsets the pointer itself): a strided view is refused here, before anything is launched"""
+    if out is not None and getattr(out, "_is_view", False):
+        raise ValueError("preallocated output must be a contiguous %s %s, not a strided view" % (tuple(shape), np.dtype(dtype)))
+    return _out_cube(out, shape, dtype, device)
 
 
 def _downsample_outputs(cube, axis, factor, truncate, dtype, out, out_mask):
@@ -478,8 +494,8 @@ def stack_cube(cube, lo, t, inv_dx, exact, mode="nanmean", fill=np.nan, mask=Non
     shape = (n0,) + tuple(cube.shape[1:])
     if out is None:
         out = DeviceArray(shape if nsrc >= 1 and 2 <= n0 <= cube.shape[0] else (1, 1, 1), dtype, cube.device)
-    elif tuple(out.shape) != shape or out.dtype != dtype:
-        raise ValueError("preallocated output must be %s %s" % (shape, dtype))
+    else:
+        out = _contiguous_out(out, shape, dtype, cube.device)          # (the entry takes no output strides)
     ws = DeviceArray((int(_lib.load().spc_stack_cube_workspace_bytes(nsrc, n0)),), np.uint8, cube.device)
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill), nsrc,
               lo.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), inv_dx.ctypes.data_as(C.c_void_p),
@@ -732,8 +748,7 @@ def spatial_conv(cube, kernel2d, mask=None, out=None, stream=None, arithmetic=No
     if arithmetic is not None and not wide:          # (the float64 stencils have one arithmetic)
         with masked_spatial_arithmetic(arithmetic):
             return spatial_conv(cube, kernel2d, mask=mask, out=out, stream=stream)
-    if out is None:
-        out = DeviceArray(cube.shape, cube.dtype, cube.device)
+    out = _out_cube(out, cube.shape, cube.dtype, cube.device)
     k2 = np.ascontiguousarray(kernel2d, dtype=np.float64)
     if k2.ndim != 2:
         raise ValueError("kernel must be 2-D")
@@ -745,17 +760,17 @@ def spatial_conv(cube, kernel2d, mask=None, out=None, stream=None, arithmetic=No
         (ky, kyp), (kx, kxp) = (_kern(sep[0]), _kern(sep[1])) if sep is not None else (_kern(k2), (None, None))
         ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV_F64, *cube.shape, k2.shape[0], k2.shape[1])
         _lib.call("spc_spatial_conv_f64", cube.device, _sh(stream), C.byref(c), C.byref(m), kyp, k2.shape[0], kxp, k2.shape[1],
-                  0 if sep is None else 1, C.c_void_p(out.ptr), 0, 0, ws, wsn)
+                  0 if sep is None else 1, C.c_void_p(out.ptr), *_strides(out), ws, wsn)
     elif sep is not None:
         (ky, kyp), (kx, kxp) = _kern(sep[0]), _kern(sep[1])
         ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV_SEP, *cube.shape, len(ky), len(kx))
         _lib.call("spc_spatial_conv_sep_f32", cube.device, _sh(stream), C.byref(c), C.byref(m),
-                  kyp, len(ky), kxp, len(kx), C.c_void_p(out.ptr), 0, 0, ws, wsn)
+                  kyp, len(ky), kxp, len(kx), C.c_void_p(out.ptr), *_strides(out), ws, wsn)
     else:
         k, kp = _kern(k2)
         ws, wsn = workspace(cube.device, stream, _lib.WS_SPATIAL_CONV2D, *cube.shape, k2.shape[0], k2.shape[1])
         _lib.call("spc_spatial_conv2d_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), kp,
-                  k2.shape[0], k2.shape[1], C.c_void_p(out.ptr), 0, 0, ws, wsn)
+                  k2.shape[0], k2.shape[1], C.c_void_p(out.ptr), *_strides(out), ws, wsn)
     return out
 
 
@@ -795,12 +810,11 @@ def spectral_lerp(cube, lo, t, inv_dx, fill=np.nan, mask=None, out=None, stream=
     d_t = DeviceArray.from_numpy(np.asarray(t, dtype=np.float64), dev)
     d_inv = DeviceArray.from_numpy(np.asarray(inv_dx, dtype=np.float64), dev)
     name, dtype = _entry("spectral_lerp", cube)
-    if out is None:
-        out = DeviceArray((nz_out,) + cube.shape[1:], dtype, dev)
+    out = _out_cube(out, (nz_out,) + tuple(cube.shape[1:]), dtype, dev)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     _lib.call(name, dev, _sh(stream), C.byref(c), C.byref(m), nz_out,
               C.c_void_p(d_lo.ptr), C.c_void_p(d_t.ptr), C.c_void_p(d_inv.ptr), float(fill),
-              C.c_void_p(out.ptr), 0, 0)
+              C.c_void_p(out.ptr), *_strides(out))
     out._plan = (d_lo, d_t, d_inv)     # keep alive until the stream has consumed them
     return out
 
@@ -864,16 +878,13 @@ def resample_bilinear(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_fo
             raise ValueError("xs, ys must be 2-D maps of identical shape")
         ny_out, nx_out = xs.shape
         d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
-    if out is None:
-        out = DeviceArray((cube.shape[0], ny_out, nx_out), dtype, dev)
-    elif out.shape != (cube.shape[0], ny_out, nx_out) or out.dtype != dtype or getattr(out, "_is_view", False):
-        raise ValueError("out must be a contiguous %s (nz, ny_out, nx_out) DeviceArray" % dtype)
+    out = _out_cube(out, (cube.shape[0], ny_out, nx_out), dtype, dev)          # (a strided view carries its strides)
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
     c, m = _cube_c(cube), _mask_c(mask, cube)
     # (the float32 kernel alone takes a workspace)
     scratch = workspace(dev, stream, _lib.WS_RESAMPLE_BILINEAR, *cube.shape, ny_out, nx_out) if dtype == _F32 else ()
     _lib.call(name, dev, _sh(stream), C.byref(c), C.byref(m), float(fill),
-              ny_out, nx_out, C.c_void_p(d_xs.ptr), C.c_void_p(d_ys.ptr), C.c_void_p(out.ptr), 0, 0,
+              ny_out, nx_out, C.c_void_p(d_xs.ptr), C.c_void_p(d_ys.ptr), C.c_void_p(out.ptr), *_strides(out),
               C.c_void_p(foot.ptr) if foot is not None else None, int(order),
               C.c_void_p(any_valid.ptr) if any_valid is not None else None, *scratch)
     out._plan = (d_xs, d_ys)
@@ -961,8 +972,8 @@ def spatial_conv_mfma(cube, kernel2d, mask=None, stream=None, out=None, want_cub
     ky, kx = (np.ascontiguousarray(f, dtype=np.float64) for f in fac)
     dev = cube.device
     nz, ny, nx = cube.shape
-    if want_cube and out is None:
-        out = DeviceArray((nz, ny, nx), np.float32, dev)
+    if want_cube:
+        out = _contiguous_out(out, (nz, ny, nx), np.float32, dev)
     if want_m0 and m0 is None:
         m0 = DeviceArray((ny, nx), np.float64, dev)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
@@ -986,8 +997,8 @@ def spatial_conv_mfma_moments(cube, kernel2d, d_cen, dv=1.0, m1_add=0.0, mask=No
     ky, kx = (np.ascontiguousarray(f, dtype=np.float64) for f in fac)
     dev = cube.device
     nz, ny, nx = cube.shape
-    if want_cube and out is None:
-        out = DeviceArray((nz, ny, nx), np.float32, dev)
+    if want_cube:
+        out = _contiguous_out(out, (nz, ny, nx), np.float32, dev)
     maps = {w: DeviceArray((ny, nx), np.float64, dev) for w in want}
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     higher = ("m1" in maps) or ("m2" in maps)
@@ -1029,8 +1040,7 @@ def resample_spline(cube, xs, ys, order, stream=None, want_footprint=True, out=N
         ny_out, nx_out = xs.shape
         d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
     nz, ny, nx = cube.shape
-    if out is None:
-        out = DeviceArray((nz, ny_out, nx_out), np.float32, dev)
+    out = _contiguous_out(out, (nz, ny_out, nx_out), np.float32, dev)       # (written a slab of planes at a time, from out.ptr)
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
     per_plane = (ny + 2) * (nx + 2) * 8
     planes = int(max(1, min(nz, slab_bytes // per_plane, 65535)))
@@ -1177,10 +1187,9 @@ def percentile_axis0(cube, q, mask=None, center=None, scale=1.0, stream=None, ou
 
 def fill_masked(cube, mask=None, fill=np.nan, stream=None, out=None):
     """device copy with excluded voxels replaced by *fill* (MaskBase._filled, masks.py:197-237)."""
-    if out is None:
-        out = DeviceArray(cube.shape, np.float32, cube.device)
+    out = _out_cube(out, cube.shape, np.float32, cube.device)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
-    _lib.call("spc_fill_masked_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(fill), C.c_void_p(out.ptr), 0, 0)
+    _lib.call("spc_fill_masked_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(fill), C.c_void_p(out.ptr), *_strides(out))
     return out
 
 
