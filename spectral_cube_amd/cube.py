@@ -34,6 +34,7 @@ from . import _lib, masks as M, ops
 from .beam import Beam, BeamError
 from .device import DeviceArray
 from .kernels import kernel_array
+from .pending import Pending
 from .wcs import (SimpleWCS, check_same_spectral_kind, join_celestial_spectral, pix_cen_spatial, pix_size, reproject_pixel_map,
                   spectral_unit_scale)
 
@@ -117,6 +118,17 @@ _ALL_NAN = ("All values in reprojected cube are nan.  This can be caused"
             "setting ``roundtrip_coords=False``.  You might also check "
             "whether the WCS transformation produces valid pixel->world "
             "and world->pixel coordinates in each axis.")
+
+
+def _channel_plan(zs, nz):
+    """reproject onto a header with a spectral axis of its own (oracle_np.reproject_separable): target channels at the source
+    channel positions *zs*.  Positions inside [-0.5, nz - 0.5] are clipped to the cube and each output channel is the linear
+    blend of the two source planes around it.  Returns ops.spectral_lerp's plan: ``inside`` (bool per output channel),
+    ``lo`` (int32 lower plane, -1 outside: a NaN plane), ``t`` (weight of plane lo + 1) and ``ones`` (its unit spacing)."""
+    inside = (zs >= -0.5) & (zs <= nz - 0.5)
+    zc = np.clip(np.where(inside, zs, 0.0), 0.0, nz - 1.0)
+    z0 = np.minimum(np.floor(zc).astype(np.int64), nz - 2)
+    return inside, np.where(inside, z0, -1).astype(np.int32), zc - z0, np.ones(len(zs))
 
 
 class SliceWarning(UserWarning):
@@ -532,7 +544,8 @@ class SpectralCube:
                 raise ValueError("SpectralCube needs a 3-D (spectral, y, x) array")
         self._data = data                 # host ndarray or None
         self._dev = _dev                  # DeviceArray float32 or None
-        self._lazy = _lazy                # pending (op, parent, args) - see spectral_smooth
+        # the Pending record of a result that has not been computed yet (pending.py), or None; a bare callable is its run()
+        self._lazy = _lazy if _lazy is None or isinstance(_lazy, Pending) else Pending(run=_lazy)
         self._source = _source            # streaming.FitsSource / NdarraySource of an out-of-core cube, or None
         self._shape = tuple(data.shape) if data is not None else (
             tuple(_dev.shape) if _dev is not None else tuple(_shape))
@@ -668,8 +681,8 @@ class SpectralCube:
 
     def _strip_plan(self, filled=True):
         """(streamed source cube, fn(strip, mask spec, stream) -> result strip, result channels) when this cube is - or
-        is a pending per-spaxel operator (spectral_smooth, spectral_interpolate, sigma_clip_spectrally) on - a cube that
-        does not fit the HBM budget; None otherwise."""
+        is a pending operator with an out-of-core route (``Pending.strips`` / ``Pending.slabs``) on - a cube that does not
+        fit the HBM budget; None otherwise.  ``_run_plan`` chooses the route."""
         fill = self._fill_value
         if self._stream_source() is not None:
             if filled and self._mask is not None:
@@ -677,28 +690,15 @@ class SpectralCube:
             # (the strip buffer itself is recycled by the pipeline: hand out a copy)
             return self, (lambda dev, mspec, stream: ops.fill_masked(dev, None, fill, stream)), self._shape[0]
         lz = self._lazy
-        parent = getattr(lz, "parent", None)
-        if (self._dev is None and lz is not None and parent is not None and getattr(lz, "slab_fn", None) is not None
-                and parent._stream_source() is not None):
-            if filled and self._mask is not None and getattr(lz, "keeps_mask", False) and self._mask is parent._mask:
-                def slab_filled(dev, mspec, stream):     # (convolve_to: the parent's mask, on the parent's voxels)
-                    from . import streaming
-                    keep = streaming.original_include(parent, dev, mspec, stream)
-                    return ops.fill_masked(lz.slab_fn(dev, mspec, stream), keep, fill, stream)
-                return parent, slab_filled, self._shape[0]
-            return parent, lz.slab_fn, self._shape[0]        # (reprojection: NaN outside the footprint is its own fill)
-        if self._dev is not None or lz is None or parent is None or getattr(lz, "strip_fn", None) is None:
+        if self._dev is not None or lz is None or not (lz.slabs or lz.strips) or lz.parent._stream_source() is None:
             return None
-        if parent._stream_source() is None:
-            return None
-        keeps_parent_mask = self._mask is parent._mask
-        if filled and self._mask is not None and keeps_parent_mask:
+        parent, fn = lz.parent, lz.fn
+        if filled and self._mask is not None and lz.keeps_mask and self._mask is parent._mask:
             def fn(dev, mspec, stream):      # the parent's mask, evaluated on the parent's voxels (as _mask_spec does)
                 from . import streaming
                 keep = streaming.original_include(parent, dev, mspec, stream)
-                return ops.fill_masked(lz.strip_fn(dev, mspec, stream), keep, fill, stream)
-        else:
-            fn = lz.strip_fn             # (spectral_interpolate: the new mask is ~isnan(result), the data are their own fill)
+                return ops.fill_masked(lz.fn(dev, mspec, stream), keep, fill, stream)
+        # (otherwise the data are their own fill: NaN outside a reprojection's footprint, ~isnan(result) of spectral_interpolate)
         return parent, fn, self._shape[0]
 
     def stream_into(self, out):
@@ -715,13 +715,14 @@ class SpectralCube:
     def _run_plan(self, plan, sink):
         from . import streaming
         src, fn, nz_out = plan
-        if getattr(self._lazy, "slab_fn", None) is not None and self._dev is None:
-            streaming.map_slabs(src, fn, tuple(self._shape[1:]), sink)        # per-channel operator: slabs of whole planes
+        if self._lazy is not None and self._lazy.slabs and self._dev is None:
+            # per-channel operator: slabs of whole planes (a record with both routes too: no halo rows to read twice)
+            streaming.map_slabs(src, fn, tuple(self._shape[1:]), sink)
         else:
             streaming.map_strips(src, fn, nz_out, sink, halo=self._strip_halo())
 
     def _strip_halo(self):
-        return int(getattr(self._lazy, "halo", 0)) if (self._lazy is not None and self._dev is None) else 0
+        return self._lazy.halo if (self._lazy is not None and self._dev is None) else 0
 
     @classmethod
     def from_device(cls, dev, wcs=None, header=None, mask=None, **kw):
@@ -1141,7 +1142,7 @@ class SpectralCube:
         if wide:
             return self._new_wide_cube(run, shape=shape, wcs=wcs, mask=mask, plain=plain)
         make = (lambda **kw: SpectralCube._new_cube_with(self, **kw)) if plain else self._new_cube_with
-        return make(lazy=_Thunk(run), shape=tuple(shape) if shape is not None else self._shape, wcs=wcs, mask=mask)
+        return make(lazy=Pending(run=run), shape=tuple(shape) if shape is not None else self._shape, wcs=wcs, mask=mask)
 
     def _derived(self, fn, **kw):
         """_result_cube of *fn*(data, mask, view) applied to ``_operand()``, on the path decided now"""
@@ -1153,10 +1154,10 @@ class SpectralCube:
         (pending until first used; the Dask class keeps the chunk dtype, dask_spectral_cube.py:829).  Its spectral moments,
         reductions, statistics() and further smoothing / interpolation run in float64; an operator without a float64 form
         narrows it with a PrecisionWarning, like a float64 source."""
-        # the narrowing thunk holds the result's DATA TOKEN, never the cube: out._lazy -> thunk -> out was a reference cycle
+        # the narrowing record holds the result's DATA TOKEN, never the cube: out._lazy -> record -> out was a reference cycle
         # that kept a dropped float64 cube (8 B / voxel of HBM) and its parent alive until a generation-2 collection
         tokens = []
-        narrow = _Thunk(lambda: ops.narrow_f64(_token_dev64(tokens[0])))
+        narrow = Pending(run=lambda: ops.narrow_f64(_token_dev64(tokens[0])))
         make = (lambda **kw: SpectralCube._new_cube_with(self, **kw)) if plain else self._new_cube_with      # plain: not the subclass's (beams)
         out = make(lazy=narrow, shape=tuple(shape) if shape is not None else self._shape, wcs=wcs, mask=mask)
         out._data_id.lazy64 = fn64
@@ -1229,20 +1230,18 @@ class SpectralCube:
                 # resident path materialises the smoothed cube; here the smoothed STRIP is materialised, then reduced.
                 # The maps are rebuilt from the first strip on (a strip's rows are written whole, nothing is accumulated).
                 lz = self._lazy
-                return streaming.moments(lz.parent, want, d_cen, dv, cref + spec0, pre=lz.strip_fn,
-                                         halo=int(getattr(lz, "halo", 0)))
+                return streaming.moments(lz.parent, want, d_cen, dv, cref + spec0, pre=lz.fn, halo=lz.halo)
         if fused_kernel is None and self._stream_source() is not None:
             from . import streaming
             return streaming.moments(self, want, d_cen, dv, cref + spec0)
         lz = self._lazy
-        if (fused_kernel is None and self._dev is None and lz is not None and getattr(lz, "strip_fn", None) is not None
-                and getattr(lz, "parent", None) is not None and lz.parent._stream_source() is not None
+        if (fused_kernel is None and self._dev is None and lz is not None and lz.strips and lz.parent._stream_source() is not None
                 and lz.parent._mask is self._mask and tuple(lz.parent._shape) == tuple(self._shape)):
             # out-of-core parent and a pending cube -> cube operator that keeps the parent's mask (spatial_smooth outside the
             # all-valid algebraic case: strip + halo rows, the strip's own rows reduced; sigma_clip_spectrally; a
             # spectral_smooth too wide to fuse): operator and reduction strip by strip
             from . import streaming
-            return streaming.moments(lz.parent, want, d_cen, dv, cref + spec0, pre=lz.strip_fn, halo=int(getattr(lz, "halo", 0)))
+            return streaming.moments(lz.parent, want, d_cen, dv, cref + spec0, pre=lz.fn, halo=lz.halo)
         if fused_kernel is not None:
             parent, karr = fused_kernel
             try:
@@ -1259,7 +1258,7 @@ class SpectralCube:
         smooth -> moment can run fused (dask_spectral_cube.py:836-840 keeps the
         original mask, so the semantics are identical)."""
         lz = self._lazy
-        if (lz is not None and getattr(lz, "op", None) == "spectral_smooth" and self._dev is None
+        if (lz is not None and lz.op == "spectral_smooth" and self._dev is None
                 and lz.parent._mask is self._mask and lz.fusable):
             return (lz.parent, lz.kernel)
         return None
@@ -1273,12 +1272,12 @@ class SpectralCube:
         shortcut does not apply (mask terms other than isfinite, any invalid voxel, S0 == 0) -
         the caller then materialises the smoothed cube."""
         lz = self._lazy
-        if not (lz is not None and getattr(lz, "op", None) == "spatial_smooth" and self._dev is None
+        if not (lz is not None and lz.op == "spatial_smooth" and self._dev is None
                 and lz.parent._mask is self._mask):
             return None
         parent = lz.parent
         spec = parent._mask_spec()
-        split_ok = getattr(lz, "arithmetic", None) != "f32"        # (asked for float32 multiply-adds: the fused forms are split-form kernels)
+        split_ok = lz.arithmetic != "f32"        # (asked for float32 multiply-adds: the fused forms are split-form kernels)
         if not split_ok and spec.array is not None:
             return None
         if tuple(want) == ("m0",) and parent._stream_source() is None and (spec.array is not None or (spec.flags & ~_lib.MASK_FINITE) == 0):
@@ -1744,10 +1743,9 @@ class SpectralCube:
         if self._stream_source() is not None:
             # out of core: a pending operator; write() / stream_into() run it strip by strip
             parent, sig = self, float(threshold)
-            thunk = _Thunk(lambda: ops.sigma_clip_axis0(parent._device_data(), sigma=sig, mask=parent._mask_spec(), **kwargs))
-            thunk.parent = parent
-            thunk.strip_fn = lambda dev, mspec, stream: ops.sigma_clip_axis0(dev, sigma=sig, mask=mspec, stream=stream, **kwargs)
-            return self._new_cube_with(lazy=thunk, shape=self._shape)
+            lazy = Pending(lambda dev, mspec, stream: ops.sigma_clip_axis0(dev, sigma=sig, mask=mspec, stream=stream, **kwargs),
+                           op="sigma_clip_spectrally", parent=parent, strips=True, keeps_mask=True)
+            return self._new_cube_with(lazy=lazy, shape=self._shape)
         if self._shape[0] <= 4096 and self._runs_wide():
             parent, kw = self, dict(kwargs)
             return self._new_wide_cube(lambda: ops.sigma_clip_axis0_f64(parent._device_data64(), sigma=float(threshold),
@@ -2099,23 +2097,11 @@ class SpectralCube:
         parent = self
         if self._runs_wide():
             # a float64 cube stays float64 (the Dask class keeps the chunk dtype, dask_spectral_cube.py:829) and is resident:
-            # none of what the float32 class below carries for a following moment or an out-of-core parent applies
+            # none of what the float32 record below carries for a following moment or an out-of-core parent applies
             return self._derived(lambda data, mask, view: ops.spectral_conv(data, karr, mask=mask))
-
-        class _Lazy:
-            op = "spectral_smooth"
-            fusable = True
-
-            def __init__(self):
-                self.parent, self.kernel = parent, karr
-
-            def __call__(self):
-                return ops.spectral_conv(parent._device_data(), karr, mask=parent._mask_spec())
-
-            def strip_fn(self, dev, mspec, stream):          # one row strip of an out-of-core parent
-                return ops.spectral_conv(dev, karr, mask=mspec, stream=stream)
-
-        return self._new_cube_with(lazy=_Lazy(), shape=self._shape)
+        lazy = Pending(lambda dev, mspec, stream: ops.spectral_conv(dev, karr, mask=mspec, stream=stream),
+                       op="spectral_smooth", parent=parent, strips=True, keeps_mask=True, kernel=karr, fusable=True)
+        return self._new_cube_with(lazy=lazy, shape=self._shape)
 
     def spatial_smooth(self, kernel, convolve=None, raise_error_jybm=True, arithmetic=None, **kwargs):
         """Smooth every channel with a 2-D kernel (dask_spectral_cube.py:962-993).  Extra keyword
@@ -2132,31 +2118,13 @@ class SpectralCube:
         parent = self
         if self._runs_wide():        # (resident: no strip / slab form; the float64 stencils have one arithmetic)
             return self._derived(lambda data, mask, view: ops.spatial_conv(data, karr, mask=mask))
-
-        class _Lazy:
-            op = "spatial_smooth"
-            fusable = False
-
-            def __init__(self):
-                self.parent, self.kernel, self.arithmetic = parent, karr, arithmetic
-
-            def __call__(self):
-                return ops.spatial_conv(parent._device_data(), karr, mask=parent._mask_spec(), arithmetic=arithmetic)
-
-            halo = karr.shape[0] // 2        # rows a strip of an out-of-core parent needs from its neighbours
-
-            def strip_fn(self, dev, mspec, stream):
-                return ops.spatial_conv(dev, karr, mask=mspec, stream=stream, arithmetic=arithmetic)
-
-            # cube -> cube (write / stream_into) of an out-of-core parent goes in slabs of whole planes instead: no halo rows
-            # to read twice (29 x 29 taps, 8 GiB host array: 8.3 GB/s each way in halo strips, the link's rate in slabs); the
-            # halo strips remain for a following moment, which needs whole spaxels
-            keeps_mask = True
-
-            def slab_fn(self, dev, mspec, stream):
-                return ops.spatial_conv(dev, karr, mask=mspec, stream=stream, arithmetic=arithmetic)
-
-        return self._new_cube_with(lazy=_Lazy(), shape=self._shape)
+        # both routes: cube -> cube (write / stream_into) of an out-of-core parent goes in slabs of whole planes - no halo rows
+        # to read twice (29 x 29 taps, 8 GiB host array: 8.3 GB/s each way in halo strips, the link's rate in slabs); the
+        # strips, with the halo rows they need from their neighbours, remain for a following moment, which needs whole spaxels
+        lazy = Pending(lambda dev, mspec, stream: ops.spatial_conv(dev, karr, mask=mspec, stream=stream, arithmetic=arithmetic),
+                       op="spatial_smooth", parent=parent, strips=True, slabs=True, halo=karr.shape[0] // 2, keeps_mask=True,
+                       kernel=karr, arithmetic=arithmetic)
+        return self._new_cube_with(lazy=lazy, shape=self._shape)
 
     # ---- median and rank filters -----------------------------------------------------------------
     def _rank_filtered(self, sizes, axis_lengths, filter, kwargs):
@@ -2181,22 +2149,9 @@ class SpectralCube:
                       nan_excluded=_nan_term_dropped(parent, view))
         if self._runs_wide():            # (resident, float64 throughout)
             return self._derived(run)
-
-        class _Lazy:
-            op = "spectral_filter" if spectral else "spatial_filter"
-            fusable = False
-            keeps_mask = True
-
-            def __init__(self):
-                self.parent = parent
-
-            def __call__(self):
-                return run(parent._device_data(), parent._mask_spec(), parent)
-
-        def part(dev, mspec, stream):    # a strip of whole spaxels / a slab of whole planes of an out-of-core parent
-            return run(dev, mspec, parent, stream)
-        lazy = _Lazy()
-        setattr(lazy, "strip_fn" if spectral else "slab_fn", part)
+        # (of an out-of-core parent: strips of whole spaxels along the spectral axis, slabs of whole planes per plane)
+        lazy = Pending(lambda dev, mspec, stream: run(dev, mspec, parent, stream), op="spectral_filter" if spectral else "spatial_filter",
+                       parent=parent, strips=spectral, slabs=not spectral, keeps_mask=True)
         return self._new_cube_with(lazy=lazy, shape=self._shape)
 
     def spectral_filter(self, ksize, filter, **kwargs):
@@ -2279,23 +2234,17 @@ class SpectralCube:
         karr = beam.deconvolve(self.beam).as_kernel(pixscale)
         is_jybm = str(self._unit).replace(" ", "").upper() in ("JY/BEAM", "JYBEAM-1", "JY/BM")
         ratio = beam.sr / self.beam.sr if is_jybm else 1.0
-        def run(data, mask, view=None):
-            res = ops.spatial_conv(data, karr, mask=mask)
-            return ops.scale_inplace(res, ratio) if ratio != 1.0 else res
+        def run(data, mask, view=None, stream=None):
+            res = ops.spatial_conv(data, karr, mask=mask, stream=stream)
+            return ops.scale_inplace(res, ratio, stream=stream) if ratio != 1.0 else res
         if self._runs_wide():        # (pending, like every float64 result; the float32 result below is made at once)
             return self._derived(run).with_beam(beam, raise_error_jybm=False)
         if self._stream_source() is not None:
             # out of core: one kernel for every channel, so slabs of whole planes; pending until write() / stream_into()
-            parent = self
-
-            def slab(dev, mspec, stream):
-                res = ops.spatial_conv(dev, karr, mask=mspec, stream=stream)
-                if ratio != 1.0:
-                    ops.scale_inplace(res, ratio, stream=stream)
-                return res
-            thunk = _Thunk(lambda: parent._device_data())           # (never resident: raises HugeCubeError with the budget)
-            thunk.parent, thunk.slab_fn, thunk.keeps_mask = parent, slab, True
-            return self._new_cube_with(lazy=thunk, shape=self._shape).with_beam(beam, raise_error_jybm=False)
+            # (never resident: materialising asks the parent for its samples, which raises HugeCubeError with the budget)
+            lazy = Pending(lambda dev, mspec, stream: run(dev, mspec, None, stream), op="convolve_to", parent=self, slabs=True,
+                           keeps_mask=True)
+            return self._new_cube_with(lazy=lazy, shape=self._shape).with_beam(beam, raise_error_jybm=False)
         new = self._new_cube_with(dev=run(self._device_data(), self._mask_spec()))
         return new.with_beam(beam, raise_error_jybm=False)
 
@@ -2335,27 +2284,21 @@ class SpectralCube:
             plan = (lo, t, inv_dx)
         if rout:
             plan = tuple(p[::-1].copy() for p in plan)
-        parent = self
 
-        def run():
-            return ops.spectral_lerp(parent._device_data(), plan[0], plan[1], plan[2], fill,
-                                     mask=parent._mask_spec())
+        def lerp(dev, mspec, stream=None):
+            return ops.spectral_lerp(dev, plan[0], plan[1], plan[2], fill, mask=mspec, stream=stream)
 
         crval = g_sorted[0] if not rout else g_sorted[-1]
         cdelt = outdiff if not rout else -outdiff
         newwcs = self._wcs.with_spectral(crval, cdelt, 1.0)
         if self._runs_wide():
-            out = self._derived(lambda data, mask, view: ops.spectral_lerp(data, plan[0], plan[1], plan[2], fill, mask=mask),
-                                shape=(len(grid),) + self._shape[1:], wcs=newwcs, mask=False)
+            out = self._derived(lambda data, mask, view: lerp(data, mask), shape=(len(grid),) + self._shape[1:], wcs=newwcs, mask=False)
             out._mask = M.NotNaNMask(out)
             return out
-        # float32: the thunk also carries what a following reproject and an out-of-core parent need
-        thunk = _Thunk(run)
-        thunk.parent = parent
-        thunk.lerp = (plan, fill)          # (a following reproject folds the interpolation into its resampling kernel)
-        thunk.strip_fn = lambda dev, mspec, stream: ops.spectral_lerp(dev, plan[0], plan[1], plan[2], fill, mask=mspec, stream=stream)
-        out = self._new_cube_with(lazy=thunk, shape=(len(grid),) + self._shape[1:], wcs=newwcs,
-                                  mask=False)
+        # float32: the record also carries what an out-of-core parent needs (row strips) and what a following reproject
+        # needs to fold the interpolation into its resampling kernel (the plan)
+        lazy = Pending(lerp, op="spectral_interpolate", parent=self, strips=True, lerp=(plan, fill))
+        out = self._new_cube_with(lazy=lazy, shape=(len(grid),) + self._shape[1:], wcs=newwcs, mask=False)
         out._mask = M.NotNaNMask(out)
         return out
 
@@ -2410,146 +2353,140 @@ class SpectralCube:
             _lib.require_gpu()
             xs, ys = ops.wcs_pixel_map(self._wcs, newwcs, (ny_out, nx_out), self.device)
         if self._stream_source() is not None:
-            # out of core: every channel is resampled on its own, so the cube goes through the device in slabs of whole
-            # planes; the result stays pending until write() / stream_into() (it does not fit the budget either)
-            from . import streaming
             if zs is not None:
                 return self._reproject_streamed_with_spectral_axis(newwcs, zs, (ny_out, nx_out), order, filled)
-            probe = DeviceArray.from_numpy(np.zeros((1,) + tuple(self._shape[1:]), np.float32), self.device)
-            _, foot = ops.resample_bilinear(probe, xs, ys, fill=np.nan, order=order)
-            footprint = foot.get().astype(bool)
-            if not footprint.any():
-                raise ValueError("All values in reprojected cube are nan.  This can be caused"
-                                 " by an error in which coordinates do not 'round-trip'.  Try "
-                                 "setting ``roundtrip_coords=False``.  You might also check "
-                                 "whether the WCS transformation produces valid pixel->world "
-                                 "and world->pixel coordinates in each axis.")
-            parent, fill = self, float(self._fill_value)
-            thunk = _Thunk(lambda: parent._device_data())           # (never resident: raises HugeCubeError with the budget)
-            thunk.parent = parent
-            thunk.slab_fn = lambda dev, mspec, stream: ops.resample_bilinear(dev, xs, ys, fill=fill, mask=mspec if filled else None,
-                                                                            order=order, stream=stream, want_footprint=False)[0]
-            shape = (nz, ny_out, nx_out)
-            out = self._new_cube_with(lazy=thunk, wcs=newwcs, mask=False, shape=shape)
-            out._mask = M.BooleanArrayMask(footprint[None], newwcs, shape=shape)
-            out._footprint = footprint
-            return out
+            return self._reproject_streamed(newwcs, xs, ys, order, filled)
         if order in (0, 1) and self._runs_wide():
-            # a float64 cube: float64 weights and results (reproject_interp computes in float64); a cube header's own spectral
-            # axis is blended from the resampled float64 planes afterwards
-            flag = DeviceArray((1,), np.uint32, self.device)
-            mask64 = self._mask_spec64() if filled else None
-            fillv = float(self._fill_value)
-            if filled and not np.isnan(fillv) and self._mask is not None and M.contains(self._mask, M.NotNaNMask) \
-                    and not M.contains(self._mask, M.InvertedMask):
-                inc = ops.mask_include(self._device_data64(), mask64, nan_excluded=True)
-                mask64 = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
-            dev64, foot = ops.resample_bilinear(self._device_data64(), xs, ys, fill=fillv, mask=mask64, order=order, any_valid=flag)
-            footprint = foot.get().astype(bool)
-            valid3d = footprint[None]
-            nothing = int(flag.get()[0]) == 0
-            if zs is not None:
-                inside = (zs >= -0.5) & (zs <= nz - 0.5)
-                zc = np.clip(np.where(inside, zs, 0.0), 0.0, nz - 1.0)
-                z0 = np.minimum(np.floor(zc).astype(np.int64), nz - 2)
-                dev64 = ops.spectral_lerp(dev64, np.where(inside, z0, -1).astype(np.int32), zc - z0, np.ones(len(zs)), np.nan)
-                if not inside.all():
-                    valid3d = footprint[None] & inside[:, None, None]
-                nothing = nothing or not inside.any()
-            if nothing:
-                raise ValueError(_ALL_NAN)
-            out = self._new_wide_cube(lambda: dev64, shape=dev64.shape, wcs=newwcs, mask=False)
-            out._mask = M.BooleanArrayMask(valid3d, newwcs, shape=dev64.shape)
-            out._footprint = footprint
-            return out
+            return self._reproject_f64(newwcs, xs, ys, zs, order, filled)
         folded = self._pending_interpolation(order) if zs is None else None
         if folded is not None:
-            # spectral_interpolate(...).reproject(...): both are linear interpolations with NaN propagation, so they commute -
-            # every INPUT plane is resampled once and the output channels are blended from neighbouring resampled planes in
-            # the same kernel (ops.resample_bilinear_lerp): one read of the parent, one write of the result, the
-            # interpolated cube is never formed
-            parent, plan = folded
-            flag = DeviceArray((1,), np.uint32, self.device)
-            dev, foot = ops.resample_bilinear_lerp(parent._device_data(), xs, ys, plan[0], plan[1], plan[2], fill=np.nan,
-                                                   mask=parent._mask_spec(), order=order, any_valid=flag)
-            footprint = foot.get().astype(bool)
-            if int(flag.get()[0]) == 0:
-                raise ValueError(_ALL_NAN)
-            out = self._new_cube_with(dev=dev, wcs=newwcs, mask=False, shape=dev.shape)
-            out._mask = M.BooleanArrayMask(footprint[None], newwcs, shape=dev.shape)
-            out._footprint = footprint
-            return out
-        mask = self._mask_spec() if filled else None
-        if filled and not np.isnan(float(self._fill_value)) and self._mask is not None and M.contains(self._mask, M.NotNaNMask) \
+            return self._reproject_folded(newwcs, xs, ys, order, *folded)
+        if order >= 2:
+            return self._reproject_spline(newwcs, xs, ys, order, filled)
+        return self._reproject_bilinear(newwcs, xs, ys, zs, order, filled)
+
+    def _resample_mask(self, filled, wide):
+        """the mask a resampler fills under (None when not *filled*), lowered for the float32 or (*wide*) float64 kernels"""
+        if not filled:
+            return None
+        data, mspec, _ = self._operand(wide)
+        if not np.isnan(float(self._fill_value)) and self._mask is not None and M.contains(self._mask, M.NotNaNMask) \
                 and not M.contains(self._mask, M.InvertedMask):
             # ~isnan(data) lowers to nothing (NaN samples never take part in a reduction), but HERE the excluded voxels are
             # replaced by a fill value that is a number (spectral_cube.py:2709-2712): the NaN samples must be named
-            inc = ops.mask_include(self._device_data(), mask, nan_excluded=True)
-            mask = ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, inc)
-        flag = DeviceArray((1,), np.uint32, self.device)
-        if order >= 2:
-            # scipy's recursive spline prefilter (which reproject_interp runs along all three axes of the NaN-filled cube)
-            # turns ONE non-finite sample into NaN everywhere: the reference then raises "All values ... are nan"
-            src = self._device_data()
-            if mask is not None:
-                src = ops.fill_masked(src, mask, float(self._fill_value))
-            finite = ops.stats_global(src, mask=ops.MaskSpec(_lib.MASK_FINITE))["npts"]
-            if int(finite) != int(np.prod(self._shape, dtype=np.int64)):
-                raise ValueError("All values in reprojected cube are nan.  This can be caused"
-                                 " by an error in which coordinates do not 'round-trip'.  Try "
-                                 "setting ``roundtrip_coords=False``.  You might also check "
-                                 "whether the WCS transformation produces valid pixel->world "
-                                 "and world->pixel coordinates in each axis.")
-            dev, foot = ops.resample_spline(src, xs, ys, order)
-            flag = None
+            return ops.MaskSpec(_lib.MASK_ARRAY, 0.0, 0.0, ops.mask_include(data, mspec, nan_excluded=True))
+        return mspec
+
+    def _reprojected(self, dev, footprint, inside, newwcs, shape=None):
+        """the result cube of a reprojection: *dev* its float32 or float64 DeviceArray, or the Pending record of a result
+        that is never resident (with its *shape*); the new mask is the *footprint*, on the output channels *inside* the
+        source's spectral range (None: all of them); ``_footprint`` keeps the 2-D map"""
+        if isinstance(dev, Pending):
+            out = self._new_cube_with(lazy=dev, wcs=newwcs, mask=False, shape=shape)
+        elif dev.dtype == np.float64:
+            out = self._new_wide_cube(lambda: dev, shape=dev.shape, wcs=newwcs, mask=False)
         else:
-            zfold = False
-            if zs is not None:
-                # reproject_separable: channel positions inside [-0.5, nz - 0.5] are clipped to the cube,
-                # each output channel is the linear blend of the two resampled planes around it
-                inside = (zs >= -0.5) & (zs <= nz - 0.5)
-                zc = np.clip(np.where(inside, zs, 0.0), 0.0, nz - 1.0)
-                z0 = np.minimum(np.floor(zc).astype(np.int64), nz - 2)
-                zlo = np.where(inside, z0, -1).astype(np.int32)
-                zfold = ops.lerp_plan_folds(zlo) and os.environ.get("SPC_REPROJECT_FOLD", "1") != "0"
-            if zfold:
-                # ascending target channels: the blend rides in the resampling kernel (one pass, no resampled copy of the cube)
-                dev, foot = ops.resample_bilinear_lerp(self._device_data(), xs, ys, zlo, zc - z0, np.ones(len(zs)),
-                                                       fill=float(self._fill_value), mask=mask, order=order, any_valid=flag)
-            else:
-                dev, foot = ops.resample_bilinear(self._device_data(), xs, ys, fill=float(self._fill_value),
-                                                  mask=mask, order=order, any_valid=flag)
-        footprint = foot.get().astype(bool)
-        valid3d = footprint[None]
-        if zs is not None:
-            if not inside.all():
-                valid3d = footprint[None] & inside[:, None, None]
-            if zfold:
-                nothing = (not inside.any()) or int(flag.get()[0]) == 0
-            else:
-                dev = ops.spectral_lerp(dev, zlo, zc - z0, np.ones(len(zs)), np.nan)
-                nothing = (not inside.any()) or ops.stats_global(dev)["npts"] == 0
-        elif flag is None:
-            nothing = not footprint.any()
-        else:
-            nothing = int(flag.get()[0]) == 0
-        if nothing:
-            raise ValueError("All values in reprojected cube are nan.  This can be caused"
-                             " by an error in which coordinates do not 'round-trip'.  Try "
-                             "setting ``roundtrip_coords=False``.  You might also check "
-                             "whether the WCS transformation produces valid pixel->world "
-                             "and world->pixel coordinates in each axis.")
-        out = self._new_cube_with(dev=dev, wcs=newwcs, mask=False, shape=dev.shape)
-        out._mask = M.BooleanArrayMask(valid3d, newwcs, shape=dev.shape)
+            out = self._new_cube_with(dev=dev, wcs=newwcs, mask=False, shape=dev.shape)
+        valid3d = footprint[None] if inside is None or inside.all() else footprint[None] & inside[:, None, None]
+        out._mask = M.BooleanArrayMask(valid3d, newwcs, shape=out._shape)
         out._footprint = footprint
         return out
+
+    def _reproject_streamed(self, newwcs, xs, ys, order, filled):
+        """out of core: every channel is resampled on its own, so the cube goes through the device in slabs of whole
+        planes; the result stays pending until write() / stream_into() (it does not fit the budget either, so
+        materialising it raises the parent's HugeCubeError).  Footprint and all-NaN error: a one-plane probe of the map."""
+        probe = DeviceArray.from_numpy(np.zeros((1,) + tuple(self._shape[1:]), np.float32), self.device)
+        _, foot = ops.resample_bilinear(probe, xs, ys, fill=np.nan, order=order)
+        footprint = foot.get().astype(bool)
+        if not footprint.any():
+            raise ValueError(_ALL_NAN)
+        fill = float(self._fill_value)
+        lazy = Pending(lambda dev, mspec, stream: ops.resample_bilinear(dev, xs, ys, fill=fill, mask=mspec if filled else None,
+                                                                        order=order, stream=stream, want_footprint=False)[0],
+                       op="reproject", parent=self, slabs=True)
+        return self._reprojected(lazy, footprint, None, newwcs, shape=(self._shape[0],) + tuple(xs.shape))
+
+    def _reproject_f64(self, newwcs, xs, ys, zs, order, filled):
+        """a float64 cube: float64 weights and results (reproject_interp computes in float64); a cube header's own spectral
+        axis is blended from the resampled float64 planes afterwards"""
+        flag = DeviceArray((1,), np.uint32, self.device)
+        mask64 = self._resample_mask(filled, True)
+        dev64, foot = ops.resample_bilinear(self._device_data64(), xs, ys, fill=float(self._fill_value), mask=mask64, order=order,
+                                            any_valid=flag)
+        footprint = foot.get().astype(bool)
+        nothing, inside = int(flag.get()[0]) == 0, None
+        if zs is not None:
+            inside, lo, t, ones = _channel_plan(zs, self._shape[0])
+            dev64 = ops.spectral_lerp(dev64, lo, t, ones, np.nan)
+            nothing = nothing or not inside.any()
+        if nothing:
+            raise ValueError(_ALL_NAN)
+        return self._reprojected(dev64, footprint, inside, newwcs)
+
+    def _reproject_folded(self, newwcs, xs, ys, order, parent, plan):
+        """spectral_interpolate(...).reproject(...): both are linear interpolations with NaN propagation, so they commute -
+        every INPUT plane is resampled once and the output channels are blended from neighbouring resampled planes in the
+        same kernel (ops.resample_bilinear_lerp): one read of the parent, one write of the result, the interpolated cube
+        is never formed"""
+        flag = DeviceArray((1,), np.uint32, self.device)
+        dev, foot = ops.resample_bilinear_lerp(parent._device_data(), xs, ys, plan[0], plan[1], plan[2], fill=np.nan,
+                                               mask=parent._mask_spec(), order=order, any_valid=flag)
+        footprint = foot.get().astype(bool)
+        if int(flag.get()[0]) == 0:
+            raise ValueError(_ALL_NAN)
+        return self._reprojected(dev, footprint, None, newwcs)
+
+    def _reproject_spline(self, newwcs, xs, ys, order, filled):
+        """order 2 / 3 of a resident float32 cube (the planner has refused a spectral axis of the target's own)"""
+        mask = self._resample_mask(filled, False)
+        # scipy's recursive spline prefilter (which reproject_interp runs along all three axes of the NaN-filled cube)
+        # turns ONE non-finite sample into NaN everywhere: the reference then raises "All values ... are nan"
+        src = self._device_data()
+        if mask is not None:
+            src = ops.fill_masked(src, mask, float(self._fill_value))
+        finite = ops.stats_global(src, mask=ops.MaskSpec(_lib.MASK_FINITE))["npts"]
+        if int(finite) != int(np.prod(self._shape, dtype=np.int64)):
+            raise ValueError(_ALL_NAN)
+        dev, foot = ops.resample_spline(src, xs, ys, order)
+        footprint = foot.get().astype(bool)
+        if not footprint.any():
+            raise ValueError(_ALL_NAN)
+        return self._reprojected(dev, footprint, None, newwcs)
+
+    def _reproject_bilinear(self, newwcs, xs, ys, zs, order, filled):
+        """order 0 / 1 of a resident float32 cube; *zs*: the target's channels in source channel units when the header
+        carries a spectral axis of its own (reproject_separable: each output channel is the linear blend of the two
+        resampled planes around it)"""
+        fill, mask = float(self._fill_value), self._resample_mask(filled, False)
+        flag = DeviceArray((1,), np.uint32, self.device)
+        inside = None
+        if zs is not None:
+            inside, lo, t, ones = _channel_plan(zs, self._shape[0])
+        if zs is not None and ops.lerp_plan_folds(lo) and os.environ.get("SPC_REPROJECT_FOLD", "1") != "0":
+            # ascending target channels: the blend rides in the resampling kernel (one pass, no resampled copy of the cube)
+            dev, foot = ops.resample_bilinear_lerp(self._device_data(), xs, ys, lo, t, ones, fill=fill, mask=mask, order=order,
+                                                   any_valid=flag)
+            folded = True
+        else:
+            dev, foot = ops.resample_bilinear(self._device_data(), xs, ys, fill=fill, mask=mask, order=order, any_valid=flag)
+            folded = False
+        footprint = foot.get().astype(bool)
+        if zs is not None and not folded:
+            dev = ops.spectral_lerp(dev, lo, t, ones, np.nan)
+            nothing = (not inside.any()) or ops.stats_global(dev)["npts"] == 0
+        else:
+            nothing = (zs is not None and not inside.any()) or int(flag.get()[0]) == 0
+        if nothing:
+            raise ValueError(_ALL_NAN)
+        return self._reprojected(dev, footprint, inside, newwcs)
 
     def _pending_interpolation(self, order):
         """(parent, plan) when this cube is a spectral_interpolate result that has not been formed yet and a reprojection of
         order 0 / 1 may fold the interpolation in: the parent is resident (or fits), nothing replaced the NaN fill or the
         ~isnan mask in between, the plan's channels ascend"""
         lz = self._lazy
-        if self._dev is not None or lz is None or getattr(lz, "lerp", None) is None or order not in (0, 1):
+        if self._dev is not None or lz is None or lz.lerp is None or order not in (0, 1):
             return None
         if os.environ.get("SPC_REPROJECT_FOLD", "1") == "0":
             return None
@@ -2576,27 +2513,13 @@ class SpectralCube:
         spatial = self.reproject(celestial, order=order, filled=filled)      # (pending; raises the all-NaN ValueError itself)
         mid = np.empty((nz, ny_out, nx_out), dtype=np.float32)
         spatial.stream_into(mid)
-        footprint = spatial._footprint
         midcube = SpectralCube(mid, wcs=celestial, device=self.device, allow_huge_operations=self.allow_huge_operations)
-        inside = (zs >= -0.5) & (zs <= nz - 0.5)
-        zc = np.clip(np.where(inside, zs, 0.0), 0.0, nz - 1.0)
-        z0 = np.minimum(np.floor(zc).astype(np.int64), nz - 2)
-        lo = np.where(inside, z0, -1).astype(np.int32)
-        t, ones = zc - z0, np.ones(len(zs))
+        inside, lo, t, ones = _channel_plan(zs, nz)
         if not inside.any():
-            raise ValueError("All values in reprojected cube are nan.  This can be caused"
-                             " by an error in which coordinates do not 'round-trip'.  Try "
-                             "setting ``roundtrip_coords=False``.  You might also check "
-                             "whether the WCS transformation produces valid pixel->world "
-                             "and world->pixel coordinates in each axis.")
-        thunk = _Thunk(lambda: ops.spectral_lerp(midcube._device_data(), lo, t, ones, np.nan))
-        thunk.parent = midcube
-        thunk.strip_fn = lambda dev, mspec, stream: ops.spectral_lerp(dev, lo, t, ones, np.nan, mask=mspec, stream=stream)
-        shape = (len(zs), ny_out, nx_out)
-        out = self._new_cube_with(lazy=thunk, wcs=newwcs, mask=False, shape=shape)
-        out._mask = M.BooleanArrayMask(footprint[None] & inside[:, None, None], newwcs, shape=shape)
-        out._footprint = footprint
-        return out
+            raise ValueError(_ALL_NAN)
+        lazy = Pending(lambda dev, mspec, stream: ops.spectral_lerp(dev, lo, t, ones, np.nan, mask=mspec, stream=stream),
+                       op="reproject", parent=midcube, strips=True)
+        return self._reprojected(lazy, spatial._footprint, inside, newwcs, shape=(len(zs), ny_out, nx_out))
 
     def __repr__(self):
         return "SpectralCube(hip) with shape=%s%s" % (self._shape, " and unit=%s" % self._unit if self._unit else "")
@@ -2768,11 +2691,10 @@ class VaryingResolutionSpectralCube(SpectralCube):
         if self._stream_source() is not None:
             # out of core: slabs of whole planes (every channel has its own kernel, the slab knows its first channel);
             # pending until write() / stream_into()
-            parent = self
-            thunk = _Thunk(lambda: parent._device_data())           # (never resident: raises HugeCubeError with the budget)
-            thunk.parent, thunk.keeps_mask = parent, True
-            thunk.slab_fn = lambda dev, mspec, stream: runs(dev, mspec, int(getattr(dev, "z0", 0)), stream)
-            new = SpectralCube._new_cube_with(self, lazy=thunk, shape=self._shape)
+            # (never resident: materialising asks the parent for its samples, which raises HugeCubeError with the budget)
+            lazy = Pending(lambda dev, mspec, stream: runs(dev, mspec, int(getattr(dev, "z0", 0)), stream), op="convolve_to",
+                           parent=self, slabs=True, keeps_mask=True)
+            new = SpectralCube._new_cube_with(self, lazy=lazy, shape=self._shape)
             return new.with_beam(beam, raise_error_jybm=False)
         new = SpectralCube._new_cube_with(self, dev=runs(self._device_data(), self._mask_spec(), 0))
         return new.with_beam(beam, raise_error_jybm=False)
@@ -2790,17 +2712,6 @@ class VaryingResolutionSpectralCube(SpectralCube):
     def __repr__(self):
         return "VaryingResolutionSpectralCube(hip) with shape=%s%s" % (
             self._shape, " and unit=%s" % self._unit if self._unit else "")
-
-
-class _Thunk:
-    op = "thunk"
-    fusable = False
-
-    def __init__(self, fn):
-        self._fn = fn
-
-    def __call__(self):
-        return self._fn()
 
 
 class _Once:

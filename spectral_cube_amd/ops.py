@@ -858,6 +858,20 @@ def wcs_pixel_map(wcs_in, wcs_out, shape_out, device=0, stream=None):
     return d_xs, d_ys
 
 
+def _pixel_map_on_device(xs, ys, dev):
+    """(d_xs, d_ys, ny_out, nx_out) of a pixel map given as float64 DeviceArrays (wcs_pixel_map: used where they are) or as
+    host arrays (uploaded to *dev*)"""
+    if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
+        if xs.dtype != np.float64 or ys.dtype != np.float64 or xs.shape != ys.shape or len(xs.shape) != 2:
+            raise ValueError("xs, ys must be 2-D float64 maps of identical shape")
+        return (xs, ys) + tuple(xs.shape)
+    xs = np.ascontiguousarray(xs, dtype=np.float64)
+    ys = np.ascontiguousarray(ys, dtype=np.float64)
+    if xs.shape != ys.shape or xs.ndim != 2:
+        raise ValueError("xs, ys must be 2-D maps of identical shape")
+    return (DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)) + xs.shape
+
+
 def resample_bilinear(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_footprint=True, out=None,
                       order=1, any_valid=None):
     """bilinear spatial resample of every channel at (xs, ys) source pixel
@@ -866,18 +880,7 @@ def resample_bilinear(cube, xs, ys, fill=np.nan, mask=None, stream=None, want_fo
     1-element uint32 DeviceArray, set to 1 iff some output value is not NaN.  A float64 cube: float64 weights and result."""
     dev = cube.device
     name, dtype = _entry("resample_bilinear", cube)
-    if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
-        if xs.dtype != np.float64 or ys.dtype != np.float64 or xs.shape != ys.shape or len(xs.shape) != 2:
-            raise ValueError("xs, ys must be 2-D float64 maps of identical shape")
-        d_xs, d_ys = xs, ys
-        ny_out, nx_out = xs.shape
-    else:
-        xs = np.ascontiguousarray(xs, dtype=np.float64)
-        ys = np.ascontiguousarray(ys, dtype=np.float64)
-        if xs.shape != ys.shape or xs.ndim != 2:
-            raise ValueError("xs, ys must be 2-D maps of identical shape")
-        ny_out, nx_out = xs.shape
-        d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
+    d_xs, d_ys, ny_out, nx_out = _pixel_map_on_device(xs, ys, dev)
     out = _out_cube(out, (cube.shape[0], ny_out, nx_out), dtype, dev)          # (a strided view carries its strides)
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
     c, m = _cube_c(cube), _mask_c(mask, cube)
@@ -926,18 +929,7 @@ def resample_bilinear_lerp(cube, xs, ys, lo, t, inv_dx, fill=np.nan, mask=None, 
         lo, t, inv_dx, flip = lo[::-1].copy(), t[::-1].copy(), inv_dx[::-1].copy(), True
     if cube.shape[0] < 2:
         raise _lib.HipUnsupported("resample_bilinear_lerp: at least two input channels")
-    if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
-        if xs.dtype != np.float64 or ys.dtype != np.float64 or xs.shape != ys.shape or len(xs.shape) != 2:
-            raise ValueError("xs, ys must be 2-D float64 maps of identical shape")
-        d_xs, d_ys = xs, ys
-        ny_out, nx_out = xs.shape
-    else:
-        xs = np.ascontiguousarray(xs, dtype=np.float64)
-        ys = np.ascontiguousarray(ys, dtype=np.float64)
-        if xs.shape != ys.shape or xs.ndim != 2:
-            raise ValueError("xs, ys must be 2-D maps of identical shape")
-        ny_out, nx_out = xs.shape
-        d_xs, d_ys = DeviceArray.from_numpy(xs, dev), DeviceArray.from_numpy(ys, dev)
+    d_xs, d_ys, ny_out, nx_out = _pixel_map_on_device(xs, ys, dev)
     nz_out = len(lo)
     d_lo = DeviceArray.from_numpy(lo, dev)
     d_t = DeviceArray.from_numpy(np.asarray(t, dtype=np.float64), dev)

@@ -164,8 +164,11 @@ def test_result_is_pending_and_keeps_mask_fill_wcs_unit_meta():
         assert out.mask is cube.mask and out.fill_value == 0.0
         assert out.wcs is cube.wcs and out.unit == cube.unit == "K" and out.meta == cube.meta
         assert out.header["CRVAL3"] == cube.header["CRVAL3"]
-    assert hasattr(cube.spectral_smooth_median(3)._lazy, "strip_fn") and not hasattr(cube.spectral_smooth_median(3)._lazy, "slab_fn")
-    assert hasattr(cube.spatial_smooth_median(3)._lazy, "slab_fn") and not hasattr(cube.spatial_smooth_median(3)._lazy, "strip_fn")
+    # the out-of-core routes each declares: strips of whole spaxels along the spectral axis, slabs of whole planes per plane
+    for out in (cube.spectral_smooth_median(3), cube.spectral_filter(5, "rank_filter", rank=-2, mode="wrap")):
+        assert out._lazy.strips is True and out._lazy.slabs is False
+    for out in (cube.spatial_smooth_median(3), cube.spatial_filter((3, 5), _stand_in("percentile_filter"), percentile=30)):
+        assert out._lazy.slabs is True and out._lazy.strips is False
 
 
 def test_varying_resolution_cube_keeps_its_beams():
