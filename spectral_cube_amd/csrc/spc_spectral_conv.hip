@@ -320,21 +320,23 @@ __global__ __launch_bounds__(256) void moment_weights_kernel(const double* cen, 
     w[3 * i] = a0 / ksum; w[3 * i + 1] = a1 / ksum; w[3 * i + 2] = a2 / ksum;
 }
 
-// returns 1 when the algebraic pass ran (A.status then marks the tiles left to the general kernel);
-// d_status (one byte per 128 columns) and d_w (3 nz doubles) come out of the caller's workspace
+// *took = 1 when the algebraic pass ran (A.status then marks the tiles left to the general kernel);
+// d_status (one byte per 128 columns) and d_w (3 nz doubles) come out of the caller's workspace, which arrives dirty:
+// the flags are cleared here (and the clear is checked), every weight is written by moment_weights_kernel
 int try_weighted_moments(ConvArgs& A, const spc_cube_f32* cube, const double* h_kernel, int ntaps,
-                         hipStream_t st, unsigned char* d_status, double* d_w) {
-    if (spc_switch("SPC_FUSE_ALGEBRAIC", 1) == 0) return 0;
+                         hipStream_t st, unsigned char* d_status, double* d_w, int* took) {
+    *took = 0;
+    if (spc_switch("SPC_FUSE_ALGEBRAIC", 1) == 0) return SPC_OK;
     const bool ext = A.mo.d_argmax || A.mo.d_argmin || A.mo.d_vmax || A.mo.d_vmin;
     const bool al = (cube->nx % 4 == 0) && (cube->row_stride % 4 == 0) && (cube->plane_stride % 4 == 0) &&
                     ((((uintptr_t)cube->d_data) & 15) == 0);
-    if (ext || !al || (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) != 0 || cube->ny > 65535 || ntaps > kMaxAlgebraicTaps) return 0;
+    if (ext || !al || (A.mask.flags & ~(uint32_t)SPC_MASK_FINITE) != 0 || cube->ny > 65535 || ntaps > kMaxAlgebraicTaps) return SPC_OK;
     const int64_t nz = cube->nz;
     WeightTaps T{};
     double ksum = 0.0;
     for (int j = 0; j < ntaps; ++j) { T.k[j] = h_kernel[j]; ksum += h_kernel[j]; }
     const size_t ntiles = (size_t)((A.ny * A.nx + 127) / 128);
-    (void)spc_flags_clear(d_status, ntiles, st);
+    SPC_HIP(spc_flags_clear(d_status, ntiles, st));
     hipLaunchKernelGGL(moment_weights_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, A.cen, nz, T, ntaps, ksum, d_w);
     WmArgs W{};
     W.cube = A.cube; W.nz = A.nz; W.ny = A.ny; W.nx = A.nx; W.row_stride = A.row_stride; W.plane_stride = A.plane_stride;
@@ -343,7 +345,8 @@ int try_weighted_moments(ConvArgs& A, const spc_cube_f32* cube, const double* h_
     if (wm_u == 4) hipLaunchKernelGGL(weighted_moments_kernel<4>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
     else hipLaunchKernelGGL(weighted_moments_kernel<8>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
     A.status = d_status;
-    return 1;
+    *took = 1;
+    return SPC_OK;
 }
 
 int launch_ring_raw(int R, const ConvArgs& A, hipStream_t st, int fast, bool fuse) {
@@ -549,7 +552,10 @@ int spc_spectral_conv_moments_f32(int device, void* stream, const spc_cube_f32* 
         // extremum request sends the caller to the materialised route.  Whether a tile was flagged is a
         // result the HOST needs before it can answer: this branch waits for the stream.
         bool ok = false;
-        if (try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w)) {
+        int took = 0;
+        rc = try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w, &took);
+        if (rc) return rc;
+        if (took) {
             std::vector<unsigned char> hs(ntiles);
             ok = hipMemcpyAsync(hs.data(), d_status, ntiles, hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipStreamSynchronize(st) == hipSuccess;
@@ -571,7 +577,10 @@ int spc_spectral_conv_moments_f32(int device, void* stream, const spc_cube_f32* 
     A.zchunk = cube->nz;
     A.skip_dead = spc_switch("SPC_SPECTRAL_SKIP_DEAD", 1);
     const int vec = pick_vec(cube, A.mask, nullptr, 0, 0);
-    if (try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w)) {
+    int took = 0;
+    rc = try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w, &took);
+    if (rc) return rc;
+    if (took) {
         SPC_LAUNCH_CHECK();
         return launch_ring_raw(R, A, st, 0, true);      // general kernel: flagged tiles only
     }
