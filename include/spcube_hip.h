@@ -757,6 +757,28 @@ int spc_percentile_global_f32(int device, void* stream, const spc_cube_f32* cube
                               double q, int has_center, float center, double* h_out,
                               void* d_workspace, size_t workspace_bytes);
 
+/* The same statistic over TWO axes at once, one result per index of the axis that is kept: median / percentile with
+ * axis=(1, 2) or (0, 2) (BaseSpectralCube.median / percentile, spectral_cube/spectral_cube.py:1172-1257:
+ * apply_numpy_function(np.nanmedian / np.nanpercentile, axis=pair)) and mad_std over a pair (:730-764, how='slice' with a
+ * two-axis tuple; astropy stats.mad_std).  A group is every sample that shares the index along keep_axis:
+ *   keep_axis = 0: the plane z (ny * nx samples), nz groups - the per-channel statistic;
+ *   keep_axis = 1: the rows (z, y) of one y (nz * nx samples), ny groups.
+ * The selection is spc_percentile_global_f32's, for all groups at once: four passes count one key byte each into
+ * per-group histograms (64-bit counters), a small kernel walks every group's 256 counters on the device after each pass, a
+ * fifth pass finds the next larger key - it is always launched and reads only the groups whose two order statistics are
+ * different values - and the last kernel applies that entry's interpolation rule per group.  With d_center (ngroups float32,
+ * DEVICE) the statistic is taken of |x - d_center[group]| in float32 arithmetic (a NaN centre: NaN); the result is
+ * multiplied by scale as in spc_percentile_axis0_f32 (1.482602218505602: mad_std).  A group without an included,
+ * non-NaN sample gives NaN.  d_out: ngroups float32, DEVICE.
+ * The cube is read at most five times; everything is queued on `stream` and the call returns without synchronising: no
+ * counter and no flag comes back to the host.  Any view spc_check_cube accepts and every mask form.  d_workspace:
+ * spc_percentile_groups_workspace_bytes(ngroups) bytes of caller-owned scratch (2 KiB of counters and a small state
+ * record per group); nothing is assumed of its contents. */
+size_t spc_percentile_groups_workspace_bytes(int64_t ngroups);
+int spc_percentile_groups_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int keep_axis,
+                              double q, const float* d_center, float scale, float* d_out,
+                              void* d_workspace, size_t workspace_bytes);
+
 /* ONE pass of that selection, for a cube that is sharded over ranks (each rank calls this on its strip, the ranks add
  * their counters - or take the minimum of their next keys - and walk them together; the reference's counterpart is
  * the dask reduction tree under dask_spectral_cube.py:657-693).  Samples are compared through their order-preserving

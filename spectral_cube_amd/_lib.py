@@ -173,6 +173,8 @@ SIGNATURES = {
     "spc_argextrema_axis_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _vp]),
     "spc_fill_masked_transpose_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _f, _vp]),
     "spc_percentile_global_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), C.c_double, _i, _f, _P(C.c_double), _vp, _sz]),
+    "spc_percentile_groups_workspace_bytes": (_sz, [_i64]),
+    "spc_percentile_groups_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _d, _vp, _f, _vp, _vp, _sz]),
     "spc_key_histogram_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), C.c_uint32, C.c_uint32, _i, _i, _f,
                                     _P(C.c_uint64), _P(C.c_uint32), _vp, _sz]),
     "spc_key_to_f32": (_f, [C.c_uint32]),

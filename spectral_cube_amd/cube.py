@@ -1017,7 +1017,7 @@ class SpectralCube:
                     raise streaming.HugeCubeError(
                         "this operation needs the whole cube in HBM: %.2f GiB against a budget of %.2f GiB (SPC_HBM_BUDGET). "
                         "Out-of-core cubes stream moments, argmax / argmin, the nan-reductions and median / percentile / mad_std along any "
-                        "axis, statistics(), and spectral_smooth / spatial_smooth / spectral_interpolate / sigma_clip_spectrally / reproject "
+                        "axis and over the pair (1, 2), statistics(), and spectral_smooth / spatial_smooth / spectral_interpolate / sigma_clip_spectrally / reproject "
                         "(celestial) into write(), stream_into() or a following moment"
                         % (nbytes / 2**30, streaming.hbm_budget(self.device) / 2**30))
                 self._dev = DeviceArray.from_numpy(self._data, self.device, dtype=np.float32)
@@ -1707,27 +1707,72 @@ class SpectralCube:
         """whole-cube statistic (axis=None): float32 like numpy's result for a float32 cube"""
         return np.float32(ops.percentile_global(self._device_data(), q, mask=self._mask_spec(), center=center))
 
+    def _order_stat_pair(self, q, pair, center=None, scale=1.0, operand=None):
+        """the statistic over two axes (spectral_cube.py:730-764, 1172-1257 with a two-axis tuple): a float32 DeviceArray
+        with one value per index of the third axis (ops.percentile_global's keep mode: per-group histograms, the descent of
+        every group on the device).  *center*: the device result of an earlier call (mad_std).  A float64 cube goes the way
+        median(axis=None) goes: its float32 samples, with a PrecisionWarning."""
+        if operand is None:
+            operand = self._pair_operand(pair)
+        if operand is None:
+            # out of core: every plane is whole in a slab of channels; the slab's results are rows z0:z1 of the spectrum
+            from . import streaming
+            self._note_narrowed()                  # (a wide source streams as float32: said once, as a resident one says it)
+            return streaming.percentile_planes(self, q, center=center, scale=scale)
+        data, mask, keep = operand
+        return ops.percentile_global(data, q, mask=mask, center=center, keep=keep, scale=scale)
+
+    def _pair_operand(self, pair):
+        """(device data, mask, kept axis) that ops.percentile_global's keep mode reduces for *pair* - mad_std's two calls share
+        it; None for the planes of a streamed cube, which go slab by slab"""
+        if pair == (1, 2) and self._stream_source() is not None:
+            return None
+        data, mask = self._device_data(), self._mask_spec()
+        if pair == (0, 1):
+            # one value per x: the NaN-filled copy with the spatial axes exchanged has x as its row index.  No mask goes
+            # with it: NaN is never a sample, and an infinity the mask included stays one (as in numpy's nanmedian)
+            return ops.fill_masked_transposed(data, mask, np.nan), None, 1
+        return data, mask, 0 if pair == (1, 2) else 1
+
+    def _pair_projection(self, dev):
+        """a statistic over two axes as mean(axis=pair) returns it"""
+        return Projection(dev.get(), unit=self._unit, wcs=None, meta=dict(self._meta))
+
     def median(self, axis=None, **kwargs):
-        """nanmedian along an axis or of the whole cube (dask_spectral_cube.py:657-671): digit
-        descent on order-preserving keys, no sort (csrc/spc_select.hip)."""
+        """nanmedian along an axis, over two axes or of the whole cube (dask_spectral_cube.py:657-671;
+        spectral_cube.py:1172-1213 for a pair): digit descent on order-preserving keys, no sort (csrc/spc_select.hip,
+        spc_select_groups.hip)."""
+        axis = self._reduced_axes(axis)
         if axis is None:
             return float(self._order_stat_global(50.0))
+        if isinstance(axis, tuple):
+            return self._pair_projection(self._order_stat_pair(50.0, axis))
         return Projection(self._order_stat(50.0, axis, "median").get(), unit=self._unit,
                           wcs=self._order_wcs(axis), meta=dict(self._meta))
 
     def percentile(self, q, axis=None, **kwargs):
-        """np.nanpercentile along an axis or of the whole cube (dask_spectral_cube.py:673-693)."""
+        """np.nanpercentile along an axis, over two axes or of the whole cube (dask_spectral_cube.py:673-693;
+        spectral_cube.py:1215-1257 for a pair)."""
+        axis = self._reduced_axes(axis)
         if axis is None:
             return float(self._order_stat_global(float(q)))
+        if isinstance(axis, tuple):
+            return self._pair_projection(self._order_stat_pair(float(q), axis))
         return Projection(self._order_stat(float(q), axis, "percentile").get(), unit=self._unit,
                           wcs=self._order_wcs(axis), meta=dict(self._meta))
 
     def mad_std(self, axis=None, ignore_nan=True, **kwargs):
-        """astropy mad_std along the spectral axis (dask_spectral_cube.py:711-731): two selections
-        (median, then median of |x - median|) without leaving the device."""
+        """astropy mad_std along an axis, over two axes - axis=(1, 2): the noise of every channel - or of the whole cube
+        (dask_spectral_cube.py:711-731; spectral_cube.py:730-764): two selections (median, then median of |x - median|)
+        without leaving the device."""
+        axis = self._reduced_axes(axis)
         if axis is None:
             med = self._order_stat_global(50.0)
             return float(np.float32(self._order_stat_global(50.0, center=med) * np.float32(ops.MAD_TO_STD)))
+        if isinstance(axis, tuple):
+            operand = self._pair_operand(axis)
+            med = self._order_stat_pair(50.0, axis, operand=operand)
+            return self._pair_projection(self._order_stat_pair(50.0, axis, center=med, scale=ops.MAD_TO_STD, operand=operand))
         med = self._order_stat(50.0, axis, "mad_std")
         out = self._order_stat(50.0, axis, "mad_std", center=med, scale=ops.MAD_TO_STD)
         return Projection(out.get(), unit=self._unit, wcs=self._order_wcs(axis), meta=dict(self._meta))

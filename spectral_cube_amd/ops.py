@@ -112,6 +112,12 @@ def workspace(device, stream, kind, nz, ny, nx, p0=0, p1=0, explicit=None):
         if explicit.nbytes < need:
             raise ValueError("workspace of %d bytes given, %d needed" % (explicit.nbytes, need))
         return C.c_void_p(explicit.ptr), explicit.nbytes
+    return _pooled_scratch(device, stream, need)
+
+
+def _pooled_scratch(device, stream, need):
+    """(c_void_p, nbytes) of the (device, stream, thread) scratch buffer, grown to *need* bytes: for the entries that size
+    their scratch with a function of their own (spc_percentile_groups_workspace_bytes) as for the kinds of workspace()"""
     h = _sh(stream)
     key = (device, getattr(h, "value", h) or 0, threading.get_ident())
     with _ws_lock:
@@ -1258,15 +1264,44 @@ def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, ou
     return out
 
 
-def percentile_global(cube, q, mask=None, center=None, stream=None):
+def percentile_global(cube, q, mask=None, center=None, stream=None, keep=None, scale=1.0, out=None):
     """q-th percentile of all included samples of the cube (np.nanpercentile(..., axis=None));
-    with *center* of |x - center|.  Returns a python float (NaN when nothing is included)."""
+    with *center* of |x - center|.  Returns a python float (NaN when nothing is included).
+
+    *keep* = 0 | 1: the same selection over the two OTHER axes, one result per index of the kept axis
+    (spc_percentile_groups_f32; spectral_cube.py:730-764, 1172-1257 with a two-axis tuple): per plane z (axis=(1, 2)) or per
+    row index y (axis=(0, 2)).  *center* is then a float32 DeviceArray of one centre per group (or None), the result -
+    multiplied by *scale* - a float32 DeviceArray of (ngroups,), *out* when given.  Nothing comes back to the host and
+    nothing waits: the result of one call may be the centre of the next (mad_std)."""
+    if keep is not None:
+        return _percentile_groups(cube, q, mask, center, stream, keep, scale, out)
+    if scale != 1.0 or out is not None:
+        raise ValueError("scale= and out= go with keep=0 | 1: the whole-cube statistic comes back as a python float")
     out = C.c_double(0.0)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(cube.device, stream, _lib.WS_PERCENTILE_GLOBAL, *cube.shape)
     _lib.call("spc_percentile_global_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), float(q),
               0 if center is None else 1, 0.0 if center is None else float(center), C.byref(out), ws, wsn)
     return out.value
+
+
+def _percentile_groups(cube, q, mask, center, stream, keep, scale, out):
+    """percentile_global's keep=0 | 1 mode"""
+    if keep not in (0, 1):
+        raise ValueError("keep must be None (the whole cube), 0 (one result per plane) or 1 (one per row index)")
+    c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
+    ngroups = int(cube.shape[keep])
+    if center is not None and (not isinstance(center, DeviceArray) or center.dtype != np.float32 or tuple(center.shape) != (ngroups,)):
+        raise TypeError("center must be a float32 (%d,) DeviceArray: one centre per group" % ngroups)
+    if out is None:
+        out = DeviceArray((ngroups,), np.float32, cube.device)
+    elif tuple(out.shape) != (ngroups,) or out.dtype != np.float32:
+        raise ValueError("preallocated output must be (%d,) float32" % ngroups)
+    ws, wsn = _pooled_scratch(cube.device, stream, int(_lib.load().spc_percentile_groups_workspace_bytes(ngroups)))
+    _lib.call("spc_percentile_groups_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(keep), float(q),
+              C.c_void_p(center.ptr) if center is not None else None, float(scale), C.c_void_p(out.ptr), ws, wsn)
+    out._group_center = center       # the kernels may still be queued: the centre lives as long as the result
+    return out
 
 
 def key_histogram(cube, prefix, pmask, shift, mask=None, center=None, stream=None):

@@ -11,7 +11,7 @@ kernels of strip k run on their own stream; the 2-D maps are assembled on the de
 writes rows [y0, y1) of the final map in place.
 
 What streams: moments of any order along any axis, argmax / argmin / max / min, statistics() and the
-axis=None reductions, median / percentile / mad_std along the spectral axis, sigma_clip_spectrally; the cube -> cube
+axis=None reductions, median / percentile / mad_std along the spectral axis and over axis=(1, 2) (slabs), sigma_clip_spectrally; the cube -> cube
 operators (spectral_smooth, spatial_smooth - halo strips before a moment, slabs of whole planes to a sink -,
 spectral_interpolate, convolve_to, reproject) through map_strips into a host array or a FITS file, or fused with
 a following moment.  What still needs the resident cube raises HugeCubeError with the budget in the message.
@@ -542,6 +542,25 @@ def percentile_axis0(cube, q, center=None, scale=1.0, rows=None):
     for y0, y1, dev, mspec in Strips(cube, compute, rows):
         ops.percentile_axis0(dev, q, mask=mspec, center=_rows_view(center, y0, y1) if center is not None else None, scale=scale,
                              stream=compute, out=_rows_view(out, y0, y1))
+    compute.synchronize()
+    return out
+
+
+def percentile_planes(cube, q, center=None, scale=1.0, planes=None):
+    """ops.percentile_global(..., keep=0) of a streamed cube (median / percentile / the two selections of mad_std over
+    axis=(1, 2): every plane is whole in a slab of channels): (nz,) float32 DeviceArray, every slab's call writing its
+    channels z0:z1.  center: the (nz,) float32 result of the first selection (mad_std), read slab by slab"""
+    from . import ops
+    nz = cube._shape[0]
+    out = DeviceArray((nz,), np.float32, cube.device)
+
+    def part(arr, z0, z1):
+        return DeviceArray((z1 - z0,), arr.dtype, arr.device, ptr=arr.ptr + z0 * arr.dtype.itemsize, owner=arr)
+
+    compute = Stream(cube.device)
+    for z0, z1, dev, mspec in Strips(cube, compute, planes, axis=0, out_factor=0.0):
+        ops.percentile_global(dev, q, mask=mspec, center=part(center, z0, z1) if center is not None else None, stream=compute,
+                              keep=0, scale=scale, out=part(out, z0, z1))
     compute.synchronize()
     return out
 
