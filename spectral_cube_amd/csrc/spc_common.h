@@ -116,7 +116,9 @@ size_t spc_ws_resample_bilinear_lerp(int64_t nz, int64_t ny_out, int64_t nx_out)
 size_t spc_ws_stats(int kind, int64_t nz, int64_t ny, int64_t nx, int64_t p0, int64_t p1);
 size_t spc_ws_percentile_global(void);
 size_t spc_ws_sigma_clip(void);
-size_t spc_ws_wide(int kind, int64_t nz, int64_t ny, int64_t nx, int64_t p0, int64_t p1);
+size_t spc_ws_stats_global_f64(void);
+size_t spc_ws_spectral_conv_f64(int64_t ntaps);
+size_t spc_ws_spatial_conv_f64(int64_t nz, int64_t ny, int64_t nx, int64_t nky, int64_t nkx);
 size_t spc_ws_spatial_conv_mfma(int64_t nz, int64_t ny, int64_t nx, int64_t nsum);
 int spc_spatial_conv_split_store(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, const double* h_ky, int nky,
                                  const double* h_kx, int nkx, float* d_out, int64_t out_row_stride, int64_t out_plane_stride);
@@ -228,8 +230,8 @@ static inline int spc_check_cube_any_order_words(const C* c) {
     return SPC_OK;
 }
 
-// the float64 moment kernel packs a count and two z indices into 21 bits each; every entry point of spc_wide_ops.hip
-// has carried its bound too.  Called after the cube check proper
+// the float64 moment kernel packs a count and two z indices into 21 bits each; cube64_args (spc_wide.h) hands its bound
+// to every float64 operator that takes a cube in spectral order.  Called after the cube check proper
 static inline int spc_check_nz_f64(const spc_cube_f64* c) {
     SPC_REQUIRE(c->nz < (1LL << 21), "nz too large for the float64 moment kernel (%lld)", (long long)c->nz);
     return SPC_OK;

@@ -12,8 +12,7 @@
 //   1e-5 contract of the float32 configurations absorbs and a float64 result does not.
 //
 // HBM-bound (8 B per voxel per pass); eight waves of a block split the channels, their partial sums meet in LDS.
-#include "spc_common.h"
-#include "spc_common.h"
+#include "spc_wide.h"
 
 #include <algorithm>
 
@@ -181,16 +180,10 @@ __global__ __launch_bounds__(kLanes * kZW) void moments_f64_kernel(const Mom64Ar
     }
 }
 
-bool pairs_ok(const spc_cube_f64* c, const MaskDev64& m) {
-    const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
-    return (c->nx % 2 == 0) && (c->row_stride % 2 == 0) && (c->plane_stride % 2 == 0) && ((((uintptr_t)c->d_data) & 15) == 0) &&
-           (!arr || ((m.row_stride % 2 == 0) && (m.plane_stride % 2 == 0) && ((((uintptr_t)m.arr) & 1) == 0)));
-}
-
 template <int ORDER>
 int launch64(Mom64Args& A, const spc_cube_f64* cube, bool ext, hipStream_t st) {
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
-    const int vec = pairs_ok(cube, A.mask) ? 2 : 1;
+    const int vec = spc_pairs_ok_f64(cube, A.mask) ? 2 : 1;
     A.groups_per_row = cube->nx / vec;
     A.ngroups = cube->ny * A.groups_per_row;
     const int64_t nblk = (A.ngroups + kLanes - 1) / kLanes;

@@ -14,7 +14,7 @@
 //
 // The value one source gives at one output voxel is restated from the resampling kernels so that it has THEIR bits:
 // bilinear_kernel (spc_resample.hip) for float32 - float weights, fmaf(w11, d, fmaf(w10, c, fmaf(w01, b, w00 * a))), the
-// mask as spc_pred reads it - and bilinear64_kernel (spc_wide_ops.hip) for float64 - double weights, a * w00 + b * w01 +
+// mask as spc_pred reads it - and bilinear64_kernel (spc_resample_f64.hip) for float64 - double weights, a * w00 + b * w01 +
 // c * w10 + d * w11, the mask in the canonical form with the NaN rule of an array-only mask.  Both: scipy's
 // map_coordinates on the image padded by one edge-replicated pixel, NaN outside [-0.5, n - 0.5], a NaN neighbour
 // propagates even with weight 0; unprojectable map entries (-1e30, or anything not finite) are outside.

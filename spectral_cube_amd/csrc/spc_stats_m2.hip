@@ -12,7 +12,7 @@
 // The whole cube at once has ONE mean, known from spc_stats_global before this pass: spc_stats_dev_axis takes it as a number
 // and writes s1 and s2 of every ray about it; the host adds the rays and forms s2 - s1^2 / n once (nothing to merge).
 //
-// Plain HBM streams in the shape of the float64 statistics kernels (spc_wide_ops.hip): a lane per output marching z or y,
+// Plain HBM streams in the shape of the float64 statistics kernels (spc_stats_f64.hip): a lane per output marching z or y,
 // a wave per row along x; one template for both sample widths.  std pays a second read of the cube; sum / mean / max / min
 // and statistics() keep their one pass.
 #include "spc_common.h"

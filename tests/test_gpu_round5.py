@@ -563,7 +563,7 @@ def test_reproject_onto_a_cube_header_resamples_all_three_axes_in_one_pass(gpu, 
     assert np.array_equal(out.mask.include(), np.broadcast_to(foot, got.shape))
 
 
-# ---- float64 cubes through the operators next to the moments (spc_wide_ops.hip, ABI 8) ---------------------------------------
+# ---- float64 cubes through the operators next to the moments (csrc/spc_*_f64.hip, ABI 8) ------------------------------------
 @pytest.mark.parametrize("source", ["file", "array"])
 def test_float64_cube_stays_float64_through_the_other_operators(gpu, tmp_path, source):
     """A BITPIX = -64 cube (a 2 mK .. 1 K line on a 1000 K baseline) read as the reference reads it (float64, masks.py:225):

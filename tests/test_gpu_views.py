@@ -38,7 +38,7 @@ GENERAL = ("xwin_off1", "xwin_oddstride", "xwin_tail")
 TABLE = [
     ("moments", "spc_moments_f32", "spc_moments.hip:534 (aligned(v), v = 4, 2, 1; mask base and strides too)", "summing",
      "m0 1e-5 max, m1 1e-5 span, m2 1e-5 scale on rays with signal; extrema, counts exact: test_gpu_ops.py:56-72"),
-    ("moments_f64", "spc_moments_f64 + spc_moment_order_f64", "spc_moments_f64.hip:186 (pairs_ok)", "summing",
+    ("moments_f64", "spc_moments_f64 + spc_moment_order_f64", "spc_moments_f64.hip:186 (spc_pairs_ok_f64, spc_wide.h:39)", "summing",
      "1e-13: mask_edges.py:301 (test_moments_f64, test_gpu_round4.py)"),
     ("moment_order", "spc_moment_order_f32 / _f64", "spc_moments.hip:654 (v4); spc_moments_f64.hip:186", "summing",
      "rtol 1e-9, atol 1e-9 max: test_gpu_ops.py:116; float64 1e-12: mask_edges.py:317"),
@@ -58,7 +58,7 @@ TABLE = [
     ("argextrema_axis", "spc_argextrema_axis_f32, axes 1 2", "spc_stats.hip:906-907 (v4, axis 1; axis 2 per row)", "exact", "-"),
     ("stats_planes", "spc_stats_planes_f32", "spc_stats.hip:191-205 (flat planes / row by row)", "summing",
      "sum, sumsq rtol 1e-12: test_gpu_ops.py:746-747"),
-    ("stats_global", "spc_stats_global_f32 / _f64", "spc_stats.hip:120-129 (one run / rows of a view); spc_wide_ops.hip:1678 (vec2)",
+    ("stats_global", "spc_stats_global_f32 / _f64", "spc_stats.hip:120-129 (one run / rows of a view); spc_stats_f64.hip:161 (vec2: spc_pairs_ok_f64)",
      "summing", "npts, min, max exact; sum, sumsq rtol 1e-12: test_gpu_ops.py:441-465"),
     ("percentile_axis2", "spc_percentile_axis2_f32", "spc_select.hip:1485-1509 (no 16-byte form: lanes take consecutive samples of a row; takes "
      "swap01)", "exact", "-"),
@@ -89,7 +89,7 @@ TABLE = [
      "the identity map at order 0 exact"),
     ("resample_spline", "spc_resample_spline_f32", "spc_resample.hip:993-1019 (no 16-byte form)", "summing", "1e-5 of the data range: test_gpu_round4.py:151"),
     ("fill_masked", "spc_fill_masked_f32, spc_fill_masked_transpose_f32, spc_mask_include_u8 / _f64, spc_narrow_f64_to_f32",
-     "spc_select.hip / spc_wide_ops.hip:1563 (scalar)", "exact", "-"),
+     "spc_select.hip / spc_convert_f64.hip:18 (scalar)", "exact", "-"),
     ("downsample", "spc_downsample_f32 / _f64, axes 0 1 2", "spc_downsample.hip:347-350 (ds_vec_ok: cube, mask, output)", "summing",
      "float32 within 1 ulp of the float64 restatement: test_gpu_downsample.py:45; float64 rtol 1e-14, atol 1e-15 max: :194"),
     ("subcube", "spc_subcube_f32 / _f64 (step 1, step 2), spc_mask_bbox_f32 / _f64", "spc_subcube.hip:258, :294", "exact", "-"),
@@ -105,7 +105,7 @@ TABLE = [
 
 # refuses: (operator, layout) -> (source line of the check, exception, message)
 REFUSES = [
-    ("every entry but percentile_axis0, percentile_axis2 and the fused sigma_clip_axis0 (float32)", "swap01", "spc_common.h:204 (spc_check_cube)",
+    ("every entry but percentile_axis0, percentile_axis2 and the fused sigma_clip_axis0 (float32)", "swap01", "spc_common.h:206 (spc_check_cube)",
      _lib.HipInvalidArgument, "plane_stride too small"),
     ("spatial_conv_mfma", "GENERAL, mask_phase", "spc_spatial_moment.hip:836-839", _lib.HipUnsupported, "8-byte column pairs / odd mask strides"),
     ("spatial_conv_mfma_moments", "GENERAL, mask_phase", "spc_spatial_moment.hip:830", _lib.HipUnsupported, "moments 1 / 2 need the split form"),
@@ -899,7 +899,7 @@ def test_operator_on_every_view(gpu, name, dtype):
 
 
 def test_float64_percentile_with_its_keys_in_lds(gpu):
-    """SPC_SELECT64 is read once per process (spc_wide_ops.hip:1530): the float64 selection that keeps its keys in LDS runs
+    """SPC_SELECT64 is read once per process (spc_select_f64.hip:632): the float64 selection that keeps its keys in LDS runs
     the same row of the matrix in a fresh process"""
     import subprocess
     import sys
@@ -949,7 +949,7 @@ def test_table_names_every_operator_of_the_matrix_and_every_ops_function_that_ta
 
 # ---- refusals: decided by the entry's SPC_REQUIREs, before any launch --------------------------------------------------------
 def test_swap01_is_refused_by_the_entries_that_check_plane_order(gpu, monkeypatch):
-    """spc_check_cube (spc_common.h:204) refuses a view whose rows lie a plane apart; only the entries that call
+    """spc_check_cube (spc_common.h:206) refuses a view whose rows lie a plane apart; only the entries that call
     spc_check_cube_any_order (percentile_axis0 float32 and float64, percentile_axis2, the fused sigma_clip_axis0) take it: the
     matrix runs those on swap01.  The loop form of sigma clipping starts with fill_masked and refuses with it"""
     monkeypatch.setenv("SPC_SIGMA_CLIP_FUSED", "0")
