@@ -453,6 +453,40 @@ int spc_mask_eval_f32(int device, void* stream, int64_t nz, int64_t ny, int64_t 
 int spc_mask_eval_f64(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask_program* prog,
                       uint8_t* d_out, int64_t out_row_stride, int64_t out_plane_stride);
 
+/* ---- binary morphology of an include array: erosion, dilation, and either one repeated to its fixed point ----
+ * What users of the reference do on the host with scipy.ndimage.binary_erosion / binary_dilation / binary_propagation on
+ * cube.get_mask_array() (spectral_cube.py:552), here on the uint8 include array where it lives.  d_in (and d_mask, or NULL)
+ * are (nz, ny, nx) uint8 arrays, any non-zero byte = True, strides in elements (0 = C-contiguous; only z * plane_stride +
+ * y * row_stride + x is formed, so rows / planes views are accepted); d_out is (nz, ny, nx) uint8, C-contiguous, written
+ * with 0 / 1, and may not overlap d_in or d_mask.
+ * The structuring element travels as a HOST list of noffsets triples (dz, dy, dx) of int8, each component within
+ * +-SPC_MORPH_MAX_REACH: the offsets index - size / 2 of its True entries, scipy's centre for even and odd extents alike.
+ * With samples outside the array equal to border_value (0 or 1), one step is
+ *     op = SPC_MORPH_DILATE:  r[p] = OR  over the offsets o of in[p - o]
+ *     op = SPC_MORPH_ERODE:   r[p] = AND over the offsets o of in[p + o]
+ *     out[p] = mask ? (mask[p] ? r[p] : in[p]) : r[p]
+ * iterations >= 1: exactly that many synchronous steps, each on the result of the one before.  iterations < 1: until a
+ * step changes nothing.  Dilation to the fixed point under a mask (binary_propagation) is the least fixed point of a
+ * monotone operator and does not depend on the order of the updates, so it is swept in place: a block settles its tile
+ * in LDS before it publishes it and the sweeps end when one leaves a device-side change word at 0; the host reads that
+ * word (4 bytes) after every batch of sweeps, the one synchronisation of these calls.  *h_iterations_run (optional)
+ * receives the number of steps / sweeps run; it is not part of the result.  The repetition of a structure WITHOUT its
+ * centre is not monotone and stays synchronous; it may cycle for ever (in scipy too): SPC_ERR_UNSUPPORTED after 65536 steps.
+ * The voxels are packed to one bit each, 32 consecutive x to a word, rows padded to a word; every step runs on two packed
+ * buffers in the workspace and the bytes are written once, at the end.  d_workspace: the number of bytes the query below
+ * returns for the same shape.  SPC_ERR_INVALID before any device work: a NULL pointer, a shape that is not positive, a
+ * stride too small, noffsets outside 1 ... SPC_MORPH_MAX_OFFSETS, an offset beyond the reach, an unknown op, a
+ * border_value that is not 0 or 1, d_out overlapping an input, a workspace too small.  No limit on any axis. */
+#define SPC_MORPH_MAX_REACH   3
+#define SPC_MORPH_MAX_OFFSETS 343
+typedef enum { SPC_MORPH_ERODE = 0, SPC_MORPH_DILATE = 1 } spc_morph_op;
+size_t spc_mask_morph_workspace_bytes(int64_t nz, int64_t ny, int64_t nx);
+int spc_mask_morph_u8(int device, void* stream, int64_t nz, int64_t ny, int64_t nx,
+                      const uint8_t* d_in, int64_t in_row_stride, int64_t in_plane_stride,
+                      const uint8_t* d_mask, int64_t mask_row_stride, int64_t mask_plane_stride,
+                      int op, const int8_t* h_offsets, int noffsets, int iterations, int border_value,
+                      uint8_t* d_out, void* d_workspace, size_t workspace_bytes, int64_t* h_iterations_run);
+
 /* ---- rank filters: median / minimum / maximum / percentile / rank over a sliding window ----
  * spectral_smooth_median / spectral_filter (spectral_cube.py:2844-2898, dask_spectral_cube.py:920-960) and
  * spatial_smooth_median / spatial_filter (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029) with a filter of

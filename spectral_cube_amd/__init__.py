@@ -22,3 +22,6 @@ from . import analysis_utilities  # noqa: F401
 from .analysis_utilities import stack_spectra, stack_cube, BadVelocitiesWarning  # noqa: F401
 from . import cube_utils  # noqa: F401
 from .cube_utils import combine_headers, mosaic_cubes  # noqa: F401
+from . import morphology  # noqa: F401
+from .morphology import (binary_dilation, binary_erosion, binary_opening, binary_closing, binary_propagation,  # noqa: F401
+                         generate_binary_structure)

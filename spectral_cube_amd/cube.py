@@ -849,6 +849,17 @@ class SpectralCube:
                                   shape=self._shape, same_data=True)
         return out
 
+    def with_mask_dilated(self, structure=None, iterations=1):
+        """the cube with its include map dilated on the device (morphology.binary_dilation; scipy.ndimage.binary_dilation
+        on get_mask_array() for users of the reference): the new mask replaces the old one"""
+        from . import morphology
+        return self.with_mask(morphology.binary_dilation(self, structure=structure, iterations=iterations), inherit_mask=False)
+
+    def with_mask_eroded(self, structure=None, iterations=1):
+        """the cube with its include map eroded on the device (morphology.binary_erosion)"""
+        from . import morphology
+        return self.with_mask(morphology.binary_erosion(self, structure=structure, iterations=iterations), inherit_mask=False)
+
     def with_fill_value(self, fill_value):
         out = self._new_cube_with(data=self._data, dev=self._dev, fill_value=fill_value,
                                   lazy=self._lazy, shape=self._shape, same_data=True)

@@ -1250,6 +1250,47 @@ def mask_eval(program, shape, device, dtype, out=None, stream=None):
     return out
 
 
+def mask_morph(inp, offsets, op, iterations=1, mask=None, border_value=0, out=None, stream=None, workspace=None,
+               return_iterations=False):
+    """uint8 (nz, ny, nx) DeviceArray: the include array *inp* (uint8 / bool, any non-zero byte True; a rows() / planes()
+    view is read where it is) eroded (*op* = _lib.MORPH_ERODE) or dilated (_lib.MORPH_DILATE) with the structuring element
+    whose True entries sit at the (n, 3) integer *offsets* (dz, dy, dx) = index - size // 2, each within
+    +-_lib.MORPH_MAX_REACH (spc_mask_morph_u8: scipy.ndimage.binary_erosion / binary_dilation / binary_propagation, which
+    users of the reference run on the host on get_mask_array(), spectral_cube.py:552).  *iterations* >= 1: that many
+    steps; < 1: until a step changes nothing.  *mask*: a uint8 array of *inp*'s shape, voxels outside it keep their
+    value at every step.  *border_value*: the samples outside the array.  *out*: a contiguous uint8 array that is neither
+    input; *workspace*: a uint8 DeviceArray of spc_mask_morph_workspace_bytes bytes (the stream's pooled scratch
+    otherwise).  Only the change words of a repetition to the fixed point (a few bytes per batch of sweeps) come back to
+    the host, inside the call.  *return_iterations*: (result, steps or sweeps run)."""
+    if inp.dtype.itemsize != 1 or inp.dtype.kind not in "ub" or len(inp.shape) != 3:
+        raise TypeError("mask_morph runs on a uint8 / bool DeviceArray of shape (nz, ny, nx)")
+    shape = tuple(int(n) for n in inp.shape)
+    if mask is not None and (tuple(mask.shape) != shape or mask.dtype.itemsize != 1 or mask.dtype.kind not in "ub"):
+        raise ValueError("mask must be a uint8 / bool array of the input's shape %s (got %s %s)" % (shape, tuple(mask.shape), mask.dtype))
+    if op not in (_lib.MORPH_ERODE, _lib.MORPH_DILATE):
+        raise ValueError("op must be _lib.MORPH_ERODE or _lib.MORPH_DILATE (got %r)" % (op,))
+    offs = np.asarray(offsets)
+    if offs.ndim != 2 or offs.shape[1] != 3 or not 1 <= offs.shape[0] <= _lib.MORPH_MAX_OFFSETS:
+        raise ValueError("offsets must be 1 to %d rows of (dz, dy, dx) (got shape %s)" % (_lib.MORPH_MAX_OFFSETS, offs.shape))
+    if np.abs(offs).max() > _lib.MORPH_MAX_REACH:
+        raise ValueError("offsets reach beyond +-%d" % _lib.MORPH_MAX_REACH)
+    offs = np.ascontiguousarray(offs, dtype=np.int8)
+    out = _contiguous_out(out, shape, np.uint8, inp.device)           # (the entry writes a compact array)
+    need = int(_lib.load().spc_mask_morph_workspace_bytes(*shape))
+    if workspace is not None:
+        if workspace.nbytes < need:
+            raise ValueError("workspace of %d bytes given, %d needed" % (workspace.nbytes, need))
+        ws, wsn = C.c_void_p(workspace.ptr), workspace.nbytes
+    else:
+        ws, wsn = _pooled_scratch(inp.device, stream, need)
+    run = C.c_int64(0)
+    mrs, mps = _strides(mask) if mask is not None else (0, 0)
+    _lib.call("spc_mask_morph_u8", inp.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(inp.ptr), *_strides(inp),
+              C.c_void_p(mask.ptr) if mask is not None else None, mrs, mps, int(op), offs.ctypes.data_as(C.c_void_p),
+              int(offs.shape[0]), int(iterations), int(border_value), C.c_void_p(out.ptr), ws, wsn, C.byref(run))
+    return (out, run.value) if return_iterations else out
+
+
 def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, out=None):
     """q-th percentile along x per (z, y) row, no transposed copy (spc_percentile_axis2_f32); *center*: a (nz, ny)
     float32 DeviceArray.  Raises HipUnsupported for rows of more than 4096 samples."""
