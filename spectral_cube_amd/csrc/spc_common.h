@@ -269,7 +269,7 @@ static inline int spc_include_from(const typename SpcAbi<T>::mask* mask, const t
     return SPC_OK;
 }
 
-// Buffer descriptor over (up to 4 GiB from) a wave-uniform base.  The base must be PROVABLY uniform, otherwise hipcc wraps
+// Buffer descriptor over (up to 4 GiB from) a wave-uniform base.  The base must be provably uniform, otherwise hipcc wraps
 // every buffer op in a waterfall loop: both halves go through readfirstlane.
 __device__ __forceinline__ auto spc_plane_srd(const void* base) {
     const unsigned long long a = (unsigned long long)base;

@@ -27,7 +27,6 @@ struct LerpArgs {
     float* out;
     int64_t out_row_stride, out_plane_stride;
     int64_t jchunk;
-    int nt_store;
 };
 
 __device__ __forceinline__ float load_filled(const float* p, const uint8_t* pm, const MaskDev& m, int64_t off, int64_t moff) {
@@ -116,8 +115,7 @@ __global__ __launch_bounds__(256) void spectral_lerp_kernel(const LerpArgs A) {
                     lset(res, i, (float)((double)diff * wj + (double)lget(a[u], i)));
                 }
             }
-            if (A.nt_store) __builtin_nontemporal_store(res, reinterpret_cast<F*>(po + j * A.out_plane_stride));
-            else *reinterpret_cast<F*>(po + j * A.out_plane_stride) = res;
+            __builtin_nontemporal_store(res, reinterpret_cast<F*>(po + j * A.out_plane_stride));
         }
     }
 }
@@ -942,8 +940,6 @@ int spc_spectral_lerp_f32(int device, void* stream, const spc_cube_f32* cube, co
     int nsplit = 1;
     if (nblocks < 2048) nsplit = (int)std::max<int64_t>(1, std::min<int64_t>((2048 + nblocks - 1) / nblocks, nz_out / 16));
     A.jchunk = (nz_out + nsplit - 1) / nsplit;
-    A.nt_store = spc_switch("SPC_LERP_NT", 1);
-    { const int jc = spc_switch("SPC_LERP_JCHUNK", 0); if (jc > 0) A.jchunk = jc; }
     nsplit = (int)((nz_out + A.jchunk - 1) / A.jchunk);
     SPC_REQUIRE(nsplit <= 65535, "too many channel groups for one launch");
     {   // short-lived blocks (see spectral_lerp_tiles_kernel): 16-byte rows, enough work to fill the chip; SPC_LERP_TILES=0 keeps the march
@@ -1075,8 +1071,7 @@ static int bilinear_launch(int device, void* stream, const spc_cube_f32* cube, c
                       (!arr || cube->ny * A.mask.row_stride < (1ll << 31));
     A.status = nullptr;
     if (want && fits) {
-        const int tenv = spc_switch("SPC_BILINEAR_TILE", -1);          // -1: not set
-        const int tile = tenv != -1 ? (tenv == 32 ? 32 : 64) : ((nx_out >= 128 && ny_out >= 128) ? 64 : 32);
+        const int tile = (nx_out >= 128 && ny_out >= 128) ? 64 : 32;
         const int kStageU = tile == 64 ? BilTile<64>::kStageU : BilTile<32>::kStageU;
         A.tile_shift = tile == 64 ? 6 : 5;
         A.tiles32_x = (nx_out + tile - 1) / tile;
@@ -1090,7 +1085,6 @@ static int bilinear_launch(int device, void* stream, const spc_cube_f32* cube, c
         // tail - not cache reuse: FETCH_SIZE did not move (profiles/r01_pmc_traffic.txt).
         // (LERP: 512 input planes per block - C5 in one pass 6.6 / 6.2 / 6.17 / 6.1 ms with 64 / 128 / 256 / 512)
         A.zchunk_lds = std::min<int64_t>((nzw + ns - 1) / ns, lerp ? 512 : 256);
-        { const int zc = spc_switch("SPC_BILINEAR_ZCHUNK", -1); if (zc != -1) A.zchunk_lds = std::max(8, zc); }
         A.zchunk_lds = ((A.zchunk_lds + kStageU - 1) / kStageU) * kStageU;
         ns = (int)((nzw + A.zchunk_lds - 1) / A.zchunk_lds);
         SPC_WS_TAKE(d_status, ws, unsigned char, ntiles);

@@ -41,12 +41,15 @@ struct SelArgs {
     int64_t x_stride, m_x_stride;
     int along_ray;
     uint32_t key_min, key_span;            // sel_key_range of the mask's predicate terms (filled by the launcher)
-    int ablate;                            // timing experiments only (SPC_SELECT_ABLATE): 1 = no descent, 2.. = passes
-    int xcd_group;                         // tiles of a row kept on one XCD (sel_tile_of_block)
+    int xcd_group;                         // tiles of a row kept on one XCD (sel_tile_of_block): kXcdGroup
 };
 
 // Block -> tile order that keeps `g` neighbouring tiles of a row on ONE XCD (blocks go round the 8 XCDs by index): a tile
 // of 16 spaxels is half a 128-byte line per plane, and the block holding the other half should find it in the same L2.
+// (g = 16.  1024^3: the clip kernel's read + write floor 4.21 -> 3.28 ms, the 256-thread selection 2.97 -> 2.65 ms;
+//  groups of 2 / 4 / 8: 3.95 / 3.54 / 3.32 - 3.6 ms; no effect on the 512-thread selection.  It rides in the kernel
+//  arguments: as a constant in the kernels it cost several of them scalar registers - profiles/retired_switches_resources.txt)
+constexpr int kXcdGroup = 16;
 __device__ __forceinline__ int64_t sel_tile_of_block(int64_t bid, int64_t nblocks, int g) {
     if (g <= 1) return bid;
     const int64_t span = 8 * (int64_t)g, whole = nblocks / span * span;
@@ -809,20 +812,7 @@ __global__ __launch_bounds__(BT, BT == 256 ? (KPL == 128 ? 2 : (TS == 128 ? 3 : 
     const int n = (int)S.nvalid[r];
     uint32_t key_lo, key_hi;
     double frac;
-#ifdef SPC_ABLATE
-    if (A.ablate == 1) {
-        uint32_t x = 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) x ^= key[i];
-        if (j == 0 && col_in) A.out[y * A.nx + x0 + r] = __uint_as_float(x + n);
-        return;
-    }
-#endif
-#ifdef SPC_ABLATE
-    ray_select<TS, KPL, BT>(S, key, KeyIdentity{}, r, j, n, A.q, key_lo, key_hi, frac, A.ablate >= 2 ? A.ablate - 1 : 8);
-#else
     ray_select<TS, KPL, BT>(S, key, KeyIdentity{}, r, j, n, A.q, key_lo, key_hi, frac);
-#endif
     if (j == 0 && col_in) A.out[y * A.nx + x0 + r] = n > 0 ? sel_value(key_lo, key_hi, frac, (double)A.scale, A.q == 50.0) : NAN;
 }
 
@@ -845,7 +835,7 @@ struct ClipRegArgs {
     int cen_mean;               // centre: 0 median, 1 mean
     int spread_mad;             // spread: 0 std, 1 mad_std
     uint32_t key_min, key_span;            // sel_key_range of the mask's predicate terms (filled by the launcher)
-    int xcd_group;              // tiles of a row kept on one XCD (sel_tile_of_block)
+    int xcd_group;              // tiles of a row kept on one XCD (sel_tile_of_block): kXcdGroup
     int compact;                // rays with few valid samples are packed (sel_compact; SPC_SELECT_COMPACT=0: off)
     const int* probe;           // NULL, or the largest valid count among the sampled rays (clip_probe_kernel): which block shape runs
 };
@@ -919,18 +909,6 @@ __device__ __forceinline__ void clip_iterate(const ClipRegArgs& A, SelShared<TS>
         }
         double cen = mean;
         float med = NAN;
-#ifdef SPC_ABLATE
-        if (A.xcd_group >= 1000 && it > 0) {                     // timing only: later iterations without their descent / without resuming
-            if (A.xcd_group == 1000) { med = (float)mean; if (!A.cen_mean) cen = mean; }
-            else {
-                uint32_t key_lo, key_hi;
-                double frac;
-                ray_select<TS, KPL, BT>(S, key, KeyIdentity{}, r, j, n, 50.0, key_lo, key_hi, frac, 8, nl, &C, false);
-                med = n > 0 ? sel_value(key_lo, key_hi, frac, 1.0) : NAN;
-                if (!A.cen_mean) cen = (double)med;
-            }
-        } else
-#endif
         if (!A.cen_mean || MAD) {
             uint32_t key_lo, key_hi;
             double frac;
@@ -1281,11 +1259,7 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
     A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
     A.q = q; A.center = d_center; A.scale = scale; A.out = d_out;
     A.x_stride = 1; A.m_x_stride = 1; A.along_ray = 0;
-    A.ablate = spc_switch("SPC_SELECT_ABLATE", 0);
-    // (16 neighbouring tiles of a row per XCD: a block's half - or quarter - of a 128-byte line is found in the L2 that fetched it
-    //  for its neighbour.  1024^3: the clip kernel's read + write floor 4.21 -> 3.28 ms, the 256-thread selection 2.97 -> 2.65 ms;
-    //  groups of 2 / 4 / 8: 3.95 / 3.54 / 3.32 - 3.6 ms; no effect on the 512-thread selection.  SPC_XCD_GROUP=0: block = tile)
-    A.xcd_group = spc_switch("SPC_XCD_GROUP", 16);
+    A.xcd_group = kXcdGroup;
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     const bool v4 = (cube->nx % 4 == 0) && (cube->row_stride % 4 == 0) && (cube->plane_stride % 4 == 0) &&
                     ((((uintptr_t)cube->d_data) & 15) == 0) &&
@@ -1297,7 +1271,7 @@ extern "C" int spc_percentile_axis0_f32(int device, void* stream, const spc_cube
         // Blocks of 512 threads (round 3): the lanes of a wave cover 64 / 32 / 16 / 8 ADJACENT spaxels for rays of up to 512 /
         // 1024 / 2048 / 4096 samples - a plane's samples of a block are one 256 / 128 / 64 / 32-byte run.  With 256 threads
         // (16 spaxels, 64-byte runs at 1024 channels) the one read of the cube ran at 2.1 TB/s and made up 2.0 of the 2.9 ms
-        // at 1024^3 (timing-only ablation, tools/bench_select_ablate.py); 32 spaxels: 0.92 ms.  SPC_SELECT_BT=256: the former table.
+        // at 1024^3 (a timing-only ablation of round 3); 32 spaxels: 0.92 ms.  SPC_SELECT_BT=256: the former table.
         {
             const int bt = spc_switch("SPC_SELECT_BT", 0);
             // (rays of up to 256 samples keep the 256-thread table - 32 spaxels per block already, and the per-ray costs of the
@@ -1554,10 +1528,7 @@ extern "C" int spc_sigma_clip_axis0_f32(int device, void* stream, const spc_cube
     A.out = d_out;
     A.lo_s = sigma_lower; A.hi_s = sigma_upper; A.maxiters = maxiters; A.cen_mean = center_is_mean ? 1 : 0;
     A.spread_mad = spread_is_mad ? 1 : 0;
-    // (16 neighbouring tiles of a row per XCD: a block's half - or quarter - of a 128-byte line is found in the L2 that fetched it
-    //  for its neighbour.  1024^3: the clip kernel's read + write floor 4.21 -> 3.28 ms, the 256-thread selection 2.97 -> 2.65 ms;
-    //  groups of 2 / 4 / 8: 3.95 / 3.54 / 3.32 - 3.6 ms; no effect on the 512-thread selection.  SPC_XCD_GROUP=0: block = tile)
-    A.xcd_group = spc_switch("SPC_XCD_GROUP", 16);
+    A.xcd_group = kXcdGroup;
     A.compact = spc_switch("SPC_SELECT_COMPACT", 2);   // 0: off, 1: packed rays through the block's loop, 2: every wave on its own
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
     hipStream_t st = (hipStream_t)stream;

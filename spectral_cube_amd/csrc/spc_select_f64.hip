@@ -3,7 +3,8 @@
 //
 // The reference's median / percentile / mad_std (dask_spectral_cube.py:657-731) and sigma_clip_spectrally (:851-878,
 // centre = median | mean, spread = std | mad_std) on the float64 samples as they are, rays of up to 4096 samples
-// (spc_select.hip is the float32 twin).  Three forms, chosen by sort64_launch (SPC_SELECT64, read once per process):
+// (spc_select.hip is the float32 twin).  Three forms, chosen by sort64_launch (SPC_SELECT64 = 1, read once per process, keeps
+// the keys in LDS for every length):
 // rays of up to 1024 samples keep their keys in registers and meet over DPP row rotations (a radix select; the clip loop
 // with spread = std runs on the same resident keys); longer rays select a key byte at a time from keys in LDS; the clip
 // loop of longer rays, and of spread = mad_std, reads a bitonic-sorted ray.  The selections give the sorted rays' order
@@ -15,10 +16,10 @@
 
 namespace {
 
-// The sorted form (round 5, when there was no radix descent like the float32 kernels' for these rays): a block sorts
+// The sorted form (round 5; today only the clip loop of rays the register form does not take): a block sorts
 // its TS = 4096 / NZP adjacent rays (order-preserving 64-bit keys, excluded / NaN samples last) in 32 KB of LDS with a bitonic
-// network, then one lane per ray reads what it needs from the sorted ray - the order statistics directly (numpy's linear rule,
-// its `_lerp` form), the clip loop as a shrinking window [a, b) of the sorted samples (clipping removes the two ends of a sorted ray;
+// network, then one lane per ray runs the clip loop on the sorted ray - its order statistics directly (numpy's linear rule,
+// its `_lerp` form), the loop as a shrinking window [a, b) of the sorted samples (clipping removes the two ends of a sorted ray;
 // mean and std of a window are two scans of it, nanstd's two-pass form).  The clipped cube is written in a last sweep over the
 // rays: a sample survives when its key lies between the window's end keys.
 constexpr int kSortKeys = 4096;          // 32 KB of keys per block: four or five blocks per CU (16384 keys, one block: 41 ms per 5e8 voxels;
@@ -37,11 +38,10 @@ struct Sort64Args {
     int nzp, ts;                 // padded ray length (power of two), rays per block
     double q, scale;
     const double* center;        // NULL, or (ny, nx): keys of |x - center|
-    double* out;                 // MODE 0: (ny, nx); MODE 1: (nz, ny, nx) C-contiguous
+    double* out;                 // percentile: (ny, nx); sigma clip: (nz, ny, nx) C-contiguous
     double lo_s, hi_s;
     int maxiters, cen_mean, spread_mad;
 };
-template <int MODE>
 __global__ __launch_bounds__(256) void sort64_kernel(const Sort64Args A) {
     __shared__ unsigned long long keys[kSortKeys];           // [sample][ray]: consecutive lanes = consecutive rays
     __shared__ unsigned long long s_wlo[64], s_whi[64];
@@ -127,43 +127,37 @@ __global__ __launch_bounds__(256) void sort64_kernel(const Sort64Args A) {
             }
             return (cnt & 1) ? d1 : 0.5 * (d1 + d2);
         };
-        if (MODE == 0) {
-            A.out[y * A.c.nx + x0 + ray] = n > 0 ? quantile(0, n, A.q) * A.scale : NAN;
-        } else {
-            int a = 0, b = n, it = 0;
-            while (b > a && (A.maxiters < 0 || it < A.maxiters)) {
-                ++it;
-                const int cnt = b - a;
-                double sum = 0.0;
-                for (int i = a; i < b; ++i) sum += val(i);
-                const double mean = sum / (double)cnt;
-                double ss = 0.0;
-                for (int i = a; i < b; ++i) { const double dv = val(i) - mean; ss = fma(dv, dv, ss); }
-                const double medw = quantile(a, cnt, 50.0);
-                const double sd = A.spread_mad ? 1.482602218505602 * mad(a, cnt, medw) : sqrt(ss / (double)cnt);
-                const double c = A.cen_mean ? mean : medw;
-                const double lob = c - A.lo_s * sd, hib = c + A.hi_s * sd;
-                int na = a, nb = b;
-                while (na < nb && val(na) < lob) ++na;
-                while (nb > na && val(nb - 1) > hib) --nb;
-                // (a NaN bound - an infinite sample in the window - clips nothing: the comparisons are false, as numpy's)
-                if (na == a && nb == b) break;
-                a = na; b = nb;
-            }
-            s_wlo[ray] = b > a ? keys[a * TS + ray] : 1ull;      // empty window: lo > hi, nothing survives
-            s_whi[ray] = b > a ? keys[(b - 1) * TS + ray] : 0ull;
+        int a = 0, b = n, it = 0;
+        while (b > a && (A.maxiters < 0 || it < A.maxiters)) {
+            ++it;
+            const int cnt = b - a;
+            double sum = 0.0;
+            for (int i = a; i < b; ++i) sum += val(i);
+            const double mean = sum / (double)cnt;
+            double ss = 0.0;
+            for (int i = a; i < b; ++i) { const double dv = val(i) - mean; ss = fma(dv, dv, ss); }
+            const double medw = quantile(a, cnt, 50.0);
+            const double sd = A.spread_mad ? 1.482602218505602 * mad(a, cnt, medw) : sqrt(ss / (double)cnt);
+            const double c = A.cen_mean ? mean : medw;
+            const double lob = c - A.lo_s * sd, hib = c + A.hi_s * sd;
+            int na = a, nb = b;
+            while (na < nb && val(na) < lob) ++na;
+            while (nb > na && val(nb - 1) > hib) --nb;
+            // (a NaN bound - an infinite sample in the window - clips nothing: the comparisons are false, as numpy's)
+            if (na == a && nb == b) break;
+            a = na; b = nb;
         }
+        s_wlo[ray] = b > a ? keys[a * TS + ray] : 1ull;      // empty window: lo > hi, nothing survives
+        s_whi[ray] = b > a ? keys[(b - 1) * TS + ray] : 0ull;
     }
-    if (MODE == 1) {
-        __syncthreads();
-        if (col_in) {
-            const unsigned long long wlo = s_wlo[r], whi = s_whi[r];
-            for (int z = jz; z < A.c.nz; z += L) {
-                double v;
-                const bool ok = inc64(A.c, A.m, z, y, x0 + r, v);
-                const unsigned long long k = ok ? fkey64(v) : kExcl;
-                A.out[((int64_t)z * A.c.ny + y) * A.c.nx + x0 + r] = (k >= wlo && k <= whi) ? v : NAN;
-            }
+    __syncthreads();
+    if (col_in) {
+        const unsigned long long wlo = s_wlo[r], whi = s_whi[r];
+        for (int z = jz; z < A.c.nz; z += L) {
+            double v;
+            const bool ok = inc64(A.c, A.m, z, y, x0 + r, v);
+            const unsigned long long k = ok ? fkey64(v) : kExcl;
+            A.out[((int64_t)z * A.c.ny + y) * A.c.nx + x0 + r] = (k >= wlo && k <= whi) ? v : NAN;
         }
     }
 }
@@ -627,14 +621,12 @@ static int sort64_launch(Sort64Args& A, const spc_cube_f64* cube, bool clip, hip
     int nzp = 2;
     while (nzp < cube->nz) nzp <<= 1;
     // SPC_SELECT64, read once per process.  2, the default: rays of up to 1024 samples keep their keys in registers; 1: the keys
-    // in LDS for every length; 0: the order statistics from sorted rays as in round 5.  The clip loop sorts wherever it does not
-    // take the register form.
-    static const int form = spc_switch("SPC_SELECT64", 2);
-    const bool sel = !clip && form != 0;
-    A.nzp = nzp; A.ts = sel ? std::min(kSelRays64, kSelKeys64 / nzp) : std::min(64, kSortKeys / nzp);
+    // in LDS for every length.  The clip loop sorts wherever it does not take the register form.
+    static const bool regs = spc_switch("SPC_SELECT64", 2) != 1;
+    A.nzp = nzp; A.ts = clip ? std::min(64, kSortKeys / nzp) : std::min(kSelRays64, kSelKeys64 / nzp);
     const int64_t nb = ((cube->nx + A.ts - 1) / A.ts) * cube->ny;
     SPC_REQUIRE(nb < (1LL << 31), "map too large for one launch");
-    if (clip && form >= 2 && cube->nz <= 1024 && !A.spread_mad) {      // (stdfunc = mad_std: a second descent over |x - median| - the sorted form below)
+    if (clip && regs && cube->nz <= 1024 && !A.spread_mad) {      // (stdfunc = mad_std: a second descent over |x - median| - the sorted form below)
         const int64_t nbr = ((cube->nx + 15) / 16) * cube->ny;
         SPC_REQUIRE(nbr < (1LL << 31), "map too large for one launch");
         const int kpl = (int)((cube->nz + 15) / 16);
@@ -646,7 +638,7 @@ static int sort64_launch(Sort64Args& A, const spc_cube_f64* cube, bool clip, hip
         SPC_LAUNCH_CHECK();
         return SPC_OK;
     }
-    if (sel && form >= 2 && cube->nz <= 1024) {
+    if (!clip && regs && cube->nz <= 1024) {
         const int64_t nbr = ((cube->nx + 15) / 16) * cube->ny;
         SPC_REQUIRE(nbr < (1LL << 31), "map too large for one launch");
         const int kpl = (int)((cube->nz + 15) / 16);
@@ -658,9 +650,8 @@ static int sort64_launch(Sort64Args& A, const spc_cube_f64* cube, bool clip, hip
         SPC_LAUNCH_CHECK();
         return SPC_OK;
     }
-    if (clip) hipLaunchKernelGGL(sort64_kernel<1>, dim3((unsigned)nb), dim3(256), 0, st, A);
-    else if (sel) hipLaunchKernelGGL(select64_kernel, dim3((unsigned)nb), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(sort64_kernel<0>, dim3((unsigned)nb), dim3(256), 0, st, A);
+    if (clip) hipLaunchKernelGGL(sort64_kernel, dim3((unsigned)nb), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(select64_kernel, dim3((unsigned)nb), dim3(256), 0, st, A);
     SPC_LAUNCH_CHECK();
     return SPC_OK;
 }

@@ -643,7 +643,7 @@ int spc_spatial_conv_sep_f32(int device, void* stream, const spc_cube_f32* cube,
     for (int i = 0; i < R; ++i) if (A.ky[i] < 0.f || A.kx[i] < 0.f) A.centre_zero = 1;
     A.top_clamp = 1;
     for (int i = 0; i < R; ++i) if (A.ky[i] < 0.f || A.kx[i] < 0.f) A.top_clamp = 0;
-    A.xcd_swizzle = spc_switch("SPC_XCD_SWIZZLE", 1) != 0;
+    A.xcd_swizzle = 1;       // (still a kernel argument: as a constant it cost kernels of this family registers or spills (profiles/retired_switches_resources.txt))
     canonical_pred(A);
     // (the 49- and 65-tap rings - 35 to 65 taps - have an all-valid kernel for isotropic kernels only: two sets of
     // that many weights do not fit the SGPR file)

@@ -4,9 +4,9 @@
 // as they are - the arithmetic of the float32 stencil (spc_spatial_conv.hip) without the final rounding to float32.  An
 // outer-product kernel takes, in this order: one ring kernel with nothing between the passes (symmetric factors of up to
 // 33 taps, none negative, centre taps positive; SPC_SPATIAL64_RING=0 turns it off, read per call), else two passes over
-// a slab of the caller's workspace in one of three forms (SPC_SPATIAL64_LDS, read once per process: 2 = LDS tiles with
-// four outputs per thread, the default; 1 = LDS tiles with one; 0 = untiled), which also redo the call, gated by a flag
-// word, when the ring meets an infinite valid sample under a padding tap.  The ring and the passes add an output's
+// a slab of the caller's workspace (LDS tiles with four outputs per thread; halos too wide for them take the x tile with
+// one output per thread or the untiled passes), which also redo the call, gated by a flag word, when the ring meets an
+// infinite valid sample under a padding tap.  The ring and the passes add an output's
 // taps in the same order: the same float64 values.  Any other kernel is summed directly.
 #include "spc_wide.h"
 
@@ -109,7 +109,8 @@ __global__ __launch_bounds__(256) void spatial64_ypass_kernel(const Sp64Args A) 
 }
 // The two passes through LDS: a block of the x pass stages its row segment once (256 outputs + the halo; the untiled pass asks the
 // texture path for 58 samples per output), a block of the y pass a tile of 16 rows x 64 columns of (num, den) pairs + the halo rows
-// (464 bytes of L2 traffic per output otherwise).  Same arithmetic, same order.
+// (464 bytes of L2 traffic per output otherwise).  Same arithmetic, same order.  The one-output x pass here serves halos of
+// 128 to 511 columns; the four-output passes below serve the rest.
 constexpr int kSpHaloMax = 511, kSpYRows = 16, kSpYHalo = 23;     // (y tiles of up to 62 rows x 64 columns x 16 bytes = 62 KB of dynamic LDS + the taps: inside the 64 KB a launch gets without hipFuncSetAttribute; 49 y taps and more take the untiled pass)
 __global__ __launch_bounds__(256) void spatial64_xpass_lds_kernel(const Sp64Args A) {
     if (A.gate && *A.gate == 0u) return;
@@ -139,47 +140,6 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds_kernel(const Sp64Args
     }
     double* o = A.tmp + ((zl * A.c.ny + y) * A.c.nx + x) * 2;
     o[0] = num; o[1] = den;
-}
-__global__ __launch_bounds__(256) void spatial64_ypass_lds_kernel(const Sp64Args A) {
-    if (A.gate && *A.gate == 0u) return;
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    extern __shared__ f64x2 tile[];                              // (kSpYRows + 2 H) x 64 pairs: sized by the launch
-    __shared__ double sk[2 * kSpYHalo + 1];
-    const int t = threadIdx.x, col = t & 63, rg = t >> 6, H = A.nky / 2;
-    if (t < A.nky) sk[t] = A.ky[A.nky - 1 - t];
-    const int64_t x = (int64_t)blockIdx.x * 64 + col, y0 = (int64_t)blockIdx.y * kSpYRows, zl = blockIdx.z, z = A.z0 + zl;
-    double ksx = 0.0;                                            // a row outside the image: valid zeros under the whole x kernel
-    for (int j = 0; j < A.nkx; ++j) ksx += A.kx[j];
-    const int64_t xc = min(x, A.c.nx - 1);
-    for (int r0 = rg; r0 < kSpYRows + 2 * H; r0 += 16) {         // (four rows per lane requested together, clamped into the image)
-        f64x2 v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t ic = min(max(y0 - H + r0 + 4 * q, (int64_t)0), A.c.ny - 1);
-            v[q] = *reinterpret_cast<const f64x2*>(A.tmp + ((zl * A.c.ny + ic) * A.c.nx + xc) * 2);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rr = r0 + 4 * q;
-            const int64_t i = y0 - H + rr;
-            if (rr < kSpYRows + 2 * H) tile[rr * 64 + col] = (i >= 0 && i < A.c.ny) ? v[q] : f64x2{0.0, ksx};
-        }
-    }
-    __syncthreads();
-    if (x >= A.c.nx) return;
-    for (int ro = rg; ro < kSpYRows; ro += 4) {
-        const int64_t y = y0 + ro;
-        if (y >= A.c.ny) break;
-        double num = 0.0, den = 0.0;
-        for (int j = 0; j < A.nky; ++j) {
-            const double kw = sk[j];
-            if (kw != 0.0) { const f64x2 tv = tile[(ro + j) * 64 + col]; num = fma(kw, tv.x, num); den = fma(kw, tv.y, den); }
-        }
-        double res;
-        if (den != 0.0) res = quot_top(num, den);
-        else { double cv; res = inc64(A.c, A.m, z, y, x, cv) ? cv : NAN; }
-        A.out[z * A.out_plane_stride + y * A.out_row_stride + x] = res;
-    }
 }
 // Round 6: the same two passes with FOUR adjacent outputs per thread.  A sample read from LDS feeds up to four accumulators
 // (the outputs x .. x + 3 / the rows y .. y + 3 see it under the taps j .. j - 3, kept in a four-deep register window), so a
@@ -228,7 +188,7 @@ __global__ __launch_bounds__(256) void spatial64_xpass_lds4_kernel(const Sp64Arg
     for (int q = 0; q < 4; ++q)
         if (x + q < A.c.nx) { o[2 * q] = num[q]; o[2 * q + 1] = den[q]; }
 }
-// y pass: the tile of kSpYRows + 2 H rows x 64 columns as before; thread (column, row group) takes the rows 4 g .. 4 g + 3
+// y pass: a tile of kSpYRows + 2 H rows x 64 columns; thread (column, row group) takes the rows 4 g .. 4 g + 3
 __global__ __launch_bounds__(256) void spatial64_ypass_lds4_kernel(const Sp64Args A) {
     if (A.gate && *A.gate == 0u) return;
     typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -589,22 +549,18 @@ int spc_spatial_conv_f64(int device, void* stream, const spc_cube_f64* cube, con
     for (int64_t z0 = 0; z0 < cube->nz; z0 += planes) {
         A.z0 = z0;
         const unsigned gz = (unsigned)std::min<int64_t>(planes, cube->nz - z0);
-        static const int tiled = spc_switch("SPC_SPATIAL64_LDS", 2);
-        // (SPC_SPATIAL64_LDS: 0 = the untiled passes, 1 = LDS tiles with one output per thread (round 5), 2 = four outputs per thread)
+        // LDS tiles with four outputs per thread where the halo fits them, one output per thread (x pass) or the untiled pass beyond
         rc = over_rows([&](unsigned gy) {
-            if (tiled == 2 && nkx / 2 <= kSpX4Halo)
+            if (nkx / 2 <= kSpX4Halo)
                 hipLaunchKernelGGL(spatial64_xpass_lds4_kernel, dim3((unsigned)((cube->nx + kSpX4Out - 1) / kSpX4Out), gy, gz), dim3(256), 0, st, A);
-            else if (tiled && nkx / 2 <= kSpHaloMax)
+            else if (nkx / 2 <= kSpHaloMax)
                 hipLaunchKernelGGL(spatial64_xpass_lds_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A);
             else
                 hipLaunchKernelGGL(spatial64_xpass_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A);
         });
         if (rc) return rc;
-        if (tiled == 2 && nky / 2 <= kSpYHalo && (cube->ny + kSpYRows - 1) / kSpYRows <= 65535)
+        if (nky / 2 <= kSpYHalo && (cube->ny + kSpYRows - 1) / kSpYRows <= 65535)
             hipLaunchKernelGGL(spatial64_ypass_lds4_kernel, dim3((unsigned)((cube->nx + 63) / 64), (unsigned)((cube->ny + kSpYRows - 1) / kSpYRows), gz),
-                               dim3(256), (size_t)(kSpYRows + 2 * (nky / 2)) * 64 * 16, st, A);
-        else if (tiled && nky / 2 <= kSpYHalo && (cube->ny + kSpYRows - 1) / kSpYRows <= 65535)
-            hipLaunchKernelGGL(spatial64_ypass_lds_kernel, dim3((unsigned)((cube->nx + 63) / 64), (unsigned)((cube->ny + kSpYRows - 1) / kSpYRows), gz),
                                dim3(256), (size_t)(kSpYRows + 2 * (nky / 2)) * 64 * 16, st, A);
         else
             rc = over_rows([&](unsigned gy) { hipLaunchKernelGGL(spatial64_ypass_kernel, dim3(gx, gy, gz), dim3(256), 0, st, A); });

@@ -357,9 +357,7 @@ __device__ __forceinline__ float2v classify(float v, unsigned char mk, float lim
     return ok ? float2v{v, 1.f} : float2v{0.f, 0.f};
 }
 
-// ABL (timing-only ablations, built with -DSPC_ABLATE and selected by SPC_SPATIAL_ABLATE; results are wrong by design):
-// 1 no output stores | 2 no mask loads | 4 no data loads | 8 no y-pass FMAs | 16 no x-pass FMAs
-template <int R, bool ARR, bool PRED, bool ISO, int ABL = 0>
+template <int R, bool ARR, bool PRED, bool ISO>
 __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(const SpArgs A) {
     constexpr int H = R / 2;
     // float2 per LDS row.  Pitch = 28 (mod 32): a 32-lane group of the x pass spans parts of
@@ -417,16 +415,16 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
 #pragma unroll
             for (int s = 0; s < R; ++s) {
                 const int64_t ic = min(max(i0 + s, 0), ny - 1);
-                v[s] = (ABL & 4) ? (float)(t + s) : p[ic * A.row_stride];
-                if (ARR) mk[s] = (ABL & 2) ? (unsigned char)1 : pm[ic * A.mask.row_stride];
+                v[s] = p[ic * A.row_stride];
+                if (ARR) mk[s] = pm[ic * A.mask.row_stride];
             }
         } else {
             const float* q = p + (int64_t)i0 * A.row_stride;
             const uint8_t* qm = ARR ? pm + (int64_t)i0 * A.mask.row_stride : nullptr;
 #pragma unroll
             for (int s = 0; s < R; ++s) {
-                v[s] = (ABL & 4) ? (float)(t + s) : q[(int64_t)s * A.row_stride];
-                if (ARR) mk[s] = (ABL & 2) ? (unsigned char)1 : qm[(int64_t)s * A.mask.row_stride];
+                v[s] = q[(int64_t)s * A.row_stride];
+                if (ARR) mk[s] = qm[(int64_t)s * A.mask.row_stride];
             }
         }
     };
@@ -434,8 +432,8 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
     // row s of the revolution starting at i0 (the rolling prefetch of the next revolution: v[s] is free once step s has used it)
     auto load_row = [&](int i0, int s) {
         const int64_t ic = min(max(i0 + s, 0), ny - 1);
-        v[s] = (ABL & 4) ? (float)(t + s + i0) : p[ic * A.row_stride];
-        if (ARR) mk[s] = (ABL & 2) ? (unsigned char)1 : pm[ic * A.mask.row_stride];
+        v[s] = p[ic * A.row_stride];
+        if (ARR) mk[s] = pm[ic * A.mask.row_stride];
     };
     const int T = (ye - yb) + 2 * H;
     load_rows(yb - H);
@@ -460,8 +458,7 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
     #pragma unroll
                     for (int k = 0; k < kRun; ++k) {
                         const int widx = k + 2 * H - i;       // kx index for output k, input i
-                        if (ABL & 16) { if (widx == H) r[k] = in; }
-                        else if (widx >= 0 && widx <= 2 * H) pk_fma_w(r[k], ISO ? A.ky : A.kx, widx, in);
+                        if (widx >= 0 && widx <= 2 * H) pk_fma_w(r[k], ISO ? A.ky : A.kx, widx, in);
                     }
                 }
                 const int64_t xo = x0 + kRun * j;
@@ -482,9 +479,7 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
                         }
                     }
                 }
-                if ((ABL & 1) && !(res[0] == 12345.678f && res[5] == 3.25f && res[7] == res[2])) {
-                    // ablation: no stores (the impossible condition keeps the arithmetic alive)
-                } else if (R <= kPairedStoreMaxR && pairable) {
+                if (R <= kPairedStoreMaxR && pairable) {
                     store_run8_paired(dst, t & 1, f32x4{res[0], res[1], res[2], res[3]}, f32x4{res[4], res[5], res[6], res[7]});
                 } else if (xo + kRun <= A.nx && ((((uintptr_t)dst) & 15) == 0)) {
                     *reinterpret_cast<f32x4*>(dst) = f32x4{res[0], res[1], res[2], res[3]};
@@ -507,8 +502,7 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
 #pragma unroll
             for (int m = 0; m < R; ++m) {
                 const int a = (s - m + R) % R;
-                if (ABL & 8) { if (a == 0) acc[m] = x2; }
-                else if (a == 0) pk_mul_w(acc[m], A.ky, 2 * H - a, x2);
+                if (a == 0) pk_mul_w(acc[m], A.ky, 2 * H - a, x2);
                 else pk_fma_w(acc[m], A.ky, 2 * H - a, x2);
             }
             // row o = i0 + s - H is complete: park it in the group's LDS slot
@@ -545,25 +539,25 @@ __global__ __launch_bounds__(kThreads, R == 29 ? 3 : 1) void spatial_sep_kernel(
 //   * the x pass divides without looking at the denominator (0 * (1 / 0) is the NaN an empty window needs for a kernel
 //     with a non-zero centre tap); the filled-centre rule of astropy for an empty window whose centre sample is valid
 //     (kernels with a zero centre tap) is a wave-uniform rare branch.
-// BT = threads per block = input columns per strip: 512 (two blocks of 8 waves per CU) wastes half as much as 256 on
-// the strip's halo columns in the y pass (28 of 512 instead of 28 of 256) and on idle lanes in the x pass (8 rows x 60
-// runs = 480 tasks for 512 lanes instead of 224 for 256).
-constexpr int grouped_txo(int R, int BT) { return ((BT - 2 * (R / 2)) / kRun) * kRun; }
-constexpr int grouped_pitch(int BT) { return BT == 256 ? 316 : 604; }     // float2 per LDS row, = 28 (mod 32): see spatial_sep_kernel
+// Threads per block = input columns per strip = kThreads.  512 would waste half as much on the strip's halo columns in
+// the y pass and on idle lanes in the x pass, but measured slower (8.76 ms against 8.29 ms at 512 x 2048^2 with a uint8
+// mask: barriers over 8 waves and two blocks per CU).
+constexpr int grouped_txo(int R) { return ((kThreads - 2 * (R / 2)) / kRun) * kRun; }
+constexpr int kGroupedPitch = 316;            // float2 per LDS row, = 28 (mod 32): see spatial_sep_kernel
 // SYM (with ISO): the taps are symmetric (every Gaussian) and addressed folded, k[min(j, 2H - j)]: 15 distinct weights
 // = 8 SGPR pairs instead of 15 - unfolded the kernel spilled 57 SGPRs (104 v_readlane + 57 v_writelane per revolution).
 #ifndef SPC_GROUPED_PF
 #define SPC_GROUPED_PF 1          // groups of rows staged ahead (experiment: 2 needs 16 more registers -> 3 blocks per CU)
 #endif
-template <int R, bool ARR, bool PRED, bool ISO, int BT, bool SYM, int ABL = 0>
-__global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) void spatial_sep_grouped_kernel(const SpArgs A) {
+template <int R, bool ARR, bool PRED, bool ISO, bool SYM>
+__global__ __launch_bounds__(kThreads, SPC_GROUPED_PF == 1 ? 1024 / kThreads : 768 / kThreads) void spatial_sep_grouped_kernel(const SpArgs A) {
     constexpr int H = R / 2;
     static_assert(!SYM || ISO, "folded weights are for kx == ky");
     auto wj = [](int j) { return SYM ? (j <= H ? j : 2 * H - j) : j; };
     constexpr int kG = 8;                                 // rows per group
     constexpr int NG = (R + kG - 1) / kG;
-    constexpr int kPitch = grouped_pitch(BT);
-    static_assert(kPitch >= BT + BT / 8, "LDS row too short");
+    constexpr int kPitch = kGroupedPitch;
+    static_assert(kPitch >= kThreads + kThreads / 8, "LDS row too short");
     // (one buffer, two barriers per group: with two buffers - one barrier - the block needs 40 KB and only three fit
     // a CU: 9.1 ms against 8.2 ms at 512 x 2048^2)
     __shared__ float2v yres[kG * kPitch];
@@ -572,7 +566,7 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
     int strip;
     int64_t z;
     spc_xcd_order(A.xcd_swizzle, strip, z);
-    constexpr int kTxo = grouped_txo(R, BT);              // output columns per strip
+    constexpr int kTxo = grouped_txo(R);                  // output columns per strip
     const int64_t x0 = (int64_t)strip * kTxo;             // first output column of the strip
     if (A.status) {   // both fast tiles this strip overlaps were finished by the all-valid kernel
         const int ft = fast_txo(R);
@@ -582,14 +576,14 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
     const int nrun_eff = ((int)min((int64_t)kTxo, A.nx - x0) + kRun - 1) / kRun;
     const int ncols = nrun_eff * kRun + 2 * H;
     if ((t & ~63) >= ncols) return;
-    const int nthr = min(BT, (ncols + 63) & ~63);
+    const int nthr = min(kThreads, (ncols + 63) & ~63);
     const float inv_nrun = 1.0f / (float)nrun_eff;
     const int ny = (int)A.ny;
     const int yb = (int)(blockIdx.z * A.ychunk);
     const int ye = (int)min((int64_t)ny, (int64_t)yb + A.ychunk);
     const int64_t xin = x0 - H + t;                       // input column of this lane (y pass)
     const bool col_in = (xin >= 0) && (xin < A.nx);
-    const bool edge_cols = (x0 - H < 0) || (x0 - H + BT > A.nx);     // block-uniform
+    const bool edge_cols = (x0 - H < 0) || (x0 - H + kThreads > A.nx);     // block-uniform
     const int64_t xc = min(max(xin, (int64_t)0), A.nx - 1);
     const float lim = A.pred_lim, lo = A.pred_lo, hi = A.pred_hi;
     // one descriptor per plane; accesses = descriptor + lane byte offset (VGPR) + row byte offset (SGPR)
@@ -617,8 +611,8 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
         for (int s = 0; s < kG; ++s) {
             if (s < n) {
                 const int ic = min(max(first_row + s, 0), ny - 1);                    // uniform
-                v[slot][s] = (ABL & 4) ? (float)(t + s) : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, (int)((unsigned)ic * rbytes), 0));
-                if (ARR) mk[slot][s] = (ABL & 2) ? 1u : (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rm, moff, (int)((unsigned)ic * mrbytes), 0);
+                v[slot][s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, (int)((unsigned)ic * rbytes), 0));
+                if (ARR) mk[slot][s] = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rm, moff, (int)((unsigned)ic * mrbytes), 0);
             }
         }
     };
@@ -641,8 +635,7 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
 #pragma unroll
                 for (int m = 0; m < R; ++m) {
                     const int a = (s - m + R) % R;
-                    if (ABL & 8) { if (a == 0) acc[m] = x2; }
-                    else if (a == 0) pk_mul_w(acc[m], A.ky, wj(2 * H - a), x2);
+                    if (a == 0) pk_mul_w(acc[m], A.ky, wj(2 * H - a), x2);
                     else pk_fma_w(acc[m], A.ky, wj(2 * H - a), x2);
                 }
                 // row o = i0 + s - H is complete: park it in the group's LDS slot
@@ -671,8 +664,7 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
 #pragma unroll
                     for (int k = 0; k < kRun; ++k) {
                         const int widx = k + 2 * H - i;       // kx index for output k, input i
-                        if (ABL & 16) { if (widx == H) r[k] = in; }
-                        else if (widx >= 0 && widx <= 2 * H) pk_fma_w(r[k], ISO ? A.ky : A.kx, wj(widx), in);
+                        if (widx >= 0 && widx <= 2 * H) pk_fma_w(r[k], ISO ? A.ky : A.kx, wj(widx), in);
                     }
                 }
                 const int64_t xo = x0 + kRun * j;
@@ -701,9 +693,7 @@ __global__ __launch_bounds__(BT, SPC_GROUPED_PF == 1 ? 1024 / BT : 768 / BT) voi
                 }
                 const int ooff = (int)((unsigned)o * orbytes + (unsigned)(xo * 4));   // (< 4 GiB per plane: checked on the host)
                 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                if ((ABL & 1) && !(res[0] == 12345.678f && res[5] == 3.25f && res[7] == res[2])) {
-                    // ablation: no stores (the impossible condition keeps the arithmetic alive)
-                } else if (out_vec && xo + kRun <= A.nx) {
+                if (out_vec && xo + kRun <= A.nx) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{res[0], res[1], res[2], res[3]}), ro, ooff, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{res[4], res[5], res[6], res[7]}), ro, ooff + 16, 0, 0);
                 } else {
@@ -774,43 +764,16 @@ int launch_sep(const SpArgs& A, hipStream_t st, dim3 grid, bool arr) {
     }
     const bool pred = (A.mask.flags & (SPC_MASK_GT | SPC_MASK_GE | SPC_MASK_LT | SPC_MASK_LE)) != 0;
     // non-isotropic kernels only come in the PRED flavour (a superset: absent bounds are NaN)
-#ifdef SPC_ABLATE
     if constexpr (R == 29) {
-        const int abl = spc_switch("SPC_SPATIAL_ABLATE", 0);
-        if (abl && iso && !pred && arr) {
-            switch (abl) {
-                case 1: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 1>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 2: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 2>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 3: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 3>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 6: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 6>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 7: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 7>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 8: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 8>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 16: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 16>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 24: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 24>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                case 31: hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, true, false, true, 256, true, 31>), dim3((unsigned)((A.nx + grouped_txo(R, 256) - 1) / grouped_txo(R, 256)), grid.y, grid.z), dim3(256), 0, st, A); break;
-                default: spc_set_error("no such ablation"); return SPC_ERR_UNSUPPORTED;
-            }
-            SPC_LAUNCH_CHECK();
-            return SPC_OK;
-        }
-    }
-#endif
-    if constexpr (R == 29) {
-        // grouped pipeline; planes of 2 GiB and more keep the round-2 kernel
-        // 0: round-2 kernel, 256 / 512: threads per block.  Measured at 512 x 2048^2 with a uint8 mask (same box): round-2
-        // kernel 9.01 ms, 256 threads 8.29 ms, 512 threads 8.76 ms (less halo and fewer idle x-pass lanes, but barriers
-        // over 8 waves and two blocks per CU)
-        const int want = spc_switch("SPC_SPATIAL_GROUPED", 256);
+        // grouped pipeline; planes of 2 GiB and more keep the round-2 kernel.  Measured at 512 x 2048^2 with a uint8 mask
+        // (same box): round-2 kernel 9.01 ms, grouped 8.29 ms
         // (byte offsets inside a plane stay below 2 GiB, like the spectral kernels: larger planes keep 64-bit addressing)
         const bool fits = (uint64_t)A.plane_stride * 4 < (1ull << 31) && (uint64_t)A.out_plane_stride * 4 < (1ull << 31) &&
                           (!arr || (uint64_t)A.mask.plane_stride < (1ull << 31));
-        if (want && fits) {
-            const int bt = (want == 256 || A.nx < 384) ? 256 : 512;
-            const int txo = bt == 256 ? grouped_txo(R, 256) : grouped_txo(R, 512);
-            dim3 ggrid((unsigned)((A.nx + txo - 1) / txo), grid.y, grid.z), gblock(bt);
-#define SPC_GROUPED(ARRV, PREDV, ISOV, SYMV)                                                                                              \
-            do { if (bt == 256) hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, ARRV, PREDV, ISOV, 256, SYMV>), ggrid, gblock, 0, st, A);  \
-                 else hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, ARRV, PREDV, ISOV, 512, SYMV>), ggrid, gblock, 0, st, A); } while (0)
+        if (fits) {
+            const int txo = grouped_txo(R);
+            dim3 ggrid((unsigned)((A.nx + txo - 1) / txo), grid.y, grid.z), gblock(kThreads);
+#define SPC_GROUPED(ARRV, PREDV, ISOV, SYMV) hipLaunchKernelGGL((spatial_sep_grouped_kernel<R, ARRV, PREDV, ISOV, SYMV>), ggrid, gblock, 0, st, A)
             const bool symk = iso && is_sym(A.ky, R);
             if (symk && !pred) { if (arr) SPC_GROUPED(true, false, true, true); else SPC_GROUPED(false, false, true, true); }
             else if (symk) { if (arr) SPC_GROUPED(true, true, true, true); else SPC_GROUPED(false, true, true, true); }

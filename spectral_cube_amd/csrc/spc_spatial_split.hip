@@ -741,7 +741,8 @@ int spc_spatial_split_launch(hipStream_t st, const spc_cube_f32* cube, const Mas
     // measured at 256 x 2048^2 + uint8 mask (profiles/r05_split_fetch_ab.txt): fetch / algorithmic x1.97 as built first, x1.52 with
     // mirrored odd bands, x1.43 with the rendezvous per channel as well; the time does not move (the kernel is bound by issue).
     // The three-sum form (16-row regions, three times the steps per channel) loses 8 % to the rendezvous: not there.
-    A.mirror = spc_switch("SPC_SPLIT_MIRROR", 1); A.sync = spc_switch("SPC_SPLIT_SYNC", 1); A.wide_mask = spc_switch("SPC_SPLIT_WIDE_MASK", 1);
+    // (mirror, sync: always on; still kernel arguments: as a constant they cost kernels of this family registers or spills (profiles/retired_switches_resources.txt))
+    A.mirror = 1; A.sync = 1; A.wide_mask = spc_switch("SPC_SPLIT_WIDE_MASK", 1);
     SPC_REQUIRE(ntaps == Geo<3>::R || ntaps == Geo<5>::R, "internal: the split form takes taps padded to 33 or 65 entries");
     const int nb = ntaps == Geo<3>::R ? 3 : 5;
     for (int i = 0; i < kMaxTaps + 3; ++i) { A.ky[i] = i < ntaps ? ky[i] : 0.f; A.kx[i] = i < ntaps ? kx[i] : 0.f; }
@@ -749,10 +750,8 @@ int spc_spatial_split_launch(hipStream_t st, const spc_cube_f32* cube, const Mas
     int nrt = geo.nrt;
     if (nsum == 0) {
         // cube -> cube: nothing of a band lives in LDS, so a wave marches down the WHOLE column (round 6): NRT + 2 HB steps for NRT
-        // output row tiles - 130 for 128 at 2048 rows, where the 64-row bands took 192 (SPC_SPLIT_BAND_TILES: row tiles per band)
-        static const int env_tiles = spc_switch("SPC_SPLIT_BAND_TILES", 0);
-        const int64_t all = (cube->ny + 15) / 16;
-        nrt = (int)(env_tiles > 0 ? std::min<int64_t>(env_tiles, all) : all);
+        // output row tiles - 130 for 128 at 2048 rows, where the 64-row bands took 192
+        nrt = (int)((cube->ny + 15) / 16);
     }
     A.nrt = nrt;
     A.nstrips = (int)((cube->nx + geo.waves_x * geo.oc - 1) / (geo.waves_x * geo.oc));

@@ -227,9 +227,8 @@ struct WmArgs {
 
 typedef float f32x4w __attribute__((ext_vector_type(4)));
 
-template <int U>
 __global__ __launch_bounds__(256) void weighted_moments_kernel(const WmArgs A) {
-    constexpr int ZW = 4;
+    constexpr int ZW = 4, U = 8;                       // U planes (stride ZW) in flight per lane
     __shared__ double sh[ZW - 1][4][4][64];            // wave, {s0, s1, s2, chk}, column, lane
     // (the wave index through readfirstlane: a plane's address offset and its three weights are then provably uniform -
     //  scalar loads instead of three per-lane loads per plane, round 4)
@@ -341,9 +340,7 @@ int try_weighted_moments(ConvArgs& A, const spc_cube_f32* cube, const double* h_
     WmArgs W{};
     W.cube = A.cube; W.nz = A.nz; W.ny = A.ny; W.nx = A.nx; W.row_stride = A.row_stride; W.plane_stride = A.plane_stride;
     W.w = d_w; W.dv = A.dv; W.m1_add = A.m1_add; W.mo = A.mo; W.mo_row_stride = A.mo_row_stride; W.status = d_status;
-    static const int wm_u = spc_switch("SPC_WMOM_U", 8);      // tuning hook
-    if (wm_u == 4) hipLaunchKernelGGL(weighted_moments_kernel<4>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
-    else hipLaunchKernelGGL(weighted_moments_kernel<8>, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
+    hipLaunchKernelGGL(weighted_moments_kernel, dim3((unsigned)((A.nx + 255) / 256), (unsigned)A.ny), dim3(256), 0, st, W);
     A.status = d_status;
     *took = 1;
     return SPC_OK;
@@ -373,9 +370,8 @@ int launch_ring(int R, ConvArgs& A, hipStream_t st, int vec, bool fuse, unsigned
     return launch_ring_raw(R, A, st, vec, fuse);
 }
 
-// two spaxels per lane need 8-byte aligned rows everywhere (SPC_CONV_VEC=1 forces one)
+// two spaxels per lane need 8-byte aligned rows everywhere
 int pick_vec(const spc_cube_f32* c, const MaskDev& m, const float* out, int64_t out_row, int64_t out_plane) {
-    if (spc_switch("SPC_CONV_VEC", 0) == 1) return 1;
     bool ok = (c->nx % 2 == 0) && (c->row_stride % 2 == 0) && (c->plane_stride % 2 == 0) &&
               (((uintptr_t)c->d_data) % 8 == 0);
     if (m.flags & SPC_MASK_ARRAY)
@@ -446,7 +442,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
         nsplit = std::max(nsplit, 1);
     }
     A.zchunk = (cube->nz + nsplit - 1) / nsplit;
-    A.skip_dead = spc_switch("SPC_SPECTRAL_SKIP_DEAD", 1);
+    A.skip_dead = 1;         // (still a kernel argument: as a constant it cost kernels of this family registers or spills (profiles/retired_switches_resources.txt))
     nsplit = (int)((cube->nz + A.zchunk - 1) / A.zchunk);
     dim3 grid((unsigned)nblocks, (unsigned)nsplit);
     hipStream_t st = (hipStream_t)stream;
@@ -457,7 +453,7 @@ int spc_spectral_conv_f32(int device, void* stream, const spc_cube_f32* cube, co
     }
     // no ring for this kernel: runs-of-16 kernel for 17 taps or more, per-output tap loop below that
     // (taps in the workspace, written there by kernel-argument uploads: nothing waits)
-    const bool wide = spc_switch("SPC_CONV_WIDE", 1) != 0 && ntaps >= 17;
+    const bool wide = ntaps >= 17;
     const int npad = wide ? ntaps + 30 : ntaps;
     std::vector<double> hk((size_t)npad, 0.0);
     for (int i = 0; i < ntaps; ++i) hk[(wide ? 15 : 0) + i] = h_kernel[i];
@@ -575,7 +571,7 @@ int spc_spectral_conv_moments_f32(int device, void* stream, const spc_cube_f32* 
         if (worst <= 1e-13 * std::max(span, 1e-300)) { A.cen_linear = 1; A.cen_c0 = c0; A.cen_dc = dc; }
     }
     A.zchunk = cube->nz;
-    A.skip_dead = spc_switch("SPC_SPECTRAL_SKIP_DEAD", 1);
+    A.skip_dead = 1;
     const int vec = pick_vec(cube, A.mask, nullptr, 0, 0);
     int took = 0;
     rc = try_weighted_moments(A, cube, h_kernel, ntaps, st, d_status, d_w, &took);

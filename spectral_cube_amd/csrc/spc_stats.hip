@@ -716,10 +716,7 @@ __global__ __launch_bounds__(256) void stats_finish_kernel(const double* partial
     if (t < 5) out[t] = s[t][0];
 }
 
-int env_blocks() {
-    const int v = spc_switch("SPC_STATS_BLOCKS", 2048);      // tuning hook; 2048 = 8 blocks per CU
-    return v > 0 ? std::min(v, 4095) : 2048;                 // (the workspace holds 4096 records: one is the finished one)
-}
+constexpr int kStatsBlocks = 2048;      // 8 blocks per CU (the workspace holds 4096 records: one is the finished one)
 
 int fill_common(StatArgs& A, const spc_cube_f32* cube, const spc_mask* mask) {
     int rc = spc_check_cube(cube);
@@ -751,7 +748,7 @@ int spc_stats_global_f32(int device, void* stream, const spc_cube_f32* cube, con
     else { A.nrows = A.nz * A.ny; A.rowlen = A.nx; A.row_a = A.plane_stride; A.row_b = A.row_stride; }
     // enough blocks to fill the chip, few enough that the host-side finish is trivial
     const int64_t per_block = 256 * 4 * 8;                   // one group: 8 chunks of 256 x 16 bytes
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(env_blocks(), contig ? (A.rowlen + per_block - 1) / per_block : (A.nrows + 3) / 4));
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(kStatsBlocks, contig ? (A.rowlen + per_block - 1) / per_block : (A.nrows + 3) / 4));
     SpcWorkspace ws(d_workspace, workspace_bytes);
     SPC_WS_TAKE(d_partial, ws, double, 5 * (size_t)(nblocks + 1));
     A.partial = d_partial;

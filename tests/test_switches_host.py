@@ -1,8 +1,10 @@
-"""CPU: the library's environment switches have one reader (spc_switch in spc_common.h), and the arithmetic of the masked
+"""CPU: the library's environment switches have one reader (spc_switch in spc_common.h), every one of them is set by something
+in the tree and listed in docs/DESIGN_NOTES.md (8b), and the arithmetic of the masked
 spatial stencil is a setting of the calling thread (spc_set_masked_spatial_form) behind ops.masked_spatial_arithmetic: it
 nests, no other thread sees it, an exception restores it and the process environment is never written."""
 import glob
 import os
+import re
 import threading
 
 import pytest
@@ -122,3 +124,54 @@ def test_the_environment_is_read_in_one_place():
             if "getenv" in line:
                 hits.append((os.path.basename(path), i))
     assert len(hits) == 1 and hits[0][0] == "spc_common.h", hits
+
+
+# ---- no switch without a setter -------------------------------------------------------------------------------------
+# A switch of the library stays only while something in the tree gives it a value: a test, a tool, bench.py or the Python
+# package.  The ones below are read and set by nothing, each for a reason:
+UNSET_ON_PURPOSE = {
+    "SPC_POOL_POISON": "a documented debugging feature of the buffer pool (include/spcube_hip.h), for whole-suite runs by hand",
+    "SPC_MOMENTS_VEC": "spc_moments_workspace_bytes reads it beside SPC_MOMENTS_NSPLIT: the moment kernel's tuning set stays whole",
+}
+_READ = re.compile(r"""spc_switch(?:_text)?\(\s*"(SPC_[A-Z0-9_]+)\"""")
+# set or forwarded: the name as a whole string literal (setenv, os.environ[...], os.environ.get, an env dict's key, a
+# (name, value) pair) or as a keyword of dict(os.environ, NAME=...).  Prose that mentions NAME=0 sets nothing.
+_SET = re.compile(r"""["'](SPC_[A-Z0-9_]+)["']|\b(SPC_[A-Z0-9_]+)\s*=\s*["']""")
+
+
+def _switches_read():
+    names = set()
+    for path in sorted(glob.glob(os.path.join(REPO, "spectral_cube_amd", "csrc", "*"))):
+        if os.path.isfile(path):
+            names.update(_READ.findall(open(path, errors="replace").read()))
+    return names
+
+
+def _switches_set():
+    paths = [os.path.join(REPO, "bench.py")] + glob.glob(os.path.join(REPO, "spectral_cube_amd", "*.py"))
+    for top in ("tests", "tools"):
+        for root, _dirs, files in os.walk(os.path.join(REPO, top)):
+            paths += [os.path.join(root, f) for f in files if f.endswith((".py", ".sh"))]
+    names = set()
+    for path in paths:
+        if os.path.abspath(path) == os.path.abspath(__file__):
+            continue                                                   # the allow-list above sets nothing
+        for quoted, keyword in _SET.findall(open(path, errors="replace").read()):
+            names.add(quoted or keyword)
+    return names
+
+
+def test_every_switch_the_library_reads_is_set_by_something_in_the_tree():
+    read, given = _switches_read(), _switches_set()
+    assert len(read) > 20, "the search for spc_switch sites found too little: %s" % sorted(read)
+    assert not (read - given - set(UNSET_ON_PURPOSE)), "read in csrc/ and set by nothing: %s" % sorted(read - given - set(UNSET_ON_PURPOSE))
+    # (and the allow-list holds nothing that has gone or that something sets by now)
+    assert set(UNSET_ON_PURPOSE) <= read - given, sorted(set(UNSET_ON_PURPOSE) - (read - given))
+
+
+def test_the_design_notes_list_exactly_the_switches_that_are_read():
+    notes = open(os.path.join(REPO, "docs", "DESIGN_NOTES.md")).read()
+    table = notes.split("### The switches the library reads", 1)[1].split("\n## ", 1)[0]
+    listed = re.findall(r"^\| `(SPC_[A-Z0-9_]+)` \|", table, flags=re.M)
+    assert len(listed) == len(set(listed)), "a switch is listed twice"
+    assert set(listed) == _switches_read()

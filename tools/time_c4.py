@@ -42,4 +42,4 @@ if "f012" in which.split(","):
     res.append("fused m012 %.3f" % timeit(lambda: ops.spatial_conv_mfma_moments(cube, k2, cen, dv=500.0, m1_add=0.0, mask=ms)))
 if "mat" in which.split(","):
     res.append("cube->cube %.3f" % timeit(lambda: ops.spatial_conv_mfma(cube, k2, mask=ms, out=out)))
-print("nz=%d mask=%s dead-skip=%s: " % (nz, sys.argv[3] if len(sys.argv) > 3 else "random", os.environ.get("SPC_SPLIT_DEAD", "1")) + ", ".join(res) + "  (ms; x%d for 4096 planes)" % (4096 // nz))
+print("nz=%d mask=%s: " % (nz, sys.argv[3] if len(sys.argv) > 3 else "random") + ", ".join(res) + "  (ms; x%d for 4096 planes)" % (4096 // nz))

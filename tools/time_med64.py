@@ -1,4 +1,5 @@
-"""scratch: float64 median along z at 512 (or argv[1]) x 1024 x 1024 + uint8 mask, per form of the kernel (SPC_SELECT64 = 0 | 1 | 2)"""
+"""scratch: float64 median along z at 512 (or argv[1]) x 1024 x 1024 + uint8 mask, per form of the kernel (SPC_SELECT64 = 1 | 2 in the
+caller's environment: keys in LDS for every ray length | in registers up to 1024 samples, the default)"""
 import sys, os
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
