@@ -487,6 +487,51 @@ int spc_mask_morph_u8(int device, void* stream, int64_t nz, int64_t ny, int64_t 
                       int op, const int8_t* h_offsets, int noffsets, int iterations, int border_value,
                       uint8_t* d_out, void* d_workspace, size_t workspace_bytes, int64_t* h_iterations_run);
 
+/* ---- connected components of an include array: labels, sizes and bounding boxes, selection by label ----
+ * What users of the reference do on the host with scipy.ndimage.label, np.bincount and scipy.ndimage.find_objects on
+ * cube.get_mask_array() (spectral_cube.py:552), here on the uint8 include array where it lives.
+ *
+ * spc_label_u8: d_in is a (nz, ny, nx) uint8 array, any non-zero byte = True, strides in elements as for
+ * spc_mask_morph_u8 (0 = C-contiguous; rows / planes views are read in place).  h_structure: 27 HOST bytes, the 3x3x3
+ * structure in C order, any non-zero byte = True.  Two True voxels p and p + o belong together when entry o + (1, 1, 1) is
+ * True.  The structure must be centrosymmetric (entry t and entry 26 - t agree for every t; scipy raises on any other):
+ * SPC_ERR_INVALID.  Its centre (entry 13) is ignored, an all-False structure makes every True voxel a component of its
+ * own: the connectivity is 13 bits, one per pair of opposite neighbours.
+ * d_labels: (nz, ny, nx) int32, C-contiguous, not overlapping d_in: 0 for a False voxel, else the number of the voxel's
+ * component, 1 ... *h_nlabels, components numbered in raster order of their first voxel (smallest linear index) - the
+ * array scipy.ndimage.label(in != 0, structure) returns, numbering included.  *h_nlabels receives the number of
+ * components: these 8 bytes and the status are all that reach the host, and the call waits for its stream to read them.
+ * The labels are made by a union-find on d_labels itself in a fixed sequence of at most six launches, whatever the shape of the
+ * components; nothing is repeated until it settles (csrc/spc_label.hip).  d_workspace: the number of bytes the query
+ * returns for the same shape (a few hundred KiB at most); the query is 0 for a shape that is not positive and never
+ * decreases when an axis grows.
+ * Linear indices are int32: nz * ny * nx > 2^31 - 1 is refused with SPC_ERR_UNSUPPORTED (1024^3 fits).  No other limit on
+ * any axis.  SPC_ERR_INVALID before any device work: a NULL pointer, a shape that is not positive, a stride too small,
+ * d_labels overlapping d_in, a workspace too small or overlapping an array.
+ *
+ * spc_label_objects_i32: d_labels as above with labels 0 ... nlabels.  d_sizes: int64[nlabels + 1], d_sizes[k] = the number
+ * of voxels with label k, entry 0 the background (np.bincount(labels, minlength = nlabels + 1)).  d_bbox:
+ * int32[(nlabels + 1) x 6] = zlo, zhi, ylo, yhi, xlo, xhi of label k with hi exclusive: the slices of
+ * scipy.ndimage.find_objects (a label without a voxel keeps lo = INT32_MAX, hi = 0).  The entry initialises both tables.
+ * A label outside 0 ... nlabels never indexes the tables: the voxel is skipped and the call returns SPC_ERR_INVALID,
+ * through a device flag that is read with the status (the call waits for its stream).  d_workspace holds that flag:
+ * SPC_LABEL_OBJECTS_WORKSPACE_BYTES, or what the query above returns, which is never less.
+ *
+ * spc_label_select_i32: d_out[p] = d_keep[d_labels[p]] != 0, written as 0 / 1; d_keep: uint8[nlabels + 1] on the
+ * device (a label outside 0 ... nlabels gives 0).  The table is staged in LDS when it fits.  d_out: (nz, ny, nx) uint8,
+ * C-contiguous, overlapping neither d_labels nor d_keep.  Nothing reaches the host.
+ *
+ * All three: the same shape checks and limit; outputs, tables and workspace may hold anything when the call begins. */
+#define SPC_LABEL_OBJECTS_WORKSPACE_BYTES 256
+size_t spc_label_workspace_bytes(int64_t nz, int64_t ny, int64_t nx);
+int spc_label_u8(int device, void* stream, int64_t nz, int64_t ny, int64_t nx,
+                 const uint8_t* d_in, int64_t in_row_stride, int64_t in_plane_stride, const uint8_t* h_structure,
+                 int32_t* d_labels, void* d_workspace, size_t workspace_bytes, int64_t* h_nlabels);
+int spc_label_objects_i32(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const int32_t* d_labels, int64_t nlabels,
+                          int64_t* d_sizes, int32_t* d_bbox, void* d_workspace, size_t workspace_bytes);
+int spc_label_select_i32(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const int32_t* d_labels, int64_t nlabels,
+                         const uint8_t* d_keep, uint8_t* d_out);
+
 /* ---- rank filters: median / minimum / maximum / percentile / rank over a sliding window ----
  * spectral_smooth_median / spectral_filter (spectral_cube.py:2844-2898, dask_spectral_cube.py:920-960) and
  * spatial_smooth_median / spatial_filter (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029) with a filter of

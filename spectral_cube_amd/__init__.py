@@ -25,3 +25,5 @@ from .cube_utils import combine_headers, mosaic_cubes  # noqa: F401
 from . import morphology  # noqa: F401
 from .morphology import (binary_dilation, binary_erosion, binary_opening, binary_closing, binary_propagation,  # noqa: F401
                          generate_binary_structure)
+from . import labelling  # noqa: F401
+from .labelling import label, remove_small_objects, LabelMap  # noqa: F401

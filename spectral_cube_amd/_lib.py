@@ -48,6 +48,8 @@ ELEM_F32, ELEM_F64, ELEM_U8 = range(3)
 # spc_morph_op and the limits of the offset list (spc_mask_morph_u8)
 MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_REACH, MORPH_MAX_OFFSETS = 3, 343
+# spc_label_u8 / spc_label_objects_i32 / spc_label_select_i32: the most voxels (int32 linear indices), the flag's scratch
+LABEL_MAX_VOXELS, LABEL_OBJECTS_WORKSPACE_BYTES = 2 ** 31 - 1, 256
 # spc_arith_program (spc_arith_f32 / _f64): the step limit and spc_arith_opcode
 ARITH_MAX_STEPS = 4
 AOP_ADD, AOP_SUB, AOP_MUL, AOP_DIV, AOP_POW, AOP_SQUARE, AOP_SQRT, AOP_RECIP, AOP_ONE = range(9)
@@ -240,6 +242,10 @@ SIGNATURES = {
     "spc_mask_morph_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "spc_mask_morph_u8": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i, _i, _i, _vp, _vp, _sz,
                                _P(_i64)]),
+    "spc_label_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "spc_label_u8": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _P(_i64)]),
+    "spc_label_objects_i32": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz]),
+    "spc_label_select_i32": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "spc_arith_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _P(SpcArithProgram), _vp, _i64, _i64]),
     "spc_arith_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _P(SpcArithProgram), _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _f, _vp, _i64, _i64]),

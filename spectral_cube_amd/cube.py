@@ -860,6 +860,14 @@ class SpectralCube:
         from . import morphology
         return self.with_mask(morphology.binary_erosion(self, structure=structure, iterations=iterations), inherit_mask=False)
 
+    def with_mask_pruned(self, min_size=64, min_channels=1, structure=None):
+        """the cube with the small islands of its include map removed on the device (labelling.remove_small_objects;
+        scipy.ndimage.label + np.bincount + find_objects on get_mask_array() for users of the reference): components of
+        fewer than *min_size* voxels or spanning fewer than *min_channels* channels leave the mask"""
+        from . import labelling
+        return self.with_mask(labelling.remove_small_objects(self, min_size=min_size, structure=structure,
+                                                             min_channels=min_channels), inherit_mask=False)
+
     def with_fill_value(self, fill_value):
         out = self._new_cube_with(data=self._data, dev=self._dev, fill_value=fill_value,
                                   lazy=self._lazy, shape=self._shape, same_data=True)

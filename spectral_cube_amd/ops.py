@@ -1276,19 +1276,101 @@ def mask_morph(inp, offsets, op, iterations=1, mask=None, border_value=0, out=No
         raise ValueError("offsets reach beyond +-%d" % _lib.MORPH_MAX_REACH)
     offs = np.ascontiguousarray(offs, dtype=np.int8)
     out = _contiguous_out(out, shape, np.uint8, inp.device)           # (the entry writes a compact array)
-    need = int(_lib.load().spc_mask_morph_workspace_bytes(*shape))
-    if workspace is not None:
-        if workspace.nbytes < need:
-            raise ValueError("workspace of %d bytes given, %d needed" % (workspace.nbytes, need))
-        ws, wsn = C.c_void_p(workspace.ptr), workspace.nbytes
-    else:
-        ws, wsn = _pooled_scratch(inp.device, stream, need)
+    ws, wsn = _scratch(int(_lib.load().spc_mask_morph_workspace_bytes(*shape)), workspace, inp.device, stream)
     run = C.c_int64(0)
     mrs, mps = _strides(mask) if mask is not None else (0, 0)
     _lib.call("spc_mask_morph_u8", inp.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(inp.ptr), *_strides(inp),
               C.c_void_p(mask.ptr) if mask is not None else None, mrs, mps, int(op), offs.ctypes.data_as(C.c_void_p),
               int(offs.shape[0]), int(iterations), int(border_value), C.c_void_p(out.ptr), ws, wsn, C.byref(run))
     return (out, run.value) if return_iterations else out
+
+
+def _scratch(need, workspace, device, stream):
+    """(c_void_p, nbytes) of *workspace* (a uint8 DeviceArray of at least *need* bytes) or of the stream's pooled scratch"""
+    if workspace is not None:
+        if workspace.nbytes < need:
+            raise ValueError("workspace of %d bytes given, %d needed" % (workspace.nbytes, need))
+        return C.c_void_p(workspace.ptr), workspace.nbytes
+    return _pooled_scratch(device, stream, need)
+
+
+def _label_map(labels, nlabels):
+    """(shape, nlabels) of an int32 label array of shape (nz, ny, nx) with labels 0 ... *nlabels*"""
+    if labels.dtype != np.int32 or len(labels.shape) != 3:
+        raise TypeError("labels must be an int32 DeviceArray of shape (nz, ny, nx)")
+    if getattr(labels, "_is_view", False):
+        raise ValueError("labels must be a contiguous array, not a strided view")
+    nlabels = int(nlabels)
+    if not 0 <= nlabels <= _lib.LABEL_MAX_VOXELS:
+        raise ValueError("nlabels must be 0 to 2**31 - 1 (got %d)" % nlabels)
+    return tuple(int(n) for n in labels.shape), nlabels
+
+
+def label_structure(structure):
+    """27 uint8: the (3, 3, 3) *structure* as spc_label_u8 takes it, checked as scipy.ndimage.label checks it"""
+    s = np.asarray(structure)
+    if s.shape != (3, 3, 3):
+        raise ValueError("structure must have shape (3, 3, 3) (got %s)" % (s.shape,))
+    s = np.ascontiguousarray(s != 0, dtype=np.uint8).ravel()
+    if not np.array_equal(s, s[::-1]):
+        raise ValueError("structure must be centrosymmetric: entry o and entry -o of every offset o agree (scipy.ndimage.label "
+                         "refuses any other)")
+    return s
+
+
+def label(inp, structure, out=None, stream=None, workspace=None):
+    """(int32 (nz, ny, nx) DeviceArray, n): the connected components of the include array *inp* (uint8 / bool, any non-zero
+    byte True; a rows() / planes() view is read where it is) under the centrosymmetric (3, 3, 3) *structure*, whose centre
+    is ignored - scipy.ndimage.label(inp != 0, structure), numbering included (spc_label_u8).  At most 2**31 - 1 voxels.
+    *out*: a contiguous int32 array that is not the input; *workspace*: a uint8 DeviceArray of spc_label_workspace_bytes
+    bytes (the stream's pooled scratch otherwise).  Only n (8 bytes) comes back to the host, inside the call."""
+    if inp.dtype.itemsize != 1 or inp.dtype.kind not in "ub" or len(inp.shape) != 3:
+        raise TypeError("label runs on a uint8 / bool DeviceArray of shape (nz, ny, nx)")
+    shape = tuple(int(n) for n in inp.shape)
+    s = label_structure(structure)
+    if shape[0] * shape[1] * shape[2] > _lib.LABEL_MAX_VOXELS:
+        raise NotImplementedError("%s voxels: linear indices are int32, at most 2**31 - 1 voxels are labelled" % (shape,))
+    out = _contiguous_out(out, shape, np.int32, inp.device)
+    ws, wsn = _scratch(int(_lib.load().spc_label_workspace_bytes(*shape)), workspace, inp.device, stream)
+    n = C.c_int64(0)
+    _lib.call("spc_label_u8", inp.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(inp.ptr), *_strides(inp),
+              s.ctypes.data_as(C.c_void_p), C.c_void_p(out.ptr), ws, wsn, C.byref(n))
+    return out, n.value
+
+
+def label_objects(labels, nlabels, out=None, stream=None, workspace=None):
+    """(sizes, bbox): int64 (nlabels + 1,) and int32 (nlabels + 1, 6) DeviceArrays of the int32 label array *labels* with
+    labels 0 ... *nlabels* - sizes[k] = the voxels with label k (entry 0: the background), bbox[k] = zlo, zhi, ylo, yhi,
+    xlo, xhi with hi exclusive, the slices of scipy.ndimage.find_objects (spc_label_objects_i32).  A label outside
+    0 ... nlabels raises ValueError; nothing is written past the tables.  *out*: {"sizes": ..., "bbox": ...}."""
+    shape, nlabels = _label_map(labels, nlabels)
+    sizes = _given(out, "sizes", (nlabels + 1,), np.int64, labels.device)
+    bbox = _given(out, "bbox", (nlabels + 1, 6), np.int32, labels.device)
+    ws, wsn = _scratch(_lib.LABEL_OBJECTS_WORKSPACE_BYTES, workspace, labels.device, stream)
+    _lib.call("spc_label_objects_i32", labels.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(labels.ptr), nlabels,
+              C.c_void_p(sizes.ptr), C.c_void_p(bbox.ptr), ws, wsn)
+    return sizes, bbox
+
+
+def label_select(labels, nlabels, keep, out=None, stream=None):
+    """uint8 (nz, ny, nx) DeviceArray: 1 where *keep*[labels] is non-zero - *keep*: a uint8 / bool table of *nlabels* + 1
+    entries, a DeviceArray or a host array that is uploaded (spc_label_select_i32).  *out*: a contiguous uint8 array."""
+    shape, nlabels = _label_map(labels, nlabels)
+    if not isinstance(keep, DeviceArray):
+        keep = np.ascontiguousarray(keep)
+        if keep.dtype.kind not in "ub" or keep.dtype.itemsize != 1:
+            raise TypeError("keep must be a uint8 / bool table (got %s)" % keep.dtype)
+        if keep.shape != (nlabels + 1,):
+            raise ValueError("keep must have nlabels + 1 = %d entries (got shape %s)" % (nlabels + 1, keep.shape))
+        keep = DeviceArray.from_numpy(keep.view(np.uint8), labels.device, stream)
+    elif keep.dtype.itemsize != 1 or keep.dtype.kind not in "ub" or tuple(keep.shape) != (nlabels + 1,):
+        raise ValueError("keep must be a uint8 / bool table of nlabels + 1 = %d entries (got %s %s)"
+                         % (nlabels + 1, tuple(keep.shape), keep.dtype))
+    out = _contiguous_out(out, shape, np.uint8, labels.device)
+    _lib.call("spc_label_select_i32", labels.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(labels.ptr), nlabels,
+              C.c_void_p(keep.ptr), C.c_void_p(out.ptr))
+    out._keep_table = keep          # the kernel may still be queued: the table lives as long as the result
+    return out
 
 
 def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, out=None):
