@@ -64,7 +64,23 @@ typedef enum {
  * only what that cannot express (an arbitrary Python function) is
  * materialised by the host.
  * A voxel is "valid" when it is included AND its value is not NaN (NaN-filled
- * data fed to nansum, dask_spectral_cube.py:1083). */
+ * data fed to nansum, dask_spectral_cube.py:1083).
+ * The include array, for every entry that takes one (d_array here, the uint8
+ * operands of a spc_mask_program, the inputs of spc_mask_morph_u8 and
+ * spc_label_u8, a keep table):
+ *   - ANY non-zero byte includes: 1, 2, 0x80 and 0xFF mean the same, and a
+ *     caller may hand in bytes of any origin (a bool array, a bit test, a count);
+ *   - a byte is never a weight or a count: it selects, nothing else;
+ *   - no entry reads a cube sample that the array excludes in a way that can
+ *     reach a result: an excluded sample is dropped by a select in front of the
+ *     arithmetic, never by a product with 0, so NaN, +-inf and +-max under
+ *     excluded voxels change no bit of any output.  (spc_subcube_* with
+ *     filled == 0 copies the raw samples: the one entry that shows them.)
+ * Every entry that WRITES a mask (spc_mask_eval_*, spc_mask_include_*, the
+ * d_out_mask of spc_downsample_* and spc_subcube_*, the d_footprint of the
+ * resamplers, spc_mask_morph_u8, spc_label_select_i32) writes 0 / 1 bytes; none
+ * copies the input's bytes.  tests/mask_patterns.py and
+ * tests/test_gpu_mask_patterns.py hold every masked entry to this. */
 #define SPC_MASK_NONE   0u
 #define SPC_MASK_ARRAY  1u
 #define SPC_MASK_FINITE 2u
@@ -338,7 +354,7 @@ int spc_mask_include_f64(int device, void* stream, const spc_cube_f64* cube, con
  * data means (NotNaNMask, the mask spectral_interpolate attaches, lowers to no term: a reduction skips NaN anyway, but
  * here excluded voxels become `fill` and drop out of the include map).
  * d_out: the output view, strides in elements (0 = C-contiguous), so that strips of a larger output are written in
- * place; d_out_mask (uint8, 1 = included; may be NULL) has the same strides.  Every input byte is read once, with 16-byte
+ * place; d_out_mask (uint8, written as 0 / 1; may be NULL) has the same strides.  Every input byte is read once, with 16-byte
  * loads (4-byte for the mask array) when every input row and plane starts 16-byte aligned - for axes 0 / 1 the outputs'
  * rows and planes as well, for axis 2 with factor > 512 a factor that is a multiple of 4 samples - and with one load
  * per sample otherwise (e.g. float32 rows with nx % 4 != 0).  No workspace. */
@@ -361,8 +377,8 @@ int spc_downsample_f64(int device, void* stream, const spc_cube_f64* cube, const
  * filled == 0: the samples are copied bit for bit (the new cube's unmasked data, NaN payloads included); filled != 0:
  * `fill` is written where the voxel is excluded (the FILLED 2-D / 1-D results of integer indices, :1362-1370).
  * d_out_mask (uint8, may be NULL): include of the parent's lowered mask at the source voxel, with the nan_excluded rule
- * of spc_downsample_*.  d_out / d_out_mask share the output strides (elements, 0 = C-contiguous), so that strips of a
- * larger result are written in place.  Only selected rows are addressed: skipped planes and rows are never read.
+ * of spc_downsample_*, written as 0 / 1 (the byte of the parent's array is evaluated, not copied).  d_out / d_out_mask
+ * share the output strides (elements, 0 = C-contiguous), so that strips of a larger result are written in place.  Only selected rows are addressed: skipped planes and rows are never read.
  * Along x a step of 1 uses 16-byte loads and stores (4-byte for the mask bytes) when the selected source rows, start[2]
  * and the output rows are 16-byte aligned, one load per sample otherwise; any other x step one load per selected sample.
  * Launches are split inside: no limit on any axis.  No workspace. */
@@ -1095,7 +1111,7 @@ int spc_wcs_pixel_map_f64(int device, void* stream, const spc_celestial_wcs* wcs
  * whose source falls outside [-0.5, n-0.5] are NaN and get footprint 0.
  * order: 1 = bilinear (a NaN neighbour propagates even with weight 0, as in
  * scipy.ndimage.map_coordinates), 0 = nearest neighbour (floor(x + 0.5)).
- * d_footprint (uint8, (ny_out,nx_out)) may be NULL.  d_any_valid (one uint32 in
+ * d_footprint (uint8, (ny_out,nx_out), written as 0 / 1) may be NULL.  d_any_valid (one uint32 in
  * HBM, may be NULL) is set to 1 iff some output value is not NaN: the reference's
  * "All values in reprojected cube are nan" check (spectral_cube.py:2733-2739)
  * without another pass over the output. */

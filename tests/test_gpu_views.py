@@ -146,10 +146,17 @@ def _bits(got, exp, what):
 class Ctx:
     """one case: the host slice, the device views and what reads an output back"""
 
-    def __init__(self, dtype, cname, mname, oname, base=V.BASE, masked=True, finite=False, pedestal=0.0):
+    def __init__(self, dtype, cname, mname, oname, base=V.BASE, masked=True, finite=False, pedestal=0.0, data=None, mask=None):
+        """*data*, *mask*: (tag, array of the base shape) in place of the samples / the include bytes of views.data; the tags
+        join the key of the reference cache (a mask's tag names its include set, whatever its byte values)"""
         self.dtype = dtype = np.dtype(dtype)
         self.lay = V.layout(cname, base)
         d, m = V.data(dtype.type, base, pedestal=pedestal)
+        self.given = {"data": data, "mask": mask}
+        if data is not None:
+            d = np.asarray(data[1], dtype)
+        if mask is not None:
+            m = np.asarray(mask[1], np.uint8)
         if finite:
             d = np.where(np.isnan(d), dtype.type(0.25), d)
         self.d, self.m = V.crop(d, self.lay), V.crop(m, self.lay)
@@ -161,7 +168,7 @@ class Ctx:
             self.marr, self._mparent = V.upload(self.mlay, self.m, 1)
             self.spec = ops.MaskSpec(_lib.MASK_ARRAY, array=self.marr)
         self.oname = oname
-        self.key = (dtype, self.lay.shape, masked, finite, pedestal)
+        self.key = (dtype, self.lay.shape, masked, finite, pedestal) + tuple(g[0] for g in (data, mask) if g is not None)
         self._outs = []
 
     def out(self, shape, dtype):
@@ -409,7 +416,9 @@ def _():
         k = _keys(x)
         for v, kk in zip(x[:8], k[:8]):                     # the key is the library's own (a host function)
             assert np.float32(ops.key_to_float(int(kk))) == v
-        return {"hist": E.exact(np.bincount(k >> 24, minlength=256).astype(np.uint64)), "next": E.exact(np.uint32(k[k > 0x80000000].min()))}
+        above = k[k > 0x80000000]
+        nxt = above.min() if above.size else 0xffffffff     # (ops.key_next: 0xffffffff when there is none)
+        return {"hist": E.exact(np.bincount(k >> 24, minlength=256).astype(np.uint64)), "next": E.exact(np.uint32(nxt))}
     return run, ref
 
 
@@ -648,6 +657,9 @@ for _a in (0, 1, 2):
     op("downsample_axis%d" % _a, out=True)(lambda _a=_a: _downsample(_a))
 
 
+_NO_BOX = ((-1, -1),) * 3           # ops.mask_bbox gives None when nothing is included
+
+
 def _subcube(step):
     def geometry(shape):
         start = (1, 2, 4 if step == 1 else 1)
@@ -661,7 +673,7 @@ def _subcube(step):
         out, omask = ops.subcube(c.cube, start, steps, shape, mask=c.spec, out=out, out_mask=omask, nan_excluded=True)
         res = {"out": c.read(out), "mask": c.read(omask)}
         box = ops.mask_bbox(c.cube, mask=c.spec, nan_excluded=True)
-        res["bbox"] = np.array(box, np.int64)
+        res["bbox"] = np.array(box if box is not None else _NO_BOX, np.int64)
         return res
 
     def ref(c):
@@ -670,7 +682,7 @@ def _subcube(step):
         sl = tuple(slice(s, s + n * step, step) for s, n in zip(start, shape))
         v = c.inc & ~np.isnan(c.d)
         w = np.argwhere(v)
-        box = np.array([(w[:, a].min(), w[:, a].max()) for a in range(3)], np.int64)
+        box = np.array([(w[:, a].min(), w[:, a].max()) for a in range(3)] if len(w) else _NO_BOX, np.int64)
         return {"out": E.exact(c.d[sl]), "mask": E.exact(v[sl].astype(np.uint8)), "bbox": E.exact(box)}
     return run, ref
 
@@ -714,7 +726,7 @@ def _():
         f = np.where(c.inc, c.d, np.nan)
         rows, ind, some = SS.restate(f, idx, shifts, (1, 2))
         assert not SS.near_half(ind, some).any(), "an indicator too close to one half for a reference to decide"
-        tol = SS.RTOL * SS.scale_of(f)
+        tol = SS.RTOL * (SS.scale_of(f) if np.isfinite(f).any() else 0.0)          # (a mask that includes nothing: every row NaN)
         ok = ~np.isnan(rows)
         return {"rows": E.within(rows.T, tol), "sum": E.within(np.where(ok, rows, 0.0).sum(axis=0), tol * idx.size),
                 "count": E.exact(ok.sum(axis=0).astype(np.int64)), "nan": E.exact((~ok).sum(axis=0).astype(np.int64))}
@@ -755,7 +767,7 @@ def _other(c, name, instead):
 @op("mosaic")
 def _():
     def run(c):
-        other = Ctx(c.dtype, _other(c, "xwin_oddstride", "xwin_off1"), "mask_contig", None)
+        other = Ctx(c.dtype, _other(c, "xwin_oddstride", "xwin_off1"), "mask_contig", None, **c.given)
         xs, ys = (_dev(a) for a in E.bilinear_maps(c.d.shape, 0.0))
         weights = DeviceArray(c.d.shape[1:], np.int32, 0)
         out = ops.mosaic([c.cube, other.cube], [(xs, ys)] * 2, [c.spec, other.spec], [FILL, FILL], 0, weights=weights)
