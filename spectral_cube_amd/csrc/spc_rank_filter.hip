@@ -4,7 +4,7 @@
 // (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029).
 //
 // Every sample is loaded once as a FILLED sample (mask predicate and fill fused into the load) and turned into an
-// order-preserving unsigned key: sign-flipped IEEE bits as in spc_select.hip, except that EVERY NaN (either sign, any
+// order-preserving unsigned key: sign-flipped IEEE bits as in spc_select_impl.h, except that EVERY NaN (either sign, any
 // payload) becomes the largest key.  Selection is done on keys, so "NaN ranks last" (numpy's sort order) costs nothing
 // and the result is np.sort(window)[rank] bit for bit (a NaN result is the canonical quiet NaN).
 //

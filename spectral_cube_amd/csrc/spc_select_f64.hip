@@ -626,27 +626,23 @@ static int sort64_launch(Sort64Args& A, const spc_cube_f64* cube, bool clip, hip
     A.nzp = nzp; A.ts = clip ? std::min(64, kSortKeys / nzp) : std::min(kSelRays64, kSelKeys64 / nzp);
     const int64_t nb = ((cube->nx + A.ts - 1) / A.ts) * cube->ny;
     SPC_REQUIRE(nb < (1LL << 31), "map too large for one launch");
-    if (clip && regs && cube->nz <= 1024 && !A.spread_mad) {      // (stdfunc = mad_std: a second descent over |x - median| - the sorted form below)
+    // the register forms (not the clip loop with stdfunc = mad_std: a second descent over |x - median| - the sorted form below):
+    // 16 rays per block, 16 lanes per ray with 8, 16 or 32 keys each, or - 513 .. 1024 samples - 32 lanes per ray with 32 keys each
+    if (regs && cube->nz <= 1024 && !(clip && A.spread_mad)) {
         const int64_t nbr = ((cube->nx + 15) / 16) * cube->ny;
         SPC_REQUIRE(nbr < (1LL << 31), "map too large for one launch");
         const int kpl = (int)((cube->nz + 15) / 16);
         dim3 grid((unsigned)nbr);
-        if (kpl <= 8) hipLaunchKernelGGL((sigma_clip64_reg_kernel<8, 16>), grid, dim3(256), 0, st, A);
-        else if (kpl <= 16) hipLaunchKernelGGL((sigma_clip64_reg_kernel<16, 16>), grid, dim3(256), 0, st, A);
-        else if (kpl <= 32) hipLaunchKernelGGL((sigma_clip64_reg_kernel<32, 16>), grid, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((sigma_clip64_reg_kernel<32, 32>), grid, dim3(512), 0, st, A);
-        SPC_LAUNCH_CHECK();
-        return SPC_OK;
-    }
-    if (!clip && regs && cube->nz <= 1024) {
-        const int64_t nbr = ((cube->nx + 15) / 16) * cube->ny;
-        SPC_REQUIRE(nbr < (1LL << 31), "map too large for one launch");
-        const int kpl = (int)((cube->nz + 15) / 16);
-        dim3 grid((unsigned)nbr);
-        if (kpl <= 8) hipLaunchKernelGGL((select64_reg_kernel<8, 16>), grid, dim3(256), 0, st, A);
-        else if (kpl <= 16) hipLaunchKernelGGL((select64_reg_kernel<16, 16>), grid, dim3(256), 0, st, A);
-        else if (kpl <= 32) hipLaunchKernelGGL((select64_reg_kernel<32, 16>), grid, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((select64_reg_kernel<32, 32>), grid, dim3(512), 0, st, A);      // 32 lanes per ray, 32 keys per lane
+        auto row = [&](auto kpl_c, auto lpr_c) {
+            constexpr int KPL = decltype(kpl_c)::value, LPR = decltype(lpr_c)::value;
+            if (clip) hipLaunchKernelGGL((sigma_clip64_reg_kernel<KPL, LPR>), grid, dim3(16 * LPR), 0, st, A);
+            else hipLaunchKernelGGL((select64_reg_kernel<KPL, LPR>), grid, dim3(16 * LPR), 0, st, A);
+        };
+        using std::integral_constant;
+        if (kpl <= 8) row(integral_constant<int, 8>{}, integral_constant<int, 16>{});
+        else if (kpl <= 16) row(integral_constant<int, 16>{}, integral_constant<int, 16>{});
+        else if (kpl <= 32) row(integral_constant<int, 32>{}, integral_constant<int, 16>{});
+        else row(integral_constant<int, 32>{}, integral_constant<int, 32>{});
         SPC_LAUNCH_CHECK();
         return SPC_OK;
     }

@@ -539,7 +539,7 @@ def _sigma(shape, dtype=np.float32):                                    # test_s
     return build
 
 
-# (nz in 513 .. 1024 and at least 256 rays: the wide block shape with the probe of 64 rays, spc_select.hip wide_ok / kProbeRays;
+# (nz in 513 .. 1024 and at least 256 rays: the wide block shape with the probe of 64 rays, spc_sigma_clip.hip wide_ok / kProbeRays;
 # see test_sigma_clip_block_shape_follows_the_mask)
 row("sigma clipping, fused with the probe (515, 8, 37)")(_sigma((515, 8, 37)))
 row("sigma clipping, the loop of kernels (60, 3, 70)", (("SPC_SIGMA_CLIP_FUSED", "0"),))(_sigma((60, 3, 70)))

@@ -334,6 +334,51 @@ def test_percentile_axis0_every_kernel(gpu, shape, monkeypatch):
         assert np.array_equal(mad, emad, equal_nan=True), env
 
 
+@pytest.mark.parametrize("nx", [7, 130, 260, 515, 1030, 2050, 4096, 4097])
+def test_percentile_axis2_every_table(gpu, nx, monkeypatch):
+    """np.nanmedian / np.nanpercentile along x through every row of the register-resident selection's 256-thread table as
+    spc_percentile_axis2_f32 walks it (32 / 16 / 8 rows per block and 16 - 128 keys per lane by row length, lengths that are
+    no multiple of the lanes per row, 37 rows hanging over a tile), with and without a uint8 mask, with 64-bit addresses (the
+    entry's default) and with descriptor loads.  Medians and MAD (centre per row) are bit-exact.  A row of 4097 samples does
+    not fit the registers of a block: HipUnsupported."""
+    import warnings
+    from spectral_cube_amd import ops, _lib
+    from spectral_cube_amd.device import DeviceArray
+    shape = (2, 37, nx)
+    rng = np.random.default_rng(nx)
+    d = rng.standard_normal(shape).astype(np.float32)
+    d[rng.random(shape) < 0.05] = np.nan
+    d[0, 0, :] = np.nan                                             # an empty ray
+    d[0, 1, : nx // 2] = 2.5                                        # ties
+    inc = rng.random(shape) < 0.8
+    dd = DeviceArray.from_numpy(d)
+    spec = ops.MaskSpec(_lib.MASK_FINITE | _lib.MASK_ARRAY, array=DeviceArray.from_numpy(inc.astype(np.uint8)))
+    if nx > 4096:
+        with pytest.raises(_lib.HipUnsupported):
+            ops.percentile_axis2(dd, 50.0, mask=spec)
+        return
+    expected = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for masked, fz in ((True, np.where(inc, d, np.nan).astype(np.float32)), (False, d)):
+            emed = np.nanmedian(fz, axis=2)
+            expected[masked] = (emed, np.nanpercentile(fz.astype(np.float64), 30.0, axis=2),
+                                np.nanmedian(np.abs(fz - emed[:, :, None]), axis=2))
+    for env in ({}, {"SPC_SELECT_DESC": "1"}):
+        monkeypatch.delenv("SPC_SELECT_DESC", raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for masked, (emed, e30, emad) in expected.items():
+            mask = spec if masked else None
+            med = ops.percentile_axis2(dd, 50.0, mask=mask)
+            assert np.array_equal(med.get(), emed, equal_nan=True), (env, masked)
+            got30 = ops.percentile_axis2(dd, 30.0, mask=mask).get()
+            assert np.array_equal(np.isnan(got30), np.isnan(e30)), (env, masked)
+            np.testing.assert_allclose(got30, e30, rtol=3e-6, atol=1e-7, equal_nan=True)
+            mad = ops.percentile_axis2(dd, 50.0, mask=mask, center=med).get()
+            assert np.array_equal(mad, emad, equal_nan=True), (env, masked)
+
+
 def test_order_statistics_mask_predicates_as_key_intervals(gpu):
     """The register-resident selection and the clip kernel test a sample's validity with ONE unsigned range test on its
     order-preserving key (sel_key_range: NaN, isfinite and every threshold comparison select a key interval).  Every

@@ -49,10 +49,10 @@ TABLE = [
     ("stats_dev_axis", "spc_stats_dev_axis_f32 / _f64", "spc_stats_m2.hip:111-140 (no 16-byte form)", "summing",
      "the whole cube's std from s1, s2 at far_from_zero.RTOL: test_gpu_far_from_zero.py:48"),
     ("percentile_axis0", "spc_percentile_axis0_f32 (register, radix-16, bisection) / _f64 (register form; its LDS form, a "
-     "once-per-process switch, in a fresh process)", "spc_select.hip:1291 (v4); takes swap01 (spc_check_cube_any_order)", "exact",
-     "median and MAD equal np.nanmedian: test_gpu_round2.py:331-337"),
-    ("sigma_clip_axis0", "spc_sigma_clip_axis0_f32 (fused: packed rays, rays in registers) / the loop of kernels (SPC_SIGMA_CLIP_FUSED=0) / _f64", "spc_select.hip:1291",
-     "exact against contig", "kept values equal the oracle's, NaN pattern differs on < 2e-4 of the samples: test_gpu_round2.py:484-486"),
+     "once-per-process switch, in a fresh process)", "spc_select.hip:377 (v4); takes swap01 (spc_check_cube_any_order)", "exact",
+     "median and MAD equal np.nanmedian: test_gpu_round2.py:327-334"),
+    ("sigma_clip_axis0", "spc_sigma_clip_axis0_f32 (fused: packed rays, rays in registers) / the loop of kernels (SPC_SIGMA_CLIP_FUSED=0) / _f64", "spc_sigma_clip.hip:68 (no 16-byte form; takes swap01)",
+     "exact against contig", "kept values equal the oracle's, NaN pattern differs on < 2e-4 of the samples: test_gpu_round2.py:529-531"),
     ("moments_spatial", "spc_moments_spatial_f32 + spc_moment_order_spatial_f32, axes 1 2",
      "spc_moments_spatial.hip:152 (per row), :184 (v4)", "summing", "rtol 1e-9, atol 1e-7 max: test_gpu_ops.py:142"),
     ("argextrema_axis", "spc_argextrema_axis_f32, axes 1 2", "spc_stats.hip:906-907 (v4, axis 1; axis 2 per row)", "exact", "-"),
@@ -60,10 +60,10 @@ TABLE = [
      "sum, sumsq rtol 1e-12: test_gpu_ops.py:746-747"),
     ("stats_global", "spc_stats_global_f32 / _f64", "spc_stats.hip:120-129 (one run / rows of a view); spc_stats_f64.hip:161 (vec2: spc_pairs_ok_f64)",
      "summing", "npts, min, max exact; sum, sumsq rtol 1e-12: test_gpu_ops.py:441-465"),
-    ("percentile_axis2", "spc_percentile_axis2_f32", "spc_select.hip:1485-1509 (no 16-byte form: lanes take consecutive samples of a row; takes "
+    ("percentile_axis2", "spc_percentile_axis2_f32", "spc_select.hip:419-440 (no 16-byte form: lanes take consecutive samples of a row; takes "
      "swap01)", "exact", "-"),
-    ("percentile_global", "spc_percentile_global_f32", "spc_select.hip:1235-1243 (one run / rows of a view)", "exact", "-"),
-    ("key_histogram", "spc_key_histogram_f32 (+ key_next)", "spc_select.hip:1235-1243", "exact", "-"),
+    ("percentile_global", "spc_percentile_global_f32", "spc_select_global.hip:86-92 (gsel_geometry: one run / rows of a view)", "exact", "-"),
+    ("key_histogram", "spc_key_histogram_f32 (+ key_next)", "spc_select_global.hip:86-92", "exact", "-"),
     ("spectral_conv", "spc_spectral_conv_f32 (9, 17, 33, 49, 65 taps; masked, all valid) / _f64",
      "spc_spectral_conv.hip:377-380 (two spaxels per lane: cube, mask and output)", "summing", "1e-5 max: test_gpu_ops.py:169"),
     ("spectral_conv_moments", "spc_spectral_conv_moments_f32", "spc_spectral_conv.hip:329-331 (algebraic form: the "
@@ -89,7 +89,7 @@ TABLE = [
      "the identity map at order 0 exact"),
     ("resample_spline", "spc_resample_spline_f32", "spc_resample.hip:993-1019 (no 16-byte form)", "summing", "1e-5 of the data range: test_gpu_round4.py:151"),
     ("fill_masked", "spc_fill_masked_f32, spc_fill_masked_transpose_f32, spc_mask_include_u8 / _f64, spc_narrow_f64_to_f32",
-     "spc_select.hip / spc_convert_f64.hip:18 (scalar)", "exact", "-"),
+     "spc_stats.hip:1024 / spc_convert_f64.hip:18 (scalar)", "exact", "-"),
     ("downsample", "spc_downsample_f32 / _f64, axes 0 1 2", "spc_downsample.hip:347-350 (ds_vec_ok: cube, mask, output)", "summing",
      "float32 within 1 ulp of the float64 restatement: test_gpu_downsample.py:45; float64 rtol 1e-14, atol 1e-15 max: :194"),
     ("subcube", "spc_subcube_f32 / _f64 (step 1, step 2), spc_mask_bbox_f32 / _f64", "spc_subcube.hip:258, :294", "exact", "-"),
@@ -346,7 +346,7 @@ def _sigma_clip():
     return run, ref
 
 
-op("sigma_clip_axis0", any_order=(F32,))(_sigma_clip)           # (spc_select.hip:1539; the float64 entry and the loop refuse)
+op("sigma_clip_axis0", any_order=(F32,))(_sigma_clip)           # (spc_sigma_clip.hip:68; the float64 entry and the loop refuse)
 op("sigma_clip_axis0[loop]", (F32,), env=(("SPC_SIGMA_CLIP_FUSED", "0"),))(_sigma_clip)
 # (rays of at most 128 valid samples are packed into LDS by default - every ray of these cubes; SPC_SELECT_COMPACT=0 keeps them
 # in registers)
@@ -389,7 +389,7 @@ def _():
             (lambda c: E.ref_stats_global(c.d, c.inc)))
 
 
-@op("percentile_axis2", (F32,), any_order=(F32,))                # (spc_select.hip:1485)
+@op("percentile_axis2", (F32,), any_order=(F32,))                # (spc_select.hip:419)
 def _():
     return ((lambda c: {"median": ops.percentile_axis2(c.cube, 50.0, mask=c.spec).get()}),
             (lambda c: {"median": E.exact(np.nanmedian(np.where(c.inc, c.d, np.nan).astype(np.float32), axis=2))}))

@@ -1,5 +1,5 @@
-"""sigma_clip_spectrally at 1024^3 + uint8 mask (80 % valid, random) by iteration count, with and without the sorted neighbourhood of
-the first median (SPC_CLIP_NEAR, read per call): where the clip kernel's time goes"""
+"""sigma_clip_spectrally at 1024^3 + uint8 mask (80 % valid, random) by iteration count and centre function: where the clip
+kernel's time goes"""
 import sys, os
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
@@ -20,12 +20,10 @@ def timeit(fn, n=3):
     return float(np.median(ts))
 keep = {}
 for cen in ("median", "mean"):
-    for near in ("1", "0"):
-        os.environ["SPC_CLIP_NEAR"] = near
-        row = []
-        for it in (1, 2, 3, 5, None):
-            def run():
-                keep["r"] = None
-                keep["r"] = ops.sigma_clip_axis0(cube, sigma=3.0, maxiters=it, cenfunc=cen, mask=ms)
-            row.append("%s: %.2f" % (it, timeit(run)))
-        print("cenfunc=%s SPC_CLIP_NEAR=%s  maxiters " % (cen, near) + "  ".join(row) + "  ms", flush=True)
+    row = []
+    for it in (1, 2, 3, 5, None):
+        def run():
+            keep["r"] = None
+            keep["r"] = ops.sigma_clip_axis0(cube, sigma=3.0, maxiters=it, cenfunc=cen, mask=ms)
+        row.append("%s: %.2f" % (it, timeit(run)))
+    print("cenfunc=%s  maxiters " % cen + "  ".join(row) + "  ms", flush=True)
