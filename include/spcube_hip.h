@@ -231,6 +231,30 @@ int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube,
                     double m1_add, const spc_moment_outputs* out,
                     void* d_workspace, size_t workspace_bytes);
 
+/* The uint8 array term of a mask as BITS, for a mask that many launches reuse: an eighth of its bytes per launch.
+ * Layout (it follows the moment kernel's lane mapping and nothing of its launch plan): lane group
+ * g = y * (nx / 4) + x / 4 over the array as the call sees it (the rows and planes of a view included), block b = g / 64,
+ * lane l = g % 64.  The bits of plane z of block b are the 32 bytes at (b * nz + z) * 32; lane l owns the nibble
+ * (l & 1) * 4 of byte l >> 1, and bit i of that nibble is "mask byte of voxel x + i != 0".  Lanes past the last group
+ * have zero bits.  spc_mask_bits_bytes: ceil(ny * (nx / 4) / 64) * nz * 32, or 0 where the form does not exist
+ * (nx % 4 != 0, an empty shape).
+ * spc_mask_pack_bits: one streaming kernel on the caller's stream writes every byte of d_bits from mask->d_array
+ * (only the array term is packed; thresholds stay in the predicate; row_stride / plane_stride 0 = contiguous).
+ * SPC_ERR_UNSUPPORTED where the lanes cannot read dwords: the mask's strides or address are no multiple of 4.
+ * spc_moments_bits_f32 is spc_moments_f32 with the packed form of ITS mask array (d_mask_bits NULL: exactly
+ * spc_moments_f32).  The bits are read only where the launch is the mask-first march of 16-byte lanes and bits_bytes
+ * is large enough; odd widths, unaligned views, SPC_MOMENTS_MASK_FIRST=0 and SPC_MOMENTS_MASK_BITS=0 read the bytes as
+ * before.  The maps are bit-identical either way.  The caller answers for the bits being those of the array: pack
+ * again after the array's bytes change.  (Added within ABI 8: nothing existing moved.) */
+size_t spc_mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx);
+int spc_mask_pack_bits(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask* mask,
+                       void* d_bits, size_t bits_bytes);
+int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube,
+                         const spc_mask* mask, const double* d_cen, double dv,
+                         double m1_add, const spc_moment_outputs* out,
+                         void* d_workspace, size_t workspace_bytes,
+                         const void* d_mask_bits, size_t bits_bytes);
+
 /* general order N >= 2 second pass:  out = sum v*(c - mu)^N / S0
  * (dask_spectral_cube.py:1094-1099; _moments.py:185-193).  d_mu, d_s0 come
  * from spc_moments_f32. */

@@ -216,6 +216,10 @@ SIGNATURES = {
     "spc_workspace_bytes": (_sz, [_i, _i64, _i64, _i64, _i64, _i64]),
     "spc_moments_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
                              _P(SpcMomentOutputs), _vp, _sz]),
+    "spc_mask_bits_bytes": (_sz, [_i64, _i64, _i64]),
+    "spc_mask_pack_bits": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMask), _vp, _sz]),
+    "spc_moments_bits_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
+                                  _P(SpcMomentOutputs), _vp, _sz, _vp, _sz]),
     "spc_moment_order_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _i, _vp, _vp, _vp, _i64]),
     # (spc_cube_f64 has the layout of spc_cube_f32: a pointer and five int64)
     "spc_moments_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _vp, _d, _d, _P(SpcMomentOutputs64)]),

@@ -168,9 +168,15 @@ __device__ __forceinline__ unsigned vget(const unsigned char& v, int) { return v
 // other lanes hold 0.f, which acc_add would have selected anyway (ok is false there whatever the sample is).  A 128-byte
 // line of the cube in which the mask includes nothing is then never requested.  Everything after the loads is the same
 // code in the same order, so the maps are bit-identical for every input, NaN and Inf under excluded voxels included.
-template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false>
+//
+// BITS (MF only): the mask of a plane is the lane's nibble of the packed form (layout: include/spcube_hip.h, spc_mask_pack_bits)
+// instead of its four mask bytes: one unsigned-byte load from bits + (blk * nz + z) * 32 + (lane >> 1), an eighth of the mask's
+// bytes.  "Nothing included" is nibble == 0 and voxel i is bit i; the batch of masks one ahead, the wait for all of them, the
+// carried pointers, the tail, acc_add and the combine are the same statements, so the maps are those of the byte form bit for bit.
+template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false, bool BITS = false>
 __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     static_assert(!MF || (ARR && VEC == 4), "mask-first is the 16-byte lane form with a mask array");
+    static_assert(!BITS || MF, "the packed mask is read by the mask-first forms only");
     using F = typename VecT<VEC>::F;
     using M = typename VecT<VEC>::M;
     const int lane = threadIdx.x;
@@ -216,13 +222,14 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
                 for (int i = 0; i < VEC; ++i) {
                     const float val = vget(v, i);
                     bool ok = mom_pred<PRED>(val, lim, lo, hi);
-                    if (ARR) ok = ok && (vget(m, i) != 0);
+                    if constexpr (BITS) ok = ok && ((m >> i) & 1u) != 0;
+                    else if (ARR) ok = ok && (vget(m, i) != 0);
                     acc_add<EXT>(acc[i], val, ok, c, c2, (int)zz);
                 }
             };
             // two carried pointers, made opaque once per batch, and every address of a batch the one before plus the uniform
             // plane step (left to itself the loop optimiser keeps 2 U pointers in registers: 124 VGPRs instead of 80)
-            const int64_t dstep = (int64_t)ZW * A.plane_stride, mstep = (int64_t)ZW * A.mask.plane_stride;
+            const int64_t dstep = (int64_t)ZW * A.plane_stride, mstep = BITS ? (int64_t)ZW * 32 : (int64_t)ZW * A.mask.plane_stride;
             // (pointers to global memory by type: one that went through the asm statement as a plain pointer is loaded from with
             //  flat_load, which also counts in lgkmcnt, where the scalar loads of the coordinates wait)
             typedef const float __attribute__((address_space(1))) gfloat;
@@ -230,12 +237,24 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
             typedef const F __attribute__((address_space(1))) GF;
             typedef const M __attribute__((address_space(1))) GM;
             gfloat* pz = (gfloat*)(p + z * A.plane_stride);      // the samples of plane z ...
-            gbyte* qz = (gbyte*)(pm + z * A.mask.plane_stride);  // ... and the first mask that has not been asked for yet
+            // (BITS: A.mask.arr is the packed form - launch_main - and this the byte that holds the lane's nibble)
+            gbyte* qz = BITS ? (gbyte*)(A.mask.arr + (blk * A.nz + z) * 32 + (lane >> 1))
+                             : (gbyte*)(pm + z * A.mask.plane_stride);  // ... and the first mask that has not been asked for yet
+            // the odd lanes own the high nibble of their byte.  The shift runs under the lane mask (scalar registers) and in place:
+            // a shift amount kept in a vector register, or a nibble written beside its byte, costs <4, 8, 8, sums> a wave per SIMD
+            const bool odd = (lane & 1) != 0;
+            // the mask of the plane at q.  BITS: the byte as it comes (a plain load: the waves of a block share its line); it becomes
+            // the lane's four bits once the whole batch has been waited for
+            auto load_mask = [&](gbyte* q) -> M {
+                if constexpr (BITS) return (M)*q;
+                else return __builtin_nontemporal_load((GM*)q);
+            };
+
             bool more = z + (int64_t)(U - 1) * ZW < ze;
             M m[U];                                              // the masks of the batch that starts at z
             if (more) {
 #pragma unroll
-                for (int u = 0; u < U; ++u, qz += mstep) m[u] = __builtin_nontemporal_load((GM*)qz);
+                for (int u = 0; u < U; ++u, qz += mstep) m[u] = load_mask(qz);
             }
             while (more) {
                 // every mask of the batch is waited for here, before the first load it decides: the loads of the samples then
@@ -244,6 +263,14 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
 #pragma unroll
                 for (int u = 1; u < U; ++u) all |= m[u];
                 asm volatile("" : "+v"(pz), "+v"(qz) : "v"(all));
+                if constexpr (BITS) {
+                    if (odd) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) asm volatile("v_lshrrev_b32 %0, 4, %0" : "+v"(m[u]));
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) asm volatile("v_and_b32 %0, 15, %0" : "+v"(m[u]));
+                }
                 F v[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u, pz += dstep) {
@@ -255,14 +282,16 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     add_plane(v[u], m[u], z + (int64_t)u * ZW);
-                    if (more) { m[u] = __builtin_nontemporal_load((GM*)qz); qz += mstep; }
+                    if (more) { m[u] = load_mask(qz); qz += mstep; }
                 }
                 z += (int64_t)U * ZW;
             }
             // tail
             for (; z < ze; z += ZW, pz += dstep, qz += mstep) {
                 F v{};
-                const M mt = *(GM*)qz;
+                M mt;
+                if constexpr (BITS) mt = ((M)*qz >> (odd ? 4 : 0)) & 0xfu;
+                else mt = *(GM*)qz;
                 if (mt != 0) v = *(GF*)pz;
                 add_plane(v, mt, z);
             }
@@ -479,13 +508,23 @@ __global__ __launch_bounds__(256) void moment_order_v4_kernel(const OrdArgs A) {
     }
 }
 
-struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; };
+struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; };   // bits: the packed mask array, or nullptr
 
 template <int VEC, int ZW, int U, bool ARR, int EXT>
-int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first) {
+int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits) {
     dim3 block(kLanes, ZW);
     dim3 grid((unsigned)((A.ngroups + kLanes - 1) / kLanes), (unsigned)A.nsplit);
     if constexpr (ARR && VEC == 4) {
+        if (mask_first && bits) {
+            // the BITS forms never read the byte array: its pointer carries the packed form, so that the arguments keep the
+            // layout (and every other instantiation the instructions) they had
+            MomArgs B = A;
+            B.mask.arr = bits;
+            if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true, true>), grid, block, 0, st, B);
+            else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true, true>), grid, block, 0, st, B);
+            SPC_LAUNCH_CHECK();
+            return SPC_OK;
+        }
         if (mask_first) {
             if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true>), grid, block, 0, st, A);
             else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true>), grid, block, 0, st, A);
@@ -507,27 +546,32 @@ int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_fir
 // and are not what make_plan picks: U = 8 with extrema (all eight 16-byte loads stay live across the branches: 131 - 134 VGPRs;
 // make_plan takes U = 2 with extrema) and <4,1,8,count,0> (81 VGPRs; ZW = 1 is for cubes of fewer than 16 planes).  They are
 // reached through SPC_MOMENTS_U / SPC_MOMENTS_ZW only.
+// The BITS forms beside them (profiles/moments_mask_bits_resources.txt): <4,4,8,sums,0> 77 VGPRs, <4,8,8,sums,0> 79, six waves
+// each; they rest on the nibble being shifted and masked IN PLACE (the asm statements in the kernel): with a shift amount in
+// a vector register <4,8,8,sums> held 82 and five waves and a nearly empty mask ran 8 % slower than on its bytes.
+// <4,4,8,count,0> holds 81 against the byte form's 80: five waves against six (and still gains what the sums form gains).
 template <bool ARR, int EXT>
 int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     if (p.vec == 4) {
         switch (p.zw * 16 + p.u) {
-            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first);
-            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
-            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first);
-            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first);
-            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first);
-            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first);
-            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first);
-            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first);
-            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first);
+            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
         }
     }
-    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
-    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first);
+    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
 }
 
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     Plan p;
+    p.bits = nullptr;
     auto aligned = [&](int v) {
         const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
         return (c->nx % v == 0) && (c->row_stride % v == 0) && (c->plane_stride % v == 0) &&
@@ -563,9 +607,100 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     return p;
 }
 
+// ---- the mask array as bits (layout: include/spcube_hip.h) ---------------------------------------------------
+// Lane group g = y * (nx / 4) + x / 4 as in moments_kernel<4, ...>; block b = g / 64, lane l = g % 64; the 32 bytes of plane z
+// of block b at (b * nz + z) * 32, lane l in nibble (l & 1) of byte l >> 1.  Nothing of a launch plan enters.
+struct PackArgs {
+    const uint8_t* arr;
+    int64_t nz, row_stride, plane_stride;
+    int64_t groups_per_row, ngroups;
+    uint8_t* bits;
+};
+
+constexpr int kPackPlanes = 8;   // planes per wave and step: 8 x 32 = 256 contiguous bytes of bits, one dword per lane
+
+// One wave = one block of 64 lane groups, eight planes per step.  A lane reads its mask dword of each plane and makes the
+// nibble; the eight lanes that share a dword of the bits (lanes 8 j .. 8 j + 7 -> bytes 4 j .. 4 j + 3) OR their shifted nibbles
+// together by three neighbour exchanges, after which each of them holds the dword of every plane; lane 8 j + p stores plane p's.
+// A wave's store covers the 256 bytes of its eight planes.  Dead lanes (g >= ngroups) contribute zero bits; planes past nz
+// are neither read nor stored.
+__global__ __launch_bounds__(256) void mask_pack_bits_kernel(const PackArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t blk = blockIdx.x;
+    const int64_t g = blk * kLanes + lane;
+    const bool live = g < A.ngroups;
+    const int64_t gg = live ? g : 0;
+    const int64_t y = gg / A.groups_per_row;
+    const int64_t x = (gg - y * A.groups_per_row) * 4;
+    const uint8_t* pm = A.arr + y * A.row_stride + x;
+    const int64_t nsteps = (A.nz + kPackPlanes - 1) / kPackPlanes;
+    const int p_mine = lane & 7;
+    for (int64_t s = (int64_t)blockIdx.y * 4 + w; s < nsteps; s += (int64_t)gridDim.y * 4) {
+        const int64_t z0 = s * kPackPlanes;
+        uint32_t m[kPackPlanes];
+#pragma unroll
+        for (int p = 0; p < kPackPlanes; ++p) {
+            m[p] = 0;
+            if (live && z0 + p < A.nz)                               // z0 + p < nz: wave-uniform
+                m[p] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(pm + (z0 + p) * A.plane_stride));
+        }
+        uint32_t mine = 0;
+#pragma unroll
+        for (int p = 0; p < kPackPlanes; ++p) {
+            uint32_t n = ((m[p] & 0xffu) != 0 ? 1u : 0u) | ((m[p] & 0xff00u) != 0 ? 2u : 0u) |
+                         ((m[p] & 0xff0000u) != 0 ? 4u : 0u) | ((m[p] & 0xff000000u) != 0 ? 8u : 0u);
+            n <<= 4 * (lane & 7);
+            n |= __shfl_xor(n, 1);
+            n |= __shfl_xor(n, 2);
+            n |= __shfl_xor(n, 4);
+            if (p == p_mine) mine = n;
+        }
+        if (z0 + p_mine < A.nz)
+            *reinterpret_cast<uint32_t*>(A.bits + (blk * A.nz + z0 + p_mine) * 32 + (lane >> 3) * 4) = mine;
+    }
+}
+
+size_t mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx) {
+    if (nz <= 0 || ny <= 0 || nx <= 0 || nx % 4 != 0) return 0;
+    const int64_t ngroups = ny * (nx / 4);
+    return (size_t)((ngroups + kLanes - 1) / kLanes) * (size_t)nz * 32;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t spc_mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx) { return mask_bits_bytes(nz, ny, nx); }
+
+int spc_mask_pack_bits(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask* mask,
+                       void* d_bits, size_t bits_bytes) {
+    SPC_REQUIRE(nz > 0 && ny > 0 && nx > 0, "mask shape must be positive (got %lld,%lld,%lld)", (long long)nz, (long long)ny, (long long)nx);
+    SPC_REQUIRE(mask != nullptr && (mask->flags & SPC_MASK_ARRAY) && mask->d_array != nullptr, "no mask array to pack");
+    SPC_REQUIRE(d_bits != nullptr, "d_bits is NULL");
+    const size_t need = mask_bits_bytes(nz, ny, nx);
+    const int64_t rs = mask->row_stride ? mask->row_stride : nx, ps = mask->plane_stride ? mask->plane_stride : ny * nx;
+    SPC_REQUIRE(rs >= nx && ps >= rs * (ny - 1) + nx, "mask strides smaller than the shape");
+    // the lanes read dwords: the conditions of make_plan's aligned(4) for the mask
+    if (need == 0 || rs % 4 != 0 || ps % 4 != 0 || !spc_aligned(mask->d_array, 4) || !spc_aligned(d_bits, 4)) {
+        spc_set_error("spc_mask_pack_bits: nx, the mask's strides and its address must be multiples of 4");
+        return SPC_ERR_UNSUPPORTED;
+    }
+    SPC_REQUIRE(bits_bytes >= need, "d_bits too small: %zu bytes given, %zu needed (spc_mask_bits_bytes)", bits_bytes, need);
+    SPC_DEVICE(device);
+    PackArgs A{};
+    A.arr = mask->d_array; A.nz = nz; A.row_stride = rs; A.plane_stride = ps;
+    A.groups_per_row = nx / 4; A.ngroups = ny * A.groups_per_row;
+    A.bits = (uint8_t*)d_bits;
+    const int64_t nblocks = (A.ngroups + kLanes - 1) / kLanes;
+    SPC_REQUIRE(nblocks < (1LL << 31), "mask too large");
+    // enough blocks to fill the chip when the map alone is small; four waves of a block take interleaved steps
+    const int64_t nsteps = (nz + kPackPlanes - 1) / kPackPlanes;
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nsteps + 3) / 4, (4096 + nblocks - 1) / nblocks), 65535));
+    hipLaunchKernelGGL(mask_pack_bits_kernel, dim3((unsigned)nblocks, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, A);
+    SPC_LAUNCH_CHECK();
+    return SPC_OK;
+}
 
 size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
     if (nz <= 0 || ny <= 0 || nx <= 0) return 0;
@@ -582,6 +717,12 @@ size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
 int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                     const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                     void* d_workspace, size_t workspace_bytes) {
+    return spc_moments_bits_f32(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, nullptr, 0);
+}
+
+int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                         const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
+                         void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes) {
     int rc = spc_check_cube(cube);
     if (rc) return rc;
     SPC_REQUIRE(out != nullptr, "outputs struct is NULL");
@@ -615,6 +756,12 @@ int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const sp
         }
     }
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    // the packed mask only where the launch is the mask-first march of 16-byte lanes; everything else reads the bytes as before
+    p.bits = nullptr;
+    if (d_mask_bits && arr && p.vec == 4 && p.mask_first && spc_switch("SPC_MOMENTS_MASK_BITS", 1) != 0) {
+        const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
+        if (need && bits_bytes >= need) p.bits = (const uint8_t*)d_mask_bits;
+    }
     hipStream_t st = (hipStream_t)stream;
     const int what = ext ? kExtrema : (out->d_nvalid ? kCount : kSums);
     if (arr) rc = what == kExtrema ? launch_plan<true, kExtrema>(A, st, p, thr)

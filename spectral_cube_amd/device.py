@@ -171,6 +171,25 @@ class DeviceArray:
         else:
             self.ptr = int(ptr)
 
+    # ---- write generation ---------------------------------------------------
+    # A form derived from an array's bytes (the packed mask bits of ops.MaskSpec) is valid for one generation of the
+    # buffer.  The counter lives on the root of the owner chain, so a write through a view is seen by every other view.
+    def _root(self):
+        a = self
+        while isinstance(a._owner, DeviceArray):
+            a = a._owner
+        return a
+
+    @property
+    def write_generation(self):
+        return getattr(self._root(), "_wgen", 0)
+
+    def mark_written(self):
+        """say that the buffer's bytes have changed (or are about to, on a stream): upload() and the package's operators
+        that write into a caller-given array call it; a caller that writes through the raw pointer does so itself"""
+        r = self._root()
+        r._wgen = getattr(r, "_wgen", 0) + 1
+
     # ---- construction / transfer ------------------------------------------
     @classmethod
     def from_numpy(cls, arr, device=0, stream=None, dtype=None):
@@ -189,6 +208,7 @@ class DeviceArray:
         a = np.ascontiguousarray(arr, dtype=self.dtype)
         if a.nbytes != self.nbytes:
             raise ValueError("upload size mismatch: %d vs %d bytes" % (a.nbytes, self.nbytes))
+        self.mark_written()
         _lib.call("spc_memcpy_h2d", self.device, C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p),
                   self.nbytes, _sh(stream))
         if stream is not None:

@@ -7,7 +7,7 @@ reference tree).  There is no CPU fallback here.
 import ctypes as C
 import os
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
@@ -19,11 +19,36 @@ from .device import DeviceArray, _sh
 @dataclass
 class MaskSpec:
     """Device-evaluable mask (AND of the enabled terms); see SPC_MASK_* in
-    include/spcube_hip.h and spectral_cube/masks.py:105-116, 425-435."""
+    include/spcube_hip.h and spectral_cube/masks.py:105-116, 425-435.
+
+    A spec that is used again is taken to describe the same mask: from its second use on, moments() reads the array term
+    as bits (spc_mask_pack_bits: an eighth of the bytes per launch), packed once and kept with the spec.  The bits are
+    keyed by the array's address, shape, strides and WRITE GENERATION (DeviceArray.mark_written: upload() and every
+    operator of this package that writes into a caller-given array advance it), so a mask rewritten that way is packed
+    again after two more uses.  Bytes changed behind the library's back - through the raw pointer, by a kernel of the
+    caller's - after a spec has been used twice need invalidate().  rows(), planes() and swap01() return specs of their
+    own, which pack for themselves on their second use."""
     flags: int = 0
     thr_lo: float = 0.0
     thr_hi: float = 0.0
     array: Optional[DeviceArray] = None      # uint8, same shape as the cube
+    # the packed form of the array term (moments()): not part of what the spec says, so neither compared nor printed
+    _bits: Optional[DeviceArray] = field(default=None, init=False, compare=False, repr=False)
+    _bits_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)
+    _bits_uses: int = field(default=0, init=False, compare=False, repr=False)
+    _bits_failed: bool = field(default=False, init=False, compare=False, repr=False)   # no form / no memory: stay with the bytes
+
+    def invalidate(self):
+        """forget the packed form of the array term and start counting uses again: after the array's bytes were changed by
+        something other than upload() or an operator of this package"""
+        with _bits_lock:
+            self._drop_bits()
+
+    def _drop_bits(self):
+        self._bits = None                    # (the buffer goes back through spc_free, which waits for the launches that read it)
+        self._bits_key = None
+        self._bits_uses = 0
+        self._bits_failed = False
 
     def to_c(self, wide=False):
         """spc_mask_f32, or (*wide*) spc_mask_f64: the thresholds as they are (a float64 cube is compared in float64)"""
@@ -57,6 +82,67 @@ class MaskSpec:
 
 
 _F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
+
+_bits_lock = threading.Lock()        # dask `threads` workers share a spec: one of them packs
+
+
+def _switch_on(name, dflt=1):
+    """a library switch as spc_switch reads it: atoi of the value when set ("" and text that is no number: 0)"""
+    e = os.environ.get(name)
+    if e is None:
+        return dflt != 0
+    e = e.strip()
+    n = 0
+    while n < len(e) and (e[n].isdigit() or (n == 0 and e[n] in "+-")):
+        n += 1
+    try:
+        return int(e[:n]) != 0
+    except ValueError:
+        return False
+
+
+def _written(a):
+    """the operator has queued a write into *a*, a 1-byte array the caller may have given (or None): a MaskSpec that has
+    packed its bytes packs them again (DeviceArray.mark_written; arrays that are no DeviceArray keep no count)"""
+    mark = getattr(a, "mark_written", None)
+    if mark is not None:
+        mark()
+
+
+def _mask_bits(mask, stream):
+    """the packed form of *mask*'s array term, or None: nothing on a spec's first use (a mask used once costs what it always
+    did), packed on *stream* on the second - the stream is waited for once, so that later launches on any stream may read
+    the bits - and handed out from then on, until the array's key or write generation changes"""
+    if mask is None or mask.array is None or not (mask.flags & _lib.MASK_ARRAY) or len(mask.array.shape) != 3:
+        return None
+    if not _switch_on("SPC_MOMENTS_MASK_BITS"):
+        return None
+    a = mask.array
+    nz, ny, nx = a.shape
+    key = (a.ptr, a.shape, getattr(a, "row_stride", nx), getattr(a, "plane_stride", ny * nx), a.write_generation)
+    with _bits_lock:
+        if mask._bits_key != key:
+            mask._drop_bits()
+            mask._bits_key = key
+        if mask._bits is not None or mask._bits_failed:
+            return mask._bits
+        mask._bits_uses += 1
+        if mask._bits_uses < 2:
+            return None
+        need = int(_lib.load().spc_mask_bits_bytes(nz, ny, nx))
+        if not need:
+            mask._bits_failed = True
+            return None
+        try:
+            bits = DeviceArray((need,), np.uint8, a.device)
+            m = mask.to_c()
+            _lib.call("spc_mask_pack_bits", a.device, _sh(stream), nz, ny, nx, C.byref(m), C.c_void_p(bits.ptr), need)
+            _lib.call("spc_stream_sync", a.device, _sh(stream))
+        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
+            mask._bits_failed = True         # never an error: the byte path goes on
+            return None
+        mask._bits = bits
+        return bits
 
 
 def _cube_c(cube, dtype=None):
@@ -178,9 +264,15 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
     if need and (ws is None or ws.nbytes < need):
         ws = DeviceArray((need,), np.uint8, cube.device)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
-    _lib.call("spc_moments_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
-              float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
-              ws.nbytes if ws is not None else 0)
+    bits = _mask_bits(mask, stream) if cube.dtype == _F32 else None
+    if bits is not None:       # (whether the launch can read them is the library's decision)
+        _lib.call("spc_moments_bits_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
+                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
+                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes)
+    else:
+        _lib.call("spc_moments_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
+                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
+                  ws.nbytes if ws is not None else 0)
     bufs["_workspace"] = ws
     return bufs
 
@@ -381,6 +473,7 @@ def downsample(cube, axis, factor, truncate=False, estimator=_lib.DS_NANMEAN, fi
     ors, ops_ = _strides(out)
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
               int(axis), int(factor), 1 if truncate else 0, int(estimator), C.c_void_p(out.ptr), ors, ops_, C.c_void_p(out_mask.ptr))
+    _written(out_mask)
     return out, out_mask
 
 
@@ -596,6 +689,7 @@ def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_m
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, st3, sp3,
               shape[0], shape[1], shape[2], C.c_void_p(out.ptr), ors, ops_,
               C.c_void_p(out_mask.ptr) if out_mask is not None else None, 1 if filled else 0, float(fill))
+    _written(out_mask)
     return out, out_mask
 
 
@@ -1246,6 +1340,7 @@ def mask_eval(program, shape, device, dtype, out=None, stream=None):
         raise ValueError("preallocated output must be %s uint8" % (shape,))
     ors, ops_ = _strides(out)
     _lib.call(name, device, _sh(stream), shape[0], shape[1], shape[2], C.byref(p), C.c_void_p(out.ptr), ors, ops_)
+    _written(out)
     out._mask_operands = held       # the kernel may still be queued: the operands live as long as the result
     return out
 
@@ -1282,6 +1377,7 @@ def mask_morph(inp, offsets, op, iterations=1, mask=None, border_value=0, out=No
     _lib.call("spc_mask_morph_u8", inp.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(inp.ptr), *_strides(inp),
               C.c_void_p(mask.ptr) if mask is not None else None, mrs, mps, int(op), offs.ctypes.data_as(C.c_void_p),
               int(offs.shape[0]), int(iterations), int(border_value), C.c_void_p(out.ptr), ws, wsn, C.byref(run))
+    _written(out)
     return (out, run.value) if return_iterations else out
 
 
@@ -1369,6 +1465,7 @@ def label_select(labels, nlabels, keep, out=None, stream=None):
     out = _contiguous_out(out, shape, np.uint8, labels.device)
     _lib.call("spc_label_select_i32", labels.device, _sh(stream), shape[0], shape[1], shape[2], C.c_void_p(labels.ptr), nlabels,
               C.c_void_p(keep.ptr), C.c_void_p(out.ptr))
+    _written(out)
     out._keep_table = keep          # the kernel may still be queued: the table lives as long as the result
     return out
 

@@ -1,8 +1,12 @@
-"""Time the fused moment kernel (ops.moments -> m0, m1, m2) at 1024^3 float32 under five kinds of mask, with the mask-first
-march on and off (SPC_MOMENTS_MASK_FIRST=1 / 0, read per call): the benchmark's mask (data > 2 sigma with a 1 % flip), a
-signal mask (data > 5 sigma), 80 % random, all ones and no mask array (where the switch selects nothing).  Cube and masks
-are one seeded 16-row tile repeated along y, as in bench.py.  One JSON record per mask and setting: median / min / max
-of the HIP-event times of the launches, and the algorithmic 5 (4 without an array) bytes per voxel over the median.
+"""Time the fused moment kernel (ops.moments -> m0, m1, m2) at 1024^3 float32 under five kinds of mask: the benchmark's mask
+(data > 2 sigma with a 1 % flip), a signal mask (data > 5 sigma), 80 % random, all ones and no mask array (where the
+switches select nothing).  Four forms of the launch, alternating in two rounds: "loop" = the loop that loads every sample
+(SPC_MOMENTS_MASK_FIRST=0), "bytes" = the mask-first march on the mask's bytes (SPC_MOMENTS_MASK_BITS=0), "bits" = the same
+march on the packed form of a reused MaskSpec, "fresh" = a new MaskSpec at every call (always its first use: the byte
+kernel, what a mask used once costs).  Both switches are read per call.  With a mask array also one "pack" record: the
+one-off spc_mask_pack_bits launch.  Cube and masks are one seeded 16-row tile repeated along y, as in bench.py.  One JSON
+record per mask and form: median / min / max of the HIP-event times of the launches, and the algorithmic 5 (4 without an
+array) bytes per voxel over the median.
 
     python tools/time_moments_masks.py [--reps 20] [--n 1024] [--out FILE.jsonl]
 """
@@ -19,7 +23,8 @@ import bench  # noqa: E402  (replicate_rows: one upload, device-to-device doubli
 from spectral_cube_amd import _lib, ops, synth  # noqa: E402
 from spectral_cube_amd.device import DeviceArray, Event, Stream  # noqa: E402
 
-SWITCH = "SPC_MOMENTS_MASK_FIRST"
+SWITCH, BITS = "SPC_MOMENTS_MASK_FIRST", "SPC_MOMENTS_MASK_BITS"
+FORMS = {"loop": ("0", "0"), "bytes": ("1", "0"), "bits": ("1", "1"), "fresh": ("1", "1")}     # form -> the two switches
 
 
 def timed(fn, st, reps, device):
@@ -68,22 +73,43 @@ def main():
             bench.replicate_rows(maskd, tmask)
             spec = ops.MaskSpec(_lib.MASK_ARRAY, array=maskd)
         per_voxel = 5 if tmask is not None else 4
-        for round_ in range(2):                                 # the two settings alternate: a drift shows as a difference between rounds
-            for switch in ("0", "1"):
-                os.environ[SWITCH] = switch                     # (the library reads it per call)
-                t = timed(lambda: ops.moments(cube, d_cen, dv=500.0, m1_add=cref + v[0], mask=spec, want=("m0", "m1", "m2"),
-                                              stream=st, out=out), st, args.reps, device)
-                ms = float(np.median(t))
-                rec = dict(mask=label, valid_fraction=round(float(np.count_nonzero(tmask)) / tmask.size, 4) if tmask is not None else 1.0,
-                           shape=list(shape), mask_first=int(switch), round=round_, launches=len(t), median_ms=round(ms, 4),
-                           min_ms=round(float(np.min(t)), 4), max_ms=round(float(np.max(t)), 4),
-                           algorithmic_tbps=round(n ** 3 * per_voxel / ms / 1e9, 3))
-                line = json.dumps(rec)
-                print(line, flush=True)
-                if sink:
-                    sink.write(line + "\n")
-                    sink.flush()
+
+        def record(form, round_, t, **more):
+            ms = float(np.median(t))
+            rec = dict(mask=label, valid_fraction=round(float(np.count_nonzero(tmask)) / tmask.size, 4) if tmask is not None else 1.0,
+                       shape=list(shape), form=form, mask_first=int(FORMS.get(form, ("1",))[0]), round=round_, launches=len(t),
+                       median_ms=round(ms, 4), min_ms=round(float(np.min(t)), 4), max_ms=round(float(np.max(t)), 4),
+                       algorithmic_tbps=round(n ** 3 * per_voxel / ms / 1e9, 3), **more)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if sink:
+                sink.write(line + "\n")
+                sink.flush()
+
+        def launch(m):
+            return ops.moments(cube, d_cen, dv=500.0, m1_add=cref + v[0], mask=m, want=("m0", "m1", "m2"), stream=st, out=out)
+
+        for round_ in range(2):                                 # the forms alternate: a drift shows as a difference between rounds
+            for form, (first, bits) in FORMS.items():
+                if spec is None and form in ("bits", "fresh"):
+                    continue                                    # no mask array: nothing to pack
+                os.environ[SWITCH], os.environ[BITS] = first, bits      # (the library reads them per call)
+                if form == "fresh":
+                    fn = lambda: launch(ops.MaskSpec(_lib.MASK_ARRAY, array=maskd))     # noqa: E731
+                else:
+                    fn = lambda: launch(spec)                                           # noqa: E731
+                t = timed(fn, st, args.reps, device)
+                record(form, round_, t, packed=bool(spec is not None and spec._bits is not None and form == "bits"))
+        if spec is not None:
+            import ctypes as C
+            need = int(_lib.load().spc_mask_bits_bytes(n, n, n))
+            bits_buf = DeviceArray((need,), np.uint8, device)
+            m = spec.to_c()
+            t = timed(lambda: _lib.call("spc_mask_pack_bits", device, st.handle, n, n, n, C.byref(m), C.c_void_p(bits_buf.ptr), need),
+                      st, args.reps, device)
+            record("pack", 0, t, bits_bytes=need)
     os.environ.pop(SWITCH, None)
+    os.environ.pop(BITS, None)
     if sink:
         sink.close()
 
