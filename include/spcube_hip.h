@@ -572,6 +572,61 @@ int spc_label_objects_i32(int device, void* stream, int64_t nz, int64_t ny, int6
 int spc_label_select_i32(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const int32_t* d_labels, int64_t nlabels,
                          const uint8_t* d_keep, uint8_t* d_out);
 
+/* ---- per-label measurements of a cube: sums, extrema with their positions, first and second moments ----
+ * The scipy.ndimage measurement family (sum_labels, mean, variance, minimum, maximum, their positions, center_of_mass)
+ * over the labels of spc_label_u8, which users of the reference run on the host on the label array and the cube: one
+ * streaming segmented reduction of the cube through its labels; only the per-label tables ever travel.
+ *
+ * cube: the samples, a strided view is read in place.  mask: the cube's mask, or NULL.  d_labels: (nz, ny, nx) int32,
+ * C-contiguous, labels 0 ... nlabels.  d_origin: double[(nlabels + 1) x 4] on the device, v0, z0, y0, x0 of every label,
+ * or NULL for all zero.  want: which groups of tables are computed (SPC_MEASURE_*); a group that is not wanted is neither
+ * computed nor written and its pointers are not read.
+ * A voxel is measured when its label is above 0, the mask includes it and its sample is not NaN; +-inf samples take part
+ * as IEEE arithmetic gives.  Label 0, the background, is never measured: entry 0 of every table is that of a label
+ * without a measured voxel.  With dz = z - z0, dy = y - y0, dx = x - x0 over the measured voxels of label k:
+ *     SPC_MEASURE_SUMS     d_count[k] (int64), d_sums[2 k] = sum (v - v0), d_sums[2 k + 1] = sum (v - v0)^2
+ *     SPC_MEASURE_EXTREMA  d_min[k], d_max[k] (the cube's sample type), d_min_pos[k], d_max_pos[k] (int64): the linear
+ *                          C-order index of the FIRST minimum / maximum (the smallest index on ties, scipy's
+ *                          minimum_position / maximum_position); -0.0 and +0.0 compare equal and a zero extreme is
+ *                          written as +0.0; a label without a measured voxel gets NaN and -1
+ *     SPC_MEASURE_FIRST    d_first[4 k ...] = sum v, sum v dz, sum v dy, sum v dx
+ *     SPC_MEASURE_SECOND   d_second[6 k ...] = sum v dz^2, v dy^2, v dx^2, v dz dy, v dz dx, v dy dx
+ * Every sum is accumulated in float64 whatever the cube's type.  Lanes run along x; a wave reduces each run of one label
+ * among its 64 voxels before anything leaves it and carries a run that goes on into its next 64 voxels, so a run costs
+ * at most one global atomic per quantity (csrc/spc_label_measure.hip).  The sample and the mask byte are fetched only
+ * where the label is above 0.  THE ORDER OF THE ATOMIC ADDS IS NOT FIXED: counts, extrema and positions are the same on
+ * every call, the float64 sums are reproducible only to float64 rounding, |difference| <= 2 (m - 1) 2^-53 sum |term| for
+ * a label of m measured voxels.  (The first floating-point atomics of this library; every other result is bit-stable.)
+ * The positions of a float64 cube take a second launch over the labels.
+ * The entry initialises every table it writes: tables and workspace may hold anything when the call begins.  A label
+ * outside 0 ... nlabels never indexes a table: the voxel is skipped and the call returns SPC_ERR_INVALID through a device
+ * flag read with the status (the call waits for its stream); nothing else reaches the host.  d_workspace: what the query
+ * returns for the same nlabels and want (the flag, and two 64-bit keys per label for the extrema).
+ * Limits as for spc_label_objects_i32: more than 2^31 - 1 voxels SPC_ERR_UNSUPPORTED; SPC_ERR_INVALID before any device
+ * work for a NULL pointer of a wanted group, a shape that is not positive, a stride too small, nlabels outside
+ * 0 ... 2^31 - 1, want 0 or with an unknown bit, buffers that overlap, a workspace too small. */
+#define SPC_MEASURE_SUMS    1u
+#define SPC_MEASURE_EXTREMA 2u
+#define SPC_MEASURE_FIRST   4u
+#define SPC_MEASURE_SECOND  8u
+typedef struct {
+    int64_t* d_count;      /* SUMS */
+    double* d_sums;        /* SUMS: (nlabels + 1) x 2 */
+    void* d_min;           /* EXTREMA: float / double (nlabels + 1) */
+    void* d_max;
+    int64_t* d_min_pos;
+    int64_t* d_max_pos;
+    double* d_first;       /* FIRST: (nlabels + 1) x 4 */
+    double* d_second;      /* SECOND: (nlabels + 1) x 6 */
+} spc_label_measure_outputs;
+size_t spc_label_measure_workspace_bytes(int64_t nlabels, uint32_t want);
+int spc_label_measure_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, const int32_t* d_labels,
+                          int64_t nlabels, const double* d_origin, uint32_t want, const spc_label_measure_outputs* out,
+                          void* d_workspace, size_t workspace_bytes);
+int spc_label_measure_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, const int32_t* d_labels,
+                          int64_t nlabels, const double* d_origin, uint32_t want, const spc_label_measure_outputs* out,
+                          void* d_workspace, size_t workspace_bytes);
+
 /* ---- rank filters: median / minimum / maximum / percentile / rank over a sliding window ----
  * spectral_smooth_median / spectral_filter (spectral_cube.py:2844-2898, dask_spectral_cube.py:920-960) and
  * spatial_smooth_median / spatial_filter (spectral_cube.py:2749-2806, dask_spectral_cube.py:995-1029) with a filter of

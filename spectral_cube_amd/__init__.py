@@ -27,3 +27,6 @@ from .morphology import (binary_dilation, binary_erosion, binary_opening, binary
                          generate_binary_structure)
 from . import labelling  # noqa: F401
 from .labelling import label, remove_small_objects, LabelMap  # noqa: F401
+from . import measurements  # noqa: F401
+from .measurements import (sum_labels, mean, variance, standard_deviation, minimum, maximum, minimum_position,  # noqa: F401
+                           maximum_position, extrema, center_of_mass)

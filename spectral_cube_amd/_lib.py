@@ -50,6 +50,8 @@ MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_REACH, MORPH_MAX_OFFSETS = 3, 343
 # spc_label_u8 / spc_label_objects_i32 / spc_label_select_i32: the most voxels (int32 linear indices), the flag's scratch
 LABEL_MAX_VOXELS, LABEL_OBJECTS_WORKSPACE_BYTES = 2 ** 31 - 1, 256
+# the groups of tables of spc_label_measure_f32 / _f64 (SPC_MEASURE_*)
+MEASURE_SUMS, MEASURE_EXTREMA, MEASURE_FIRST, MEASURE_SECOND = 1, 2, 4, 8
 # spc_arith_program (spc_arith_f32 / _f64): the step limit and spc_arith_opcode
 ARITH_MAX_STEPS = 4
 AOP_ADD, AOP_SUB, AOP_MUL, AOP_DIV, AOP_POW, AOP_SQUARE, AOP_SQRT, AOP_RECIP, AOP_ONE = range(9)
@@ -155,6 +157,13 @@ class SpcStatsOutputs(C.Structure):
                 ("d_sum", C.c_void_p), ("d_sumsq", C.c_void_p)]
 
 
+class SpcLabelMeasureOutputs(C.Structure):
+    """spc_label_measure_outputs: the tables of spc_label_measure_f32 / _f64, one pointer each; a group that is not wanted
+    stays NULL"""
+    _fields_ = [("d_count", C.c_void_p), ("d_sums", C.c_void_p), ("d_min", C.c_void_p), ("d_max", C.c_void_p),
+                ("d_min_pos", C.c_void_p), ("d_max_pos", C.c_void_p), ("d_first", C.c_void_p), ("d_second", C.c_void_p)]
+
+
 class SpcDeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("arch", C.c_char * 64),
                 ("compute_units", C.c_int), ("wavefront_size", C.c_int),
@@ -250,6 +259,9 @@ SIGNATURES = {
     "spc_label_u8": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _P(_i64)]),
     "spc_label_objects_i32": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz]),
     "spc_label_select_i32": (_i, [_i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "spc_label_measure_workspace_bytes": (_sz, [_i64, C.c_uint32]),
+    "spc_label_measure_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _i64, _vp, C.c_uint32, _P(SpcLabelMeasureOutputs), _vp, _sz]),
+    "spc_label_measure_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _vp, _i64, _vp, C.c_uint32, _P(SpcLabelMeasureOutputs), _vp, _sz]),
     "spc_arith_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _P(SpcArithProgram), _vp, _i64, _i64]),
     "spc_arith_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _P(SpcArithProgram), _vp, _i64, _i64]),
     "spc_rank_filter_axis0_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i, _i, _i, _f, _vp, _i64, _i64]),

@@ -13,8 +13,10 @@ ignored, and an all-False structure makes every True voxel a component of its ow
 on its own: it becomes the middle plane of a 3x3x3 structure whose other planes are False.
 
 Limits: at most 2**31 - 1 voxels (linear indices are int32; 1024**3 fits); an out-of-core cube is refused (components
-cross its strips); cubes sharded over several devices are not labelled; boundaries are not periodic; per-label sums of
-the cube's samples (``sum_labels``, flux and moment catalogues) are not built.
+cross its strips); cubes sharded over several devices are not labelled; boundaries are not periodic.
+
+``LabelMap.measure(cube)`` and ``LabelMap.catalog(cube)`` measure a cube's samples inside the regions (measurements.py:
+the scipy.ndimage measurement family and a flux / peak / centroid / dispersion catalogue, on the device).
 """
 import numpy as np
 
@@ -109,6 +111,19 @@ class LabelMap:
         elif k.shape != (self.n + 1,):
             raise ValueError("a keep table has n + 1 = %d entries (got shape %s)" % (self.n + 1, k.shape))
         return M.DeviceBooleanMask(ops.label_select(self._labels, self.n, k), wcs=self.wcs, shape=self.shape)
+
+    def measure(self, cube, want=("sums", "extrema", "first"), origin=None):
+        """{table: host array of n + 1 rows}: the samples of *cube* measured inside every label in one pass on the device
+        (measurements.measure, ops.label_measure) - count and sums, extrema with their positions, first moments; row 0,
+        the background, is never measured.  An out-of-core cube is refused."""
+        from . import measurements
+        return measurements.measure(cube, self, want=want, origin=origin)
+
+    def catalog(self, cube):
+        """a dict of host arrays of length n, one row per label: npix, flux, peak, peak_position, centroid, sigma_z /
+        sigma_y / sigma_x, position_angle and, with a WCS, v_cen, sigma_v, lon, lat (measurements.catalog)"""
+        from . import measurements
+        return measurements.catalog(cube, self)
 
 
 def label(input, structure=None, cube=None):

@@ -1470,6 +1470,66 @@ def label_select(labels, nlabels, keep, out=None, stream=None):
     return out
 
 
+MEASURE_GROUPS = {"sums": _lib.MEASURE_SUMS, "extrema": _lib.MEASURE_EXTREMA, "first": _lib.MEASURE_FIRST,
+                  "second": _lib.MEASURE_SECOND}
+# table -> (its group, the columns after the label axis, dtype; None: the cube's)
+_MEASURE_TABLES = {"count": ("sums", (), np.int64), "sums": ("sums", (2,), np.float64),
+                   "min": ("extrema", (), None), "max": ("extrema", (), None),
+                   "min_pos": ("extrema", (), np.int64), "max_pos": ("extrema", (), np.int64),
+                   "first": ("first", (4,), np.float64), "second": ("second", (6,), np.float64)}
+
+
+def label_measure(data, labels, nlabels, mask_spec=None, origin=None, want=("sums", "extrema", "first"), out=None, stream=None,
+                  workspace=None):
+    """{table: DeviceArray} of nlabels + 1 rows each (row 0: the background, never measured): the float32 / float64 cube
+    *data* (a strided view is read in place) measured through the int32 label array *labels* with labels 0 ... *nlabels*
+    (spc_label_measure_f32 / _f64: the sums behind scipy.ndimage.sum_labels, mean, variance, minimum, maximum, their
+    positions and center_of_mass).  A voxel counts when its label is above 0, *mask_spec* (the cube's MaskSpec; None: no mask)
+    includes it and its sample is not NaN.  *origin*: (nlabels + 1, 4) float64, v0, z0, y0, x0 of every label, a DeviceArray or a host array that is
+    uploaded; None: all zero.  *want*: the groups of tables, each computed only when asked for -
+    "sums": count (int64), sums (n + 1, 2) = sum (v - v0), sum (v - v0)^2;
+    "extrema": min, max (the cube's dtype), min_pos, max_pos (int64 linear C-order index of the FIRST extreme; NaN and -1
+    for a label with nothing measured);
+    "first": first (n + 1, 4) = sum v, sum v (z - z0), sum v (y - y0), sum v (x - x0);
+    "second": second (n + 1, 6) = sum v dz^2, v dy^2, v dx^2, v dz dy, v dz dx, v dy dx.
+    All sums are float64; their atomic order is not fixed, so they are reproducible to float64 rounding only.  A label
+    outside 0 ... nlabels raises ValueError.  *out*: {table: preallocated DeviceArray}; *workspace*: a uint8 DeviceArray of
+    spc_label_measure_workspace_bytes bytes (the stream's pooled scratch otherwise).  Tables and workspace may hold
+    anything.  Only the status reaches the host, inside the call."""
+    shape, nlabels = _label_map(labels, nlabels)
+    name, dtype = _entry("label_measure", data)
+    c = _cube_c(data)
+    if tuple(int(n) for n in data.shape) != shape:
+        raise ValueError("labels %s and the cube %s must have one shape" % (shape, tuple(data.shape)))
+    if isinstance(want, str):
+        want = (want,)
+    unknown = [g for g in want if g not in MEASURE_GROUPS]
+    if unknown or not want:
+        raise ValueError("want must name at least one of %s (got %r)" % (sorted(MEASURE_GROUPS), tuple(want)))
+    bits = 0
+    for g in want:
+        bits |= MEASURE_GROUPS[g]
+    m = _mask_c(mask_spec, data)
+    nt = nlabels + 1
+    if origin is not None and not isinstance(origin, DeviceArray):
+        origin = np.ascontiguousarray(origin, dtype=np.float64)
+        if origin.shape != (nt, 4):
+            raise ValueError("origin must have shape (nlabels + 1, 4) = (%d, 4) (got %s)" % (nt, origin.shape))
+        origin = DeviceArray.from_numpy(origin, labels.device, stream)
+    elif origin is not None and (tuple(origin.shape) != (nt, 4) or origin.dtype != _F64):
+        raise ValueError("origin must be a float64 table of shape (%d, 4) (got %s %s)" % (nt, tuple(origin.shape), origin.dtype))
+    res = {}
+    o = _lib.SpcLabelMeasureOutputs()
+    for table, (group, cols, dt) in _MEASURE_TABLES.items():
+        if group in want:
+            res[table] = _given(out, table, (nt,) + cols, dtype if dt is None else dt, labels.device)
+            setattr(o, "d_" + table, res[table].ptr)
+    ws, wsn = _scratch(int(_lib.load().spc_label_measure_workspace_bytes(nlabels, bits)), workspace, labels.device, stream)
+    _lib.call(name, labels.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(labels.ptr), nlabels,
+              C.c_void_p(origin.ptr) if origin is not None else None, bits, C.byref(o), ws, wsn)
+    return res
+
+
 def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, out=None):
     """q-th percentile along x per (z, y) row, no transposed copy (spc_percentile_axis2_f32); *center*: a (nz, ny)
     float32 DeviceArray.  Raises HipUnsupported for rows of more than 4096 samples."""
