@@ -427,6 +427,37 @@ int spc_mask_bbox_f32(int device, void* stream, const spc_cube_f32* cube, const 
 int spc_mask_bbox_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded,
                       int64_t* d_box);
 
+/* ---- position-velocity diagrams: the spectrum at every point of a path on the sky ----
+ * Replaces SpectralCube.to_pvextractor (spectral_cube.py:2506-2513: the hand-over to pvextractor.extract_pv_slice(cube,
+ * path), which pulls the cube to the host) and the axis-aligned cube[:, j, :] Slice: d_out[k, p] (nz x npts, the cube's
+ * dtype, out_row_stride elements between channels, 0 = npts) is the mean over nlines parallel lines of the FILLED cube
+ * interpolated at the pixel position (d_xs[l * npts + p], d_ys[l * npts + p]) (device arrays of nlines x npts float64,
+ * 0-based) of channel k.  The cube is read in place (any view spc_check_cube accepts); there is no workspace and no
+ * (nz, nlines, npts) intermediate.
+ *   sample: the cube's value where the mask includes the voxel, `fill` where it does not (nan_excluded: the rule of
+ *     spc_subcube_*, a NaN sample counts as excluded).  The mask byte is read first; an excluded sample is not fetched
+ *     (a predicate term needs the sample and fetches it).
+ *   domain: a point is inside when 0 <= x <= nx - 1 and 0 <= y <= ny - 1, anything else (-1e-9, nx - 1 + 1e-9, NaN)
+ *     gives NaN: scipy.ndimage.map_coordinates(mode='constant', cval=nan).
+ *   order 0: the sample at (floor(y + 0.5), floor(x + 0.5)); with one line and respect_nan it is copied bit for bit.
+ *   order 1: x0 = floor(x), fx = x - x0 (likewise y); the weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx of the
+ *     neighbours (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1) in float64.  A neighbour whose weight is exactly 0 is not
+ *     read and does not count (x = nx - 1 is inside: its right-hand neighbours weigh 0).  The line's value is
+ *     0 + w v + w v ... in float64 in that order, each product and each sum rounded on its own (no fused multiply-add).
+ *   respect_nan != 0: the line's value is NaN when a neighbour of non-zero weight is NaN; == 0: such a neighbour adds
+ *     0 (at order 0 a NaN sample becomes 0, as map_coordinates on nan_to_num'd data gives).
+ *   width: d_out = (v_0 + v_1 + ...) / n over the n lines whose value is not NaN, added in line order in float64 and
+ *     rounded once to the cube's dtype; NaN when n = 0.  No atomics: the same call gives the same bits.
+ *   d_count (int32, nz x npts, count_row_stride elements between channels, 0 = npts; may be NULL): n.
+ * Lanes run along the path, blocks split the channels in batches whose loads are issued together; launches cover any
+ * npts and nz.  SPC_ERR_INVALID for npts < 1, nlines < 1, an order other than 0 / 1, NULL arrays, strides below npts. */
+int spc_pv_extract_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int nan_excluded, float fill,
+                       int64_t npts, int64_t nlines, const double* d_xs, const double* d_ys, int order, int respect_nan,
+                       float* d_out, int64_t out_row_stride, int32_t* d_count, int64_t count_row_stride);
+int spc_pv_extract_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int nan_excluded, double fill,
+                       int64_t npts, int64_t nlines, const double* d_xs, const double* d_ys, int order, int respect_nan,
+                       double* d_out, int64_t out_row_stride, int32_t* d_count, int64_t count_row_stride);
+
 /* ---- mask expressions evaluated once on the device (masks.py:239-250 composition, :399-455 CompositeMask / InvertedMask,
  * :670-758 LazyComparisonMask) ----
  * A mask tree that is not an AND of spc_mask terms - a threshold that is a map, a spectrum or a cube, `|` `^` `~`, == and

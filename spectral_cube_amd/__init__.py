@@ -30,3 +30,5 @@ from .labelling import label, remove_small_objects, LabelMap  # noqa: F401
 from . import measurements  # noqa: F401
 from .measurements import (sum_labels, mean, variance, standard_deviation, minimum, maximum, minimum_position,  # noqa: F401
                            maximum_position, extrema, center_of_mass)
+from . import pvextract  # noqa: F401
+from .pvextract import Path, extract_pv_slice  # noqa: F401

@@ -248,6 +248,8 @@ SIGNATURES = {
     "spc_downsample_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i, _i64, _i, _i, _vp, _i64, _i64, _vp]),
     "spc_subcube_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _P(_i64), _P(_i64), _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _f]),
     "spc_subcube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _P(_i64), _P(_i64), _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _d]),
+    "spc_pv_extract_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64, _vp, _i64]),
+    "spc_pv_extract_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64, _vp, _i64]),
     "spc_mask_bbox_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp]),
     "spc_mask_bbox_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
     "spc_mask_eval_f32": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),

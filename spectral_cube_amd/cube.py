@@ -1920,7 +1920,8 @@ class SpectralCube:
         ``cube[k]`` / ``cube[k, ys, xs]``: the FILLED channel as a 2-D Projection with the celestial WCS, its header
         carrying CRVAL3 / CDELT3 / CUNIT3 of that channel.  ``cube[zs, j, i]``: the filled spectrum as a 1-D Projection
         whose wcs is the spectral axis alone.  Integers that include the spectral axis and another:
-        NotImplementedError as the reference; one integer on y or x (a position-velocity slice): NotImplementedError."""
+        NotImplementedError as the reference; one integer on y or x (a position-velocity slice): NotImplementedError
+        (``pv_slice(y=j)`` / ``pv_slice(x=i)`` give it)."""
         view = self._normalize_view(view)
         meta = dict(self._meta)
         slice_data = [(s.start, s.stop, s.step) if isinstance(s, slice) else s for s in view]
@@ -1933,7 +1934,8 @@ class SpectralCube:
                 raise NotImplementedError("1D slices along non-spectral axes are not yet implemented.")
             return self._spectrum(view, meta)
         if ints[0] != 0:
-            raise NotImplementedError("a single integer index on a spatial axis (a position-velocity slice) is not built")
+            raise NotImplementedError("a single integer index on a spatial axis (a position-velocity slice) is not built "
+                                      "as an index: cube.pv_slice(y=j) / cube.pv_slice(x=i) give it as a Projection")
         return self._channel(view, meta)
 
     def _view_spec(self, view):
@@ -2019,6 +2021,21 @@ class SpectralCube:
         data, _ = self._gather(spec, shape, filled=True)
         meta = self._spectrum_meta(meta, view)
         return Projection(data.get()[:, 0, 0], unit=self._unit, wcs=w1, meta=meta, device=self.device)
+
+    def pv_slice(self, path=None, y=None, x=None, **kwargs):
+        """The position-velocity diagram along *path* (a ``pvextract.Path`` or a list of ``(x, y)`` pixel positions) as a
+        Projection of shape ``(nz, npts)``: ``pvextract.extract_pv_slice(self, path, **kwargs)`` (spacing, order - 1 by
+        default, not pvextractor's 3 -, respect_nan, nlines), computed on the device; stands in for ``to_pvextractor()``
+        (spectral_cube.py:2506-2513).  ``pv_slice(y=j)`` / ``pv_slice(x=i)``: the axis-aligned cut, an exact copy of
+        ``filled_data[:, j, :]`` / ``filled_data[:, :, i]`` (negative indices as in numpy)."""
+        from . import pvextract
+        if path is None:
+            if kwargs:
+                raise TypeError("pv_slice(y=...) / pv_slice(x=...) take no other keyword (got %s)" % sorted(kwargs))
+            return pvextract.axis_cut(self, y=y, x=x)
+        if y is not None or x is not None:
+            raise ValueError("give a path, or one of y= and x=, not both")
+        return pvextract.extract_pv_slice(self, path, **kwargs)
 
     def _spectral_value(self, value):
         """a spectral coordinate in the cube's spectral unit: plain numbers are taken to be in it, an object with

@@ -693,6 +693,49 @@ def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_m
     return out, out_mask
 
 
+def pv_extract(data, xs, ys, order=1, respect_nan=True, mask_spec=None, fill=np.nan, out=None, count=None, stream=None,
+               nan_excluded=False):
+    """(nz, npts) DeviceArray in the cube's dtype: the position-velocity diagram of the float32 / float64 cube *data* (a
+    strided view is read in place) along the path whose pixel positions are *xs*, *ys* - host arrays or float64
+    DeviceArrays of shape (npts,) or (nlines, npts), 0-based - averaged over the lines (spc_pv_extract_f32 / _f64; stands in
+    for pvextractor.extract_pv_slice behind SpectralCube.to_pvextractor, spectral_cube.py:2506-2513, and for the
+    axis-aligned cube[:, j, :]).  A sample is the FILLED cube's: *fill* where *mask_spec* (the cube's MaskSpec; None: no
+    mask; *nan_excluded* as in subcube) excludes the voxel, and such a sample is not fetched.  A point is inside when
+    0 <= x <= nx - 1 and 0 <= y <= ny - 1 and NaN otherwise (scipy's mode='constant', cval=nan).  *order* 0: the sample at
+    (floor(y + 0.5), floor(x + 0.5)); 1: bilinear in float64, a neighbour of weight exactly 0 neither read nor counted.
+    *respect_nan*: a NaN neighbour of non-zero weight makes the line's value NaN; otherwise it adds 0.  The result is the
+    mean over the lines whose value is not NaN, added in line order in float64 and rounded once; NaN when there is none.
+    *count*: an int32 (nz, npts) DeviceArray that receives the number of such lines.  *out* / *count* may hold anything.
+    Two calls give the same bits (no atomics)."""
+    name, dtype = _entry("pv_extract", data)
+    c, m = _cube_c(data), _mask_c(mask_spec, data)
+    if int(order) not in (0, 1) or order != int(order):
+        raise ValueError("order %r is not built on the device: 0 (nearest) or 1 (bilinear)" % (order,))
+    if isinstance(xs, DeviceArray) and isinstance(ys, DeviceArray):
+        if xs.dtype != _F64 or ys.dtype != _F64 or xs.shape != ys.shape or len(xs.shape) not in (1, 2):
+            raise ValueError("xs, ys must be float64 arrays of one shape, (npts,) or (nlines, npts)")
+        d_xs, d_ys = xs, ys
+    else:
+        xs, ys = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(ys, dtype=np.float64)
+        if xs.shape != ys.shape or xs.ndim not in (1, 2):
+            raise ValueError("xs, ys must have one shape, (npts,) or (nlines, npts) (got %s and %s)" % (xs.shape, ys.shape))
+        d_xs, d_ys = (DeviceArray.from_numpy(a, data.device, stream) if a.size else None for a in (xs, ys))
+    shape2 = tuple(int(n) for n in xs.shape)
+    nlines, npts = shape2 if len(shape2) == 2 else (1, shape2[0])
+    if npts < 1 or nlines < 1:
+        raise ValueError("a path needs at least one point and one line (got %d lines of %d points)" % (nlines, npts))
+    nz = int(data.shape[0])
+    out = _given({"out": out}, "out", (nz, npts), dtype, data.device)
+    if count is not None and (tuple(count.shape) != (nz, npts) or count.dtype != np.dtype(np.int32)):
+        raise ValueError("count must be an int32 array of shape %s" % ((nz, npts),))
+    _lib.call(name, data.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill), npts, nlines,
+              C.c_void_p(d_xs.ptr), C.c_void_p(d_ys.ptr), int(order), 1 if respect_nan else 0, C.c_void_p(out.ptr),
+              getattr(out, "row_stride", npts), C.c_void_p(count.ptr) if count is not None else None,
+              getattr(count, "row_stride", npts))
+    out._plan = (d_xs, d_ys)             # the uploads stay alive until the result goes
+    return out
+
+
 def arith_operand_strides(shape, cube_shape, strides=None):
     """element strides (z, y, x) of an operand of *shape* broadcast against *cube_shape* by numpy's rules, 0 along a
     broadcast axis; *strides*: the operand's own element strides per axis (C-contiguous when None).  ValueError in
