@@ -458,6 +458,55 @@ int spc_pv_extract_f64(int device, void* stream, const spc_cube_f64* cube, const
                        int64_t npts, int64_t nlines, const double* d_xs, const double* d_ys, int order, int respect_nan,
                        double* d_out, int64_t out_row_stride, int32_t* d_count, int64_t count_row_stride);
 
+/* ---- polynomial baselines: fit every spectrum on its line-free channels, subtract the model ----
+ * The step docs/continuum_subtraction.rst does for a constant (mask the line channels, median(axis=0), subtract) and
+ * apply_function_parallel_spectral (spectral_cube.py:3103) does for anything else by handing every spectrum to a
+ * Python function on the host (CASA: imcontsub fitorder=n).  Two entries: the fit, a masked streaming reduction along z
+ * into a small normal-equation system per spaxel, and the apply, one element-wise pass.
+ *   abscissa: the channel index mapped to [-1, 1], t_k = (2k - (nz - 1)) / (nz - 1); t_0 = 0 when nz == 1.
+ *   basis: Legendre, P_0 ... P_p with p = order, 0 <= order <= SPC_BASELINE_MAX_ORDER.  The CALLER computes the table
+ *     d_basis[k * (p + 1) + j] = P_j(t_k) for all nz channels in float64 (numpy.polynomial.legendre.legvander(t, p)) and
+ *     uploads it; the device never recomputes a basis value.  (A power basis in the channel number has a Gram matrix of
+ *     condition 4e24 at nz = 257, order 5; Legendre's is 11.)
+ *   fit set of spectrum (y, x): every channel k that is in the channel list (d_channels: nfit int32 channel numbers in
+ *     increasing order; NULL: all channels, nfit == nz), whose voxel (k, y, x) the mask includes and whose sample is not
+ *     NaN; n is its size.  Channels outside the list are not read, neither their mask bytes nor their samples (a list
+ *     entry outside 0 ... nz - 1 is skipped).  Inside the list the mask byte is read first and an excluded sample is not
+ *     fetched (a predicate term needs the sample and fetches it): the include-array rule above.
+ *   solve: G_ij = sum P_i(t_k) P_j(t_k) and b_i = sum P_i(t_k) v_k over the fit set, in float64 for float32 cubes too,
+ *     added in list order from 0, each product and each sum rounded on its own (no fused multiply-add).  A long list is
+ *     cut into spc_baseline_segments() segments of ceil(nfit / segments) list entries, each summed from 0 on its own, and
+ *     the segments are added in index order: the result depends on the shape and nfit only, never on timing.
+ *     n >= p + 1: c = G^-1 b by the root-free Cholesky factorisation G = L D L^T in float64, in this order -
+ *       D_j = G_jj - sum_{k<j} L_jk (L_jk D_k);  L_ij = (G_ij - sum_{k<j} L_ik (L_jk D_k)) / D_j   (i > j; k ascending)
+ *       z_i = b_i - sum_{k<i} L_ik z_k;  w_i = z_i / D_i;  c_i = w_i - sum_{k>i} L_ki c_k          (i descending, k ascending)
+ *     n < p + 1, or a pivot D_j that is not > 0: all p + 1 coefficients are NaN.
+ *   outputs of the fit: d_coef float64 (p + 1, ny, nx) contiguous; d_npts int32 (ny, nx) contiguous, n; may be NULL.
+ *   apply: model_k = c_0 P[k,0] + c_1 P[k,1] + ... + c_p P[k,p], added in that order in float64, for EVERY channel and
+ *     every voxel of the cube whatever any mask says (as cube - map treats the unmasked data).  mode 0: d_out =
+ *     (T)((double)v - model) - a NaN sample stays NaN; mode 1: d_out = (T)model, the cube's samples are not read.  NaN
+ *     coefficients give a NaN spectrum in both modes.  d_out has the cube's shape and its own strides (0 = contiguous).
+ *   No atomics: two identical calls give identical bits.
+ * Lanes run along x, each owns a spaxel and keeps its (p+1)(p+2)/2 + (p+1) float64 sums in registers (the kernels are
+ * templated on the order); a batch of channels' mask bytes is loaded, then the included samples, then the arithmetic.
+ * With more than one segment the partial sums go to d_workspace (spc_baseline_workspace_bytes(); 0 bytes for one
+ * segment) and a second small kernel adds them and solves.  Launches cover any ny, nx, nz.  Outputs and workspace may
+ * hold anything.  SPC_ERR_INVALID for an order outside 0 ... 5, NULL arrays, nfit < 1, nfit != nz without a list, bad
+ * strides, a mode other than 0 / 1, and outputs or workspace that overlap an input or each other. */
+#define SPC_BASELINE_MAX_ORDER 5
+int64_t spc_baseline_segments(int64_t nz, int64_t ny, int64_t nx, int64_t nfit);
+size_t spc_baseline_workspace_bytes(int64_t nz, int64_t ny, int64_t nx, int64_t nfit, int order);
+int spc_baseline_fit_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, int order,
+                         const int32_t* d_channels, int64_t nfit, const double* d_basis, double* d_coef, int32_t* d_npts,
+                         void* d_workspace, size_t workspace_bytes);
+int spc_baseline_fit_f64(int device, void* stream, const spc_cube_f64* cube, const spc_mask_f64* mask, int order,
+                         const int32_t* d_channels, int64_t nfit, const double* d_basis, double* d_coef, int32_t* d_npts,
+                         void* d_workspace, size_t workspace_bytes);
+int spc_baseline_apply_f32(int device, void* stream, const spc_cube_f32* cube, int order, const double* d_basis,
+                           const double* d_coef, int mode, float* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+int spc_baseline_apply_f64(int device, void* stream, const spc_cube_f64* cube, int order, const double* d_basis,
+                           const double* d_coef, int mode, double* d_out, int64_t out_row_stride, int64_t out_plane_stride);
+
 /* ---- mask expressions evaluated once on the device (masks.py:239-250 composition, :399-455 CompositeMask / InvertedMask,
  * :670-758 LazyComparisonMask) ----
  * A mask tree that is not an AND of spc_mask terms - a threshold that is a map, a spectrum or a cube, `|` `^` `~`, == and

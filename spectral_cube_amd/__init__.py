@@ -32,3 +32,5 @@ from .measurements import (sum_labels, mean, variance, standard_deviation, minim
                            maximum_position, extrema, center_of_mass)
 from . import pvextract  # noqa: F401
 from .pvextract import Path, extract_pv_slice  # noqa: F401
+from . import baseline  # noqa: F401
+from .baseline import fit_baseline, subtract_baseline, BaselineFit  # noqa: F401

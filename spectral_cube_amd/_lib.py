@@ -54,6 +54,7 @@ LABEL_MAX_VOXELS, LABEL_OBJECTS_WORKSPACE_BYTES = 2 ** 31 - 1, 256
 MEASURE_SUMS, MEASURE_EXTREMA, MEASURE_FIRST, MEASURE_SECOND = 1, 2, 4, 8
 # spc_arith_program (spc_arith_f32 / _f64): the step limit and spc_arith_opcode
 ARITH_MAX_STEPS = 4
+BASELINE_MAX_ORDER = 5          # SPC_BASELINE_MAX_ORDER
 AOP_ADD, AOP_SUB, AOP_MUL, AOP_DIV, AOP_POW, AOP_SQUARE, AOP_SQRT, AOP_RECIP, AOP_ONE = range(9)
 ARITH_OPCODES = {"add": AOP_ADD, "sub": AOP_SUB, "mul": AOP_MUL, "div": AOP_DIV, "pow": AOP_POW,
                  "square": AOP_SQUARE, "sqrt": AOP_SQRT, "recip": AOP_RECIP, "one": AOP_ONE}
@@ -250,6 +251,12 @@ SIGNATURES = {
     "spc_subcube_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _P(_i64), _P(_i64), _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _d]),
     "spc_pv_extract_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _f, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64, _vp, _i64]),
     "spc_pv_extract_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _d, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64, _vp, _i64]),
+    "spc_baseline_segments": (_i64, [_i64, _i64, _i64, _i64]),
+    "spc_baseline_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i]),
+    "spc_baseline_fit_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz]),
+    "spc_baseline_fit_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz]),
+    "spc_baseline_apply_f32": (_i, [_i, _vp, _P(SpcCube), _i, _vp, _vp, _i, _vp, _i64, _i64]),
+    "spc_baseline_apply_f64": (_i, [_i, _vp, _P(SpcCube), _i, _vp, _vp, _i, _vp, _i64, _i64]),
     "spc_mask_bbox_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _i, _vp]),
     "spc_mask_bbox_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _i, _vp]),
     "spc_mask_eval_f32": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMaskProgram), _vp, _i64, _i64]),

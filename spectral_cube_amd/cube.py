@@ -2037,6 +2037,20 @@ class SpectralCube:
             raise ValueError("give a path, or one of y= and x=, not both")
         return pvextract.extract_pv_slice(self, path, **kwargs)
 
+    def fit_baseline(self, order=1, fit_mask=None, channels=None, exclude=None):
+        """A ``baseline.BaselineFit``: a polynomial of degree *order* (0 ... 5) fitted on the device to the line-free
+        channels of every spectrum - ``baseline.fit_baseline(self, ...)``, which documents *fit_mask* (anything with_mask
+        accepts, ``~signal``), *channels* and *exclude* (``(lo, hi)`` spectral ranges left out).  Stands in for a polyfit per
+        spectrum through ``apply_function_parallel_spectral`` (spectral_cube.py:3103)."""
+        from . import baseline
+        return baseline.fit_baseline(self, order=order, fit_mask=fit_mask, channels=channels, exclude=exclude)
+
+    def subtract_baseline(self, order=1, fit_mask=None, channels=None, exclude=None):
+        """The cube minus the polynomial baseline of ``fit_baseline(...)``, subtracted in every voxel; it keeps this cube's
+        mask, WCS, unit, meta and beam(s)."""
+        from . import baseline
+        return baseline.subtract_baseline(self, order=order, fit_mask=fit_mask, channels=channels, exclude=exclude)
+
     def _spectral_value(self, value):
         """a spectral coordinate in the cube's spectral unit: plain numbers are taken to be in it, an object with
         ``.value`` and ``.unit`` is converted (same kind of unit only, spectral_cube.py:1794-1819)"""

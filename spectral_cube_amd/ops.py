@@ -736,6 +736,107 @@ def pv_extract(data, xs, ys, order=1, respect_nan=True, mask_spec=None, fill=np.
     return out
 
 
+def baseline_abscissa(nz):
+    """t_k = (2k - (nz - 1)) / (nz - 1), the channel index on [-1, 1] (float64; t_0 = 0 when nz == 1)"""
+    nz = int(nz)
+    if nz == 1:
+        return np.zeros(1, np.float64)
+    return (2.0 * np.arange(nz, dtype=np.float64) - (nz - 1)) / (nz - 1)
+
+
+def baseline_basis(nz, order):
+    """(nz, order + 1) float64: the Legendre table P_j(t_k) the baseline entries take (include/spcube_hip.h), computed on
+    the host with numpy.polynomial.legendre.legvander - the device never recomputes a basis value"""
+    return np.ascontiguousarray(np.polynomial.legendre.legvander(baseline_abscissa(nz), int(order)), dtype=np.float64)
+
+
+def _baseline_order(order):
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= int(order) <= _lib.BASELINE_MAX_ORDER:
+        raise ValueError("order must be an integer from 0 to %d (got %r)" % (_lib.BASELINE_MAX_ORDER, order))
+    return int(order)
+
+
+def baseline_channels(channels, nz):
+    """the channel list of a baseline fit as increasing int32 channel numbers: *channels* is None (all), a boolean (nz,)
+    array, or integer indices (negative ones count from the end; duplicates are dropped).  ValueError for anything else"""
+    nz = int(nz)
+    if channels is None:
+        return np.arange(nz, dtype=np.int32)
+    c = np.asarray(channels)
+    if c.dtype == np.bool_:
+        if c.shape != (nz,):
+            raise ValueError("a boolean channel selection must have shape (%d,) (got %s)" % (nz, c.shape))
+        return np.flatnonzero(c).astype(np.int32)
+    if c.ndim != 1 or (c.size and c.dtype.kind not in "iu"):
+        raise ValueError("channels must be a boolean (nz,) array or a 1-D list of integer indices")
+    c = c.astype(np.int64)
+    if c.size and (c.min() < -nz or c.max() >= nz):
+        raise ValueError("channel index out of range for %d channels" % nz)
+    return np.unique(np.where(c < 0, c + nz, c)).astype(np.int32)
+
+
+def baseline_segments(shape, nfit):
+    """how many segments spc_baseline_fit_* cuts a channel list of *nfit* entries into for a cube of *shape*: a fixed rule
+    on the plane and nfit (1: the fit kernel solves itself; more: partial sums through the workspace, added in order)"""
+    nz, ny, nx = (int(n) for n in shape)
+    return int(_lib.load().spc_baseline_segments(nz, ny, nx, int(nfit)))
+
+
+def baseline_fit(data, order, channels=None, mask_spec=None, coef=None, npts=None, stream=None, workspace=None):
+    """(coef, npts): the Legendre coefficients, a float64 (order + 1, ny, nx) DeviceArray, of the polynomial of *order*
+    (0 ... 5) fitted by least squares to every spectrum of the float32 / float64 cube *data* (a strided view is read in
+    place), and the int32 (ny, nx) number of samples each fit used (spc_baseline_fit_f32 / _f64; stands in for a per-spectrum
+    polyfit through apply_function_parallel_spectral, spectral_cube.py:3103, and for CASA's imcontsub fitorder=n).  A
+    spectrum is fitted on the channels of *channels* (None: all; a boolean (nz,) array or integer indices, host side)
+    whose voxel *mask_spec* (the cube's MaskSpec; None: no mask) includes and whose sample is not NaN; other channels are
+    not read.  The abscissa is the channel index mapped to [-1, 1]; sums, the L D L^T solve and the coefficients are
+    float64.  Fewer than order + 1 samples, or a pivot that is not positive: NaN coefficients.  *coef*, *npts*: preallocated
+    outputs; *workspace*: a uint8 DeviceArray of spc_baseline_workspace_bytes bytes (the stream's pooled scratch
+    otherwise).  All three may hold anything.  Two calls give the same bits (no atomics)."""
+    name, _ = _entry("baseline_fit", data)
+    order = _baseline_order(order)
+    c, m = _cube_c(data), _mask_c(mask_spec, data)
+    nz, ny, nx = (int(n) for n in data.shape)
+    chan = baseline_channels(channels, nz)
+    if chan.size < 1:
+        raise ValueError("the channel list is empty")
+    given = {"coef": coef, "npts": npts}
+    for a in (coef, npts):
+        if a is not None and getattr(a, "_is_view", False):
+            raise ValueError("coef and npts must be contiguous arrays, not strided views")
+    coef = _given(given, "coef", (order + 1, ny, nx), np.float64, data.device)
+    npts = _given(given, "npts", (ny, nx), np.int32, data.device)
+    d_basis = DeviceArray.from_numpy(baseline_basis(nz, order), data.device, stream)
+    d_chan = None if channels is None else DeviceArray.from_numpy(chan, data.device, stream)
+    need = int(_lib.load().spc_baseline_workspace_bytes(nz, ny, nx, int(chan.size), order))
+    ws, wsn = _scratch(need, workspace, data.device, stream) if need else (None, 0)
+    _lib.call(name, data.device, _sh(stream), C.byref(c), C.byref(m), order, C.c_void_p(d_chan.ptr) if d_chan is not None else None,
+              int(chan.size), C.c_void_p(d_basis.ptr), C.c_void_p(coef.ptr), C.c_void_p(npts.ptr), ws, wsn)
+    coef._plan = (d_basis, d_chan)       # the uploads stay alive until the result goes
+    return coef, npts
+
+
+def baseline_apply(data, coef, subtract=True, out=None, stream=None):
+    """A DeviceArray of the cube's shape and dtype: *data* minus the baseline model of *coef* (the (order + 1, ny, nx)
+    float64 Legendre coefficients of baseline_fit), or - *subtract* False - the model itself (spc_baseline_apply_f32 / _f64).
+    model_k = sum_j c_j P_j(t_k) in float64 for every channel and every voxel, whatever any mask says; a NaN sample stays
+    NaN in the difference, NaN coefficients give a NaN spectrum.  *out*: a preallocated array, which may be a strided
+    view and may hold anything, but not the cube itself."""
+    name, dtype = _entry("baseline_apply", data)
+    c = _cube_c(data)
+    nz, ny, nx = (int(n) for n in data.shape)
+    if coef.dtype != _F64 or len(coef.shape) != 3 or tuple(coef.shape[1:]) != (ny, nx) or getattr(coef, "_is_view", False):
+        raise ValueError("coef must be a contiguous float64 (order + 1, %d, %d) DeviceArray" % (ny, nx))
+    order = _baseline_order(int(coef.shape[0]) - 1)
+    out = _out_cube(out, (nz, ny, nx), dtype, data.device)
+    ors, ops_ = _strides(out)
+    d_basis = DeviceArray.from_numpy(baseline_basis(nz, order), data.device, stream)
+    _lib.call(name, data.device, _sh(stream), C.byref(c), order, C.c_void_p(d_basis.ptr), C.c_void_p(coef.ptr),
+              0 if subtract else 1, C.c_void_p(out.ptr), ors, ops_)
+    out._plan = (d_basis, coef)
+    return out
+
+
 def arith_operand_strides(shape, cube_shape, strides=None):
     """element strides (z, y, x) of an operand of *shape* broadcast against *cube_shape* by numpy's rules, 0 along a
     broadcast axis; *strides*: the operand's own element strides per axis (C-contiguous when None).  ValueError in
