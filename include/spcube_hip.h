@@ -255,6 +255,61 @@ int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube,
                          void* d_workspace, size_t workspace_bytes,
                          const void* d_mask_bits, size_t bits_bytes);
 
+/* A cube reduced again under the same mask, read as a LIST of the 16-byte lane segments the mask includes, for one
+ * launch plan.  The list is derived from the packed bits (above), so it always agrees with what the bits march reads.
+ * Layout: lane groups and blocks are those of the bits (g = y * (nx / 4) + x / 4, b = g / 64, l = g % 64).  A launch
+ * plan is (zw, nsplit, zchunk): zw waves per block, nsplit ranges of zchunk planes.  Sublist j = split * zw + w of
+ * block b holds the planes wave w of split `split` marches - z = zb + w, zb + w + zw, ... < ze with zb = split * zchunk,
+ * ze = min(nz, zb + zchunk) - of which a lane keeps, in ascending order, those where its nibble of the bits is not zero.
+ * len[b * nsub + j] (uint32) is the longest lane's count, off[b * nsub + j] (uint64) the exclusive prefix sum of len in
+ * ENTRY ROWS.  An entry row is 64 x 16 bytes of samples (the lane's four floats exactly as they lie in the cube, the
+ * voxels the mask excludes among them) in d_samples and 64 x 4 bytes of meta (z | nibble << 28) in d_meta, both at row
+ * off + k.  Lanes shorter than len, and lanes past the last group, are padded with entries of zero samples and zero
+ * meta, which every kernel treats as a plane the mask excludes; every byte of rows [0, sum of len) is written.
+ * There is a list only for nz < 2^28, 16-byte lanes (what spc_mask_pack_bits asks for, and a cube whose address and
+ * strides are multiples of 4 elements) and the mask-first march (SPC_MOMENTS_MASK_FIRST not 0).
+ *   spc_moments_list_plan_f32   (host only, no device) fills desc with the plan spc_moments_list_f32 would launch for
+ *       these arguments, after its workspace fallback; SPC_ERR_UNSUPPORTED where there is no list.
+ *   spc_moments_list_count_f32  the same desc, and one kernel that reads ONLY the bits: d_len[b * nsub + j] as above and
+ *       d_lines[b * nsub + j] = the 128-byte cube lines the bits march fetches for that sublist (the non-zero 32-bit
+ *       words of its bits rows).  nsublists = entries of d_len and of d_lines, at least nblocks * nsub.
+ *   spc_moments_list_fill_f32   one wave per sublist marches its planes mask-first through the cube (with the strides
+ *       the call sees) and writes list->d_samples / d_meta from list->d_off / d_len, padding included.  Nothing is
+ *       written past row list->rows or past a sublist's len, whatever d_off / d_len hold.
+ *   spc_moments_list_f32        spc_moments_bits_f32 plus the list (NULL: exactly spc_moments_bits_f32).  The list is
+ *       read only if the call's plan equals list->desc, the bits are read, the buffers are large enough for
+ *       list->rows and SPC_MOMENTS_LIST is not 0; in every other case the call is spc_moments_bits_f32.  The maps are
+ *       bit-identical either way: a lane's included planes are added in the order of the march, and the planes left
+ *       out only added +0.0.
+ * The caller answers for the list being that of the cube's and the mask's present bytes: count and fill again after
+ * either changes.  (Added within ABI 8: nothing existing moved.) */
+typedef struct {
+    int32_t zw, nsplit;          /* waves per block (1, 4, 8) and z ranges of the launch plan */
+    int64_t zchunk;              /* planes per z range */
+    int64_t nblocks;             /* ceil(ny * (nx / 4) / 64) */
+    int64_t nsub;                /* sublists per block: nsplit * zw */
+} spc_moments_list_desc;
+typedef struct {
+    spc_moments_list_desc desc;
+    void* d_samples; size_t samples_bytes;       /* rows * 1024 bytes, 16-byte aligned */
+    void* d_meta; size_t meta_bytes;             /* rows * 256 bytes */
+    const uint64_t* d_off; const uint32_t* d_len; size_t nsublists;   /* >= desc.nblocks * desc.nsub entries each */
+    uint64_t rows;               /* sum of len */
+} spc_moments_list;
+int spc_moments_list_plan_f32(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out,
+                              const void* d_workspace, size_t workspace_bytes, spc_moments_list_desc* desc);
+int spc_moments_list_count_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                               const spc_moment_outputs* out, const void* d_workspace, size_t workspace_bytes,
+                               const void* d_mask_bits, size_t bits_bytes, uint32_t* d_len, uint32_t* d_lines,
+                               size_t nsublists, spc_moments_list_desc* desc);
+int spc_moments_list_fill_f32(int device, void* stream, const spc_cube_f32* cube, const void* d_mask_bits,
+                              size_t bits_bytes, const spc_moments_list* list);
+int spc_moments_list_f32(int device, void* stream, const spc_cube_f32* cube,
+                         const spc_mask* mask, const double* d_cen, double dv,
+                         double m1_add, const spc_moment_outputs* out,
+                         void* d_workspace, size_t workspace_bytes,
+                         const void* d_mask_bits, size_t bits_bytes, const spc_moments_list* list);
+
 /* general order N >= 2 second pass:  out = sum v*(c - mu)^N / S0
  * (dask_spectral_cube.py:1094-1099; _moments.py:185-193).  d_mu, d_s0 come
  * from spc_moments_f32. */

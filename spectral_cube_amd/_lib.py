@@ -93,6 +93,18 @@ class SpcMomentOutputs(C.Structure):
                 ("d_nvalid", C.c_void_p), ("out_row_stride", C.c_int64)]
 
 
+class SpcMomentsListDesc(C.Structure):
+    """spc_moments_list_desc: the launch plan a list is made for"""
+    _fields_ = [("zw", C.c_int32), ("nsplit", C.c_int32), ("zchunk", C.c_int64), ("nblocks", C.c_int64), ("nsub", C.c_int64)]
+
+
+class SpcMomentsList(C.Structure):
+    """spc_moments_list: the entry rows of the lane segments a mask includes (spc_moments_list_fill_f32 / spc_moments_list_f32)"""
+    _fields_ = [("desc", SpcMomentsListDesc), ("d_samples", C.c_void_p), ("samples_bytes", C.c_size_t),
+                ("d_meta", C.c_void_p), ("meta_bytes", C.c_size_t), ("d_off", C.c_void_p), ("d_len", C.c_void_p),
+                ("nsublists", C.c_size_t), ("rows", C.c_uint64)]
+
+
 class SpcMask64(C.Structure):
     """spc_mask_f64: the mask of a float64 cube (thresholds compared in float64)"""
     _fields_ = [("flags", C.c_uint32), ("thr_lo", C.c_double), ("thr_hi", C.c_double),
@@ -230,6 +242,12 @@ SIGNATURES = {
     "spc_mask_pack_bits": (_i, [_i, _vp, _i64, _i64, _i64, _P(SpcMask), _vp, _sz]),
     "spc_moments_bits_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
                                   _P(SpcMomentOutputs), _vp, _sz, _vp, _sz]),
+    "spc_moments_list_plan_f32": (_i, [_P(SpcCube), _P(SpcMask), _P(SpcMomentOutputs), _vp, _sz, _P(SpcMomentsListDesc)]),
+    "spc_moments_list_count_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _P(SpcMomentOutputs), _vp, _sz, _vp, _sz, _vp, _vp, _sz,
+                                        _P(SpcMomentsListDesc)]),
+    "spc_moments_list_fill_f32": (_i, [_i, _vp, _P(SpcCube), _vp, _sz, _P(SpcMomentsList)]),
+    "spc_moments_list_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
+                                  _P(SpcMomentOutputs), _vp, _sz, _vp, _sz, _P(SpcMomentsList)]),
     "spc_moment_order_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _i, _vp, _vp, _vp, _i64]),
     # (spc_cube_f64 has the layout of spc_cube_f32: a pointer and five int64)
     "spc_moments_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _vp, _d, _d, _P(SpcMomentOutputs64)]),

@@ -35,6 +35,7 @@
 namespace {
 
 constexpr int kLanes = 64;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct MomArgs {
     const float* cube;
@@ -51,6 +52,12 @@ struct MomArgs {
     double* ws;              // partial sums workspace (nsplit > 1)
     float lim, lo, hi;       // the mask predicate in canonical form: |v| <= lim && !(v <= lo) && !(v >= hi)
     int xcd_group;           // blocks of one XCD take neighbouring column groups
+    // the LIST forms only (include/spcube_hip.h, spc_moments_list_*): the entry rows of the included lane segments
+    const f32x4* list_samples;      // [rows][64] the lane's four samples
+    const uint32_t* list_meta;      // [rows][64] z | nibble << 28
+    const uint64_t* list_off;       // [nblocks * nsplit * ZW] first entry row of a sublist
+    const uint32_t* list_len;       // [nblocks * nsplit * ZW] its entry rows
+    uint64_t list_rows;             // rows the two arrays hold
 };
 
 // per-column running state
@@ -149,7 +156,6 @@ __device__ __forceinline__ void ws_load(const MomArgs& A, Acc& a, int split, int
     a.bmin = __int_as_float((int)(p >> 32)); a.imin = (int)(p & 0xffffffffLL);
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int VEC> struct VecT;
 template <> struct VecT<4> { using F = f32x4; using M = uint32_t; };   // 4 mask bytes in one dword
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -173,10 +179,19 @@ __device__ __forceinline__ unsigned vget(const unsigned char& v, int) { return v
 // instead of its four mask bytes: one unsigned-byte load from bits + (blk * nz + z) * 32 + (lane >> 1), an eighth of the mask's
 // bytes.  "Nothing included" is nibble == 0 and voxel i is bit i; the batch of masks one ahead, the wait for all of them, the
 // carried pointers, the tail, acc_add and the combine are the same statements, so the maps are those of the byte form bit for bit.
-template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false, bool BITS = false>
+//
+// LIST (BITS only): the loader alone differs.  The wave walks the entry rows of its sublist (layout: include/spcube_hip.h,
+// spc_moments_list_*): U rows in flight, the metas and the samples of a batch back to back, all coalesced and unconditional.
+// An entry is a plane of the lane that the bits include, with its nibble; the planes a lane's sublist leaves out are those for
+// which the march adds +0.0 to every sum with ok false, which changes neither a sum (they start at +0.0 and round-to-nearest
+// never makes -0.0 of these additions) nor the count, the any-valid bit or the extrema; a lane's entries keep the order of the
+// march, and padding entries (meta 0, samples 0) are excluded planes.  So the maps are those of the march bit for bit.  The
+// channel coordinate is a per-lane load (the lanes of a row hold different planes); cen is nz doubles and stays in the caches.
+template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false, bool BITS = false, bool LIST = false>
 __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     static_assert(!MF || (ARR && VEC == 4), "mask-first is the 16-byte lane form with a mask array");
     static_assert(!BITS || MF, "the packed mask is read by the mask-first forms only");
+    static_assert(!LIST || BITS, "the list holds what the packed mask includes");
     using F = typename VecT<VEC>::F;
     using M = typename VecT<VEC>::M;
     const int lane = threadIdx.x;
@@ -213,7 +228,50 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     if (live) {
         int64_t z = zb + w;
         // main loop: U planes (stride ZW) in flight per lane
-        if constexpr (MF) {
+        if constexpr (LIST) {
+            // one entry of a lane: add_plane of the march below, with the lane's own plane number and coordinate (a plane number
+            // past the cube, which no filled list holds, reads the last coordinate instead of memory that is not cen's)
+            auto add_entry = [&](const F& v, uint32_t mt) {
+                const int zz = (int)min((int64_t)(mt & 0x0fffffffu), A.nz - 1);
+                const uint32_t m = mt >> 28;
+                const double c = A.cen[zz];
+                const double c2 = c * c;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const float val = vget(v, i);
+                    bool ok = mom_pred<PRED>(val, lim, lo, hi);
+                    ok = ok && ((m >> i) & 1u) != 0;
+                    acc_add<EXT>(acc[i], val, ok, c, c2, zz);
+                }
+            };
+            // the sublist of this wave: wave-uniform indices, scalar loads
+            typedef const uint64_t __attribute__((address_space(4))) cu64;
+            typedef const uint32_t __attribute__((address_space(4))) cu32;
+            const int64_t sub = (blk * A.nsplit + split) * ZW + w;
+            const uint64_t row = ((cu64*)A.list_off)[sub];
+            uint32_t n = ((cu32*)A.list_len)[sub];
+            if (row + n > A.list_rows) n = 0;                    // never past the arrays, whatever off and len hold
+            typedef const F __attribute__((address_space(1))) GF;
+            typedef const uint32_t __attribute__((address_space(1))) GU;
+            GF* ps = (GF*)A.list_samples + row * kLanes + lane;
+            GU* pq = (GU*)A.list_meta + row * kLanes + lane;
+            uint32_t k = 0;
+            for (; k + U <= n; k += U, ps += U * kLanes, pq += U * kLanes) {
+                uint32_t mt[U];
+                F v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) mt[u] = __builtin_nontemporal_load(pq + u * kLanes);
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(ps + u * kLanes);
+#pragma unroll
+                for (int u = 0; u < U; ++u) add_entry(v[u], mt[u]);
+            }
+            for (; k < n; ++k, ps += kLanes, pq += kLanes) {
+                const uint32_t mt = *pq;
+                const F v = *ps;
+                add_entry(v, mt);
+            }
+        } else if constexpr (MF) {
             // one plane of a lane: its VEC samples and mask bytes into the sums
             auto add_plane = [&](const F& v, const M& m, int64_t zz) {
                 const double c = cenp[zz];                           // uniform index: a scalar load
@@ -508,10 +566,11 @@ __global__ __launch_bounds__(256) void moment_order_v4_kernel(const OrdArgs A) {
     }
 }
 
-struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; };   // bits: the packed mask array, or nullptr
+// bits: the packed mask array, or nullptr; list_u: 0, or the rows in flight of the LIST form that reads A.list_* (4 or 8)
+struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; int list_u; };
 
 template <int VEC, int ZW, int U, bool ARR, int EXT>
-int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits) {
+int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits, int list_u) {
     dim3 block(kLanes, ZW);
     dim3 grid((unsigned)((A.ngroups + kLanes - 1) / kLanes), (unsigned)A.nsplit);
     if constexpr (ARR && VEC == 4) {
@@ -520,6 +579,18 @@ int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_fir
             // layout (and every other instantiation the instructions) they had
             MomArgs B = A;
             B.mask.arr = bits;
+            if (list_u) {
+                // the LIST forms: the plan's ZW and split with a batch of their own (U counts planes in the march, rows here)
+                if (list_u == 8) {
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, true>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, true>), grid, block, 0, st, B);
+                } else {
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 1, true, true, true>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 0, true, true, true>), grid, block, 0, st, B);
+                }
+                SPC_LAUNCH_CHECK();
+                return SPC_OK;
+            }
             if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true, true>), grid, block, 0, st, B);
             else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true, true>), grid, block, 0, st, B);
             SPC_LAUNCH_CHECK();
@@ -554,24 +625,25 @@ template <bool ARR, int EXT>
 int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     if (p.vec == 4) {
         switch (p.zw * 16 + p.u) {
-            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
         }
     }
-    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
-    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits);
+    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
 }
 
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     Plan p;
     p.bits = nullptr;
+    p.list_u = 0;
     auto aligned = [&](int v) {
         const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
         return (c->nx % v == 0) && (c->row_stride % v == 0) && (c->plane_stride % v == 0) &&
@@ -667,6 +739,238 @@ size_t mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx) {
     return (size_t)((ngroups + kLanes - 1) / kLanes) * (size_t)nz * 32;
 }
 
+// ---- the list of included lane segments (layout: include/spcube_hip.h) -----------------------------------------
+// One wave per sublist s = b * nsub + j, j = split * zw + w: it marches the planes wave w of split `split` of block b marches
+// in moments_kernel, reading the lane's nibble of the bits as the BITS form does.
+struct ListArgs {
+    const uint8_t* bits;
+    int64_t nz, zchunk, nsub, total;   // total = nblocks * nsub
+    int zw;
+    uint32_t* len;                     // count: the longest lane's included planes ...
+    uint32_t* lines;                   // ... and the non-zero 32-bit words of the sublist's bits rows
+    const float* cube;                 // fill
+    int64_t row_stride, plane_stride, groups_per_row, ngroups;
+    const uint64_t* off;
+    const uint32_t* flen;
+    f32x4* samples;
+    uint32_t* meta;
+    uint64_t rows;
+};
+
+constexpr int kListWaves = 4;          // sublists per block of the count and fill kernels
+constexpr int kListBatch = 8;          // planes in flight per lane
+
+__global__ __launch_bounds__(kLanes * kListWaves) void list_count_kernel(const ListArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (s >= A.total) return;                                        // wave-uniform
+    const int64_t b = s / A.nsub;
+    const int j = (int)(s - b * A.nsub);
+    const int split = j / A.zw, w = j - split * A.zw;
+    const int64_t zb = (int64_t)split * A.zchunk;
+    const int64_t ze = min(A.nz, zb + A.zchunk);
+    const uint8_t* q = A.bits + b * A.nz * 32 + (lane >> 1);
+    const int sh = (lane & 1) * 4;
+    uint32_t cnt = 0, lines = 0;
+    auto take = [&](uint32_t byte) {
+        const bool inc = ((byte >> sh) & 0xfu) != 0;
+        cnt += inc ? 1u : 0u;
+        // eight lanes share a 32-bit word of the bits and a 128-byte line of the cube: bit 0 of every byte of the ballot after the folds
+        unsigned long long any = __ballot(inc);
+        any |= any >> 1;
+        any |= any >> 2;
+        any |= any >> 4;
+        lines += (uint32_t)__popcll(any & 0x0101010101010101ULL);
+    };
+    int64_t z = zb + w;
+    for (; z + (int64_t)(kListBatch - 1) * A.zw < ze; z += (int64_t)kListBatch * A.zw) {
+        uint32_t byte[kListBatch];
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) byte[u] = q[(z + (int64_t)u * A.zw) * 32];
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) take(byte[u]);
+    }
+    for (; z < ze; z += A.zw) take(q[z * 32]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt = max(cnt, (uint32_t)__shfl_xor((int)cnt, o));
+    if (lane == 0) {
+        A.len[s] = cnt;
+        A.lines[s] = lines;
+    }
+}
+
+__global__ __launch_bounds__(kLanes * kListWaves) void list_fill_kernel(const ListArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (s >= A.total) return;                                        // wave-uniform
+    const int64_t b = s / A.nsub;
+    const int j = (int)(s - b * A.nsub);
+    const int split = j / A.zw, w = j - split * A.zw;
+    const int64_t zb = (int64_t)split * A.zchunk;
+    const int64_t ze = min(A.nz, zb + A.zchunk);
+    const int64_t g = b * kLanes + lane;
+    const bool live = g < A.ngroups;                                 // dead lanes load nothing and hold only padding
+    const int64_t gg = live ? g : 0;
+    const int64_t y = gg / A.groups_per_row;
+    const int64_t x = (gg - y * A.groups_per_row) * 4;
+    const float* p = A.cube + y * A.row_stride + x;
+    const uint8_t* q = A.bits + b * A.nz * 32 + (lane >> 1);
+    const int sh = (lane & 1) * 4;
+    // the rows of this sublist, cut to what the arrays hold whatever off and len say
+    const uint64_t row0 = A.off[s];
+    uint32_t n = A.flen[s];
+    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
+    if (n > room) n = (uint32_t)room;
+    f32x4* ps = A.samples + row0 * kLanes + lane;
+    uint32_t* pq = A.meta + row0 * kLanes + lane;
+    uint32_t k = 0;                                                  // the lane's own running index
+    auto put = [&](const f32x4& v, uint32_t nib, int64_t z) {
+        if (nib != 0 && k < n) {
+            ps[(uint64_t)k * kLanes] = v;
+            pq[(uint64_t)k * kLanes] = (uint32_t)z | (nib << 28);
+            ++k;
+        }
+    };
+    int64_t z = zb + w;
+    for (; z + (int64_t)(kListBatch - 1) * A.zw < ze; z += (int64_t)kListBatch * A.zw) {
+        uint32_t nib[kListBatch];
+        f32x4 v[kListBatch];
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) nib[u] = live ? (uint32_t)(q[(z + (int64_t)u * A.zw) * 32] >> sh) & 0xfu : 0u;
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) {
+            v[u] = f32x4{};
+            if (nib[u] != 0) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + (z + (int64_t)u * A.zw) * A.plane_stride));
+        }
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) put(v[u], nib[u], z + (int64_t)u * A.zw);
+    }
+    for (; z < ze; z += A.zw) {
+        const uint32_t nib = live ? (uint32_t)(q[z * 32] >> sh) & 0xfu : 0u;
+        f32x4 v{};
+        if (nib != 0) v = *reinterpret_cast<const f32x4*>(p + z * A.plane_stride);
+        put(v, nib, z);
+    }
+    // padding: samples 0, meta 0 - a plane the mask excludes
+    for (; k < n; ++k) {
+        ps[(uint64_t)k * kLanes] = f32x4{};
+        pq[(uint64_t)k * kLanes] = 0u;
+    }
+}
+
+constexpr int64_t kListMaxNz = 1LL << 28;      // z shares its meta word with the nibble
+
+// what every moments entry works out before it launches: the checks, the kernel arguments, the plan after the workspace
+// fallback and whether the launch reads the packed mask
+int moments_setup(const spc_cube_f32* cube, const spc_mask* mask, const double* d_cen, bool need_cen, double dv, double m1_add,
+                  const spc_moment_outputs* out, const void* d_workspace, size_t workspace_bytes,
+                  const void* d_mask_bits, size_t bits_bytes, MomArgs& A, Plan& p) {
+    int rc = spc_check_cube(cube);
+    if (rc) return rc;
+    SPC_REQUIRE(out != nullptr, "outputs struct is NULL");
+    SPC_REQUIRE(!need_cen || d_cen != nullptr, "d_cen is NULL");
+    SPC_REQUIRE(cube->nz < (1LL << 31), "nz too large");
+    rc = spc_mask_to_dev(mask, cube, &A.mask);
+    if (rc) return rc;
+    A.cube = cube->d_data;
+    A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
+    A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
+    A.cen = d_cen; A.dv = dv; A.m1_add = m1_add;
+    A.out = *out;
+    A.out_row_stride = out->out_row_stride ? out->out_row_stride : cube->nx;
+    const bool ext = out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin;
+    p = make_plan(cube, A.mask, ext);
+    spc_canonical_pred(A.mask.flags, A.mask.thr_lo, A.mask.thr_hi, &A.lim, &A.lo, &A.hi);
+    A.xcd_group = spc_switch("SPC_MOMENTS_XCD", 0);    // measured: +- 1 % either way on the real kernel (profiles/r04_moments_issue.log)
+    A.groups_per_row = cube->nx / p.vec;
+    A.ngroups = cube->ny * A.groups_per_row;
+    A.nsplit = p.nsplit;
+    A.zchunk = p.zchunk;
+    A.ws = (double*)d_workspace;
+    if (p.nsplit > 1) {
+        const size_t need = (size_t)p.nsplit * kWsFields * sizeof(double) * (size_t)(cube->ny * cube->nx);
+        if (!d_workspace || workspace_bytes < need) {
+            // not enough workspace: fall back to a single z range (still correct)
+            A.nsplit = 1; A.zchunk = cube->nz; p.nsplit = 1; p.zchunk = cube->nz;
+        }
+    }
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    // the packed mask only where the launch is the mask-first march of 16-byte lanes; everything else reads the bytes as before
+    p.bits = nullptr;
+    if (d_mask_bits && arr && p.vec == 4 && p.mask_first && spc_switch("SPC_MOMENTS_MASK_BITS", 1) != 0) {
+        const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
+        if (need && bits_bytes >= need) p.bits = (const uint8_t*)d_mask_bits;
+    }
+    return SPC_OK;
+}
+
+// the plan of a launch as a list is made for it
+spc_moments_list_desc list_desc(const MomArgs& A, const Plan& p) {
+    spc_moments_list_desc d;
+    d.zw = p.zw; d.nsplit = A.nsplit; d.zchunk = A.zchunk;
+    d.nblocks = (A.ngroups + kLanes - 1) / kLanes;
+    d.nsub = (int64_t)A.nsplit * p.zw;
+    return d;
+}
+
+// there is a list for this launch: the march of 16-byte lanes over the packed mask (have_bits: the bits were given and are
+// read; without them the same conditions on the plan alone), short enough for z to share a word with the nibble
+int list_exists(const MomArgs& A, const Plan& p, bool have_bits, const char* who) {
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    if (!arr || p.vec != 4 || !p.mask_first || A.nz >= kListMaxNz || (have_bits && !p.bits) ||
+        spc_switch("SPC_MOMENTS_MASK_BITS", 1) == 0 || spc_switch("SPC_MOMENTS_LIST", 1) == 0) {
+        spc_set_error("%s: no list for this launch (it needs a mask array read as bits by the mask-first march of 16-byte lanes, "
+                      "nz < 2^28 and SPC_MOMENTS_LIST not 0)", who);
+        return SPC_ERR_UNSUPPORTED;
+    }
+    return SPC_OK;
+}
+
+int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, const double* d_cen, double dv, double m1_add,
+                const spc_moment_outputs* out, void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
+                const spc_moments_list* list) {
+    MomArgs A{};
+    Plan p;
+    int rc = moments_setup(cube, mask, d_cen, true, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
+    if (rc) return rc;
+    SPC_DEVICE(device);
+    const bool ext = out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin;
+    const bool thr = (A.mask.flags & (SPC_MASK_GT | SPC_MASK_GE | SPC_MASK_LT | SPC_MASK_LE)) != 0;
+    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    // the list only where it was made for exactly this plan and its arrays hold the rows it names; otherwise the bits march
+    if (list && p.bits && A.nz < kListMaxNz && spc_switch("SPC_MOMENTS_LIST", 1) != 0) {
+        const spc_moments_list_desc d = list_desc(A, p);
+        const spc_moments_list_desc& l = list->desc;
+        const bool same = d.zw == l.zw && d.nsplit == l.nsplit && d.zchunk == l.zchunk && d.nblocks == l.nblocks && d.nsub == l.nsub;
+        if (same && list->d_samples && list->d_meta && list->d_off && list->d_len && list->nsublists >= (size_t)(d.nblocks * d.nsub) &&
+            list->samples_bytes / 1024 >= list->rows && list->meta_bytes / 256 >= list->rows &&
+            spc_aligned(list->d_samples, 16) && spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4)) {
+            A.list_samples = (const f32x4*)list->d_samples;
+            A.list_meta = (const uint32_t*)list->d_meta;
+            A.list_off = list->d_off;
+            A.list_len = list->d_len;
+            A.list_rows = list->rows;
+            // rows in flight per lane (profiles/moments_list_bench.txt)
+            p.list_u = spc_switch("SPC_MOMENTS_LIST_U", ext ? 4 : 8) == 4 ? 4 : 8;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int what = ext ? kExtrema : (out->d_nvalid ? kCount : kSums);
+    if (arr) rc = what == kExtrema ? launch_plan<true, kExtrema>(A, st, p, thr)
+                : what == kCount ? launch_plan<true, kCount>(A, st, p, thr) : launch_plan<true, kSums>(A, st, p, thr);
+    else rc = what == kExtrema ? launch_plan<false, kExtrema>(A, st, p, thr)
+            : what == kCount ? launch_plan<false, kCount>(A, st, p, thr) : launch_plan<false, kSums>(A, st, p, thr);
+    if (rc) return rc;
+    if (A.nsplit > 1) {
+        const int64_t ncols = cube->ny * cube->nx;
+        dim3 grid((unsigned)((ncols + 255) / 256));
+        if (ext) hipLaunchKernelGGL(moments_combine_kernel<kExtrema>, grid, dim3(256), 0, st, A, p.vec);
+        else hipLaunchKernelGGL(moments_combine_kernel<kCount>, grid, dim3(256), 0, st, A, p.vec);
+        SPC_LAUNCH_CHECK();
+    }
+    return SPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -723,59 +1027,98 @@ int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const sp
 int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                          const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                          void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes) {
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, nullptr);
+}
+
+int spc_moments_list_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                         const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
+                         void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
+                         const spc_moments_list* list) {
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list);
+}
+
+int spc_moments_list_plan_f32(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out,
+                              const void* d_workspace, size_t workspace_bytes, spc_moments_list_desc* desc) {
+    SPC_REQUIRE(desc != nullptr, "desc is NULL");
+    MomArgs A{};
+    Plan p;
+    int rc = moments_setup(cube, mask, nullptr, false, 0.0, 0.0, out, d_workspace, workspace_bytes, nullptr, 0, A, p);
+    if (rc) return rc;
+    rc = list_exists(A, p, false, "spc_moments_list_plan_f32");
+    if (rc) return rc;
+    *desc = list_desc(A, p);
+    return SPC_OK;
+}
+
+int spc_moments_list_count_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                               const spc_moment_outputs* out, const void* d_workspace, size_t workspace_bytes,
+                               const void* d_mask_bits, size_t bits_bytes, uint32_t* d_len, uint32_t* d_lines,
+                               size_t nsublists, spc_moments_list_desc* desc) {
+    SPC_REQUIRE(desc != nullptr, "desc is NULL");
+    SPC_REQUIRE(d_mask_bits != nullptr, "d_mask_bits is NULL");
+    SPC_REQUIRE(d_len != nullptr && d_lines != nullptr, "d_len or d_lines is NULL");
+    MomArgs A{};
+    Plan p;
+    int rc = moments_setup(cube, mask, nullptr, false, 0.0, 0.0, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
+    if (rc) return rc;
+    rc = list_exists(A, p, true, "spc_moments_list_count_f32");
+    if (rc) return rc;
+    const spc_moments_list_desc d = list_desc(A, p);
+    const int64_t total = d.nblocks * d.nsub;
+    SPC_REQUIRE(nsublists >= (size_t)total, "d_len and d_lines too small: %zu entries given, %lld sublists", nsublists, (long long)total);
+    SPC_REQUIRE(spc_aligned(d_len, 4) && spc_aligned(d_lines, 4), "d_len and d_lines must be 4-byte aligned");
+    SPC_REQUIRE((total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
+    *desc = d;
+    SPC_DEVICE(device);
+    ListArgs L{};
+    L.bits = p.bits; L.nz = A.nz; L.zchunk = d.zchunk; L.nsub = d.nsub; L.total = total; L.zw = d.zw;
+    L.len = d_len; L.lines = d_lines;
+    hipLaunchKernelGGL(list_count_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
+                       (hipStream_t)stream, L);
+    SPC_LAUNCH_CHECK();
+    return SPC_OK;
+}
+
+int spc_moments_list_fill_f32(int device, void* stream, const spc_cube_f32* cube, const void* d_mask_bits, size_t bits_bytes,
+                              const spc_moments_list* list) {
     int rc = spc_check_cube(cube);
     if (rc) return rc;
-    SPC_REQUIRE(out != nullptr, "outputs struct is NULL");
-    SPC_REQUIRE(d_cen != nullptr, "d_cen is NULL");
-    SPC_REQUIRE(cube->nz < (1LL << 31), "nz too large");
-    MomArgs A{};
-    rc = spc_mask_to_dev(mask, cube, &A.mask);
-    if (rc) return rc;
+    SPC_REQUIRE(list != nullptr, "list is NULL");
+    SPC_REQUIRE(d_mask_bits != nullptr, "d_mask_bits is NULL");
+    SPC_REQUIRE(cube->nz < kListMaxNz, "nz too large for a list (%lld)", (long long)cube->nz);
+    // 16-byte lanes: make_plan's aligned(4) for the cube
+    if (cube->nx % 4 != 0 || cube->row_stride % 4 != 0 || cube->plane_stride % 4 != 0 || !spc_aligned(cube->d_data, 16)) {
+        spc_set_error("spc_moments_list_fill_f32: nx, the cube's strides and its address must be multiples of 4 elements");
+        return SPC_ERR_UNSUPPORTED;
+    }
+    const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
+    SPC_REQUIRE(need && bits_bytes >= need, "d_mask_bits too small: %zu bytes given, %zu needed (spc_mask_bits_bytes)", bits_bytes, need);
+    const spc_moments_list_desc& d = list->desc;
+    const int64_t ngroups = cube->ny * (cube->nx / 4);
+    SPC_REQUIRE((d.zw == 1 || d.zw == 4 || d.zw == 8) && d.nsplit >= 1 && d.zchunk >= 1 && d.nsub == (int64_t)d.nsplit * d.zw &&
+                d.nblocks == (ngroups + kLanes - 1) / kLanes, "desc is not a launch plan of this cube");
+    // the splits cover [0, nz) and none of them is empty
+    SPC_REQUIRE(d.zchunk <= cube->nz && (int64_t)(d.nsplit - 1) * d.zchunk < cube->nz && (int64_t)d.nsplit * d.zchunk >= cube->nz,
+                "desc: %d splits of %lld planes do not cover %lld planes", d.nsplit, (long long)d.zchunk, (long long)cube->nz);
+    const int64_t total = d.nblocks * d.nsub;
+    SPC_REQUIRE(list->d_off != nullptr && list->d_len != nullptr && list->nsublists >= (size_t)total,
+                "d_off and d_len: %zu entries given, %lld sublists", list->nsublists, (long long)total);
+    SPC_REQUIRE(list->rows == 0 || (list->d_samples != nullptr && list->d_meta != nullptr), "d_samples or d_meta is NULL");
+    SPC_REQUIRE(list->samples_bytes / 1024 >= list->rows && list->meta_bytes / 256 >= list->rows,
+                "d_samples / d_meta too small for %llu rows (1024 and 256 bytes each)", (unsigned long long)list->rows);
+    SPC_REQUIRE(spc_aligned(list->d_samples, 16) && spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4),
+                "d_samples must be 16-byte, d_off 8-byte, d_meta and d_len 4-byte aligned");
+    SPC_REQUIRE((total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
     SPC_DEVICE(device);
-    A.cube = cube->d_data;
-    A.nz = cube->nz; A.ny = cube->ny; A.nx = cube->nx;
-    A.row_stride = cube->row_stride; A.plane_stride = cube->plane_stride;
-    A.cen = d_cen; A.dv = dv; A.m1_add = m1_add;
-    A.out = *out;
-    A.out_row_stride = out->out_row_stride ? out->out_row_stride : cube->nx;
-    const bool ext = out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin;
-    Plan p = make_plan(cube, A.mask, ext);
-    spc_canonical_pred(A.mask.flags, A.mask.thr_lo, A.mask.thr_hi, &A.lim, &A.lo, &A.hi);
-    const bool thr = (A.mask.flags & (SPC_MASK_GT | SPC_MASK_GE | SPC_MASK_LT | SPC_MASK_LE)) != 0;
-    A.xcd_group = spc_switch("SPC_MOMENTS_XCD", 0);    // measured: +- 1 % either way on the real kernel (profiles/r04_moments_issue.log)
-    A.groups_per_row = cube->nx / p.vec;
-    A.ngroups = cube->ny * A.groups_per_row;
-    A.nsplit = p.nsplit;
-    A.zchunk = p.zchunk;
-    A.ws = (double*)d_workspace;
-    if (p.nsplit > 1) {
-        const size_t need = (size_t)p.nsplit * kWsFields * sizeof(double) * (size_t)(cube->ny * cube->nx);
-        if (!d_workspace || workspace_bytes < need) {
-            // not enough workspace: fall back to a single z range (still correct)
-            A.nsplit = 1; A.zchunk = cube->nz; p.nsplit = 1;
-        }
-    }
-    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
-    // the packed mask only where the launch is the mask-first march of 16-byte lanes; everything else reads the bytes as before
-    p.bits = nullptr;
-    if (d_mask_bits && arr && p.vec == 4 && p.mask_first && spc_switch("SPC_MOMENTS_MASK_BITS", 1) != 0) {
-        const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
-        if (need && bits_bytes >= need) p.bits = (const uint8_t*)d_mask_bits;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int what = ext ? kExtrema : (out->d_nvalid ? kCount : kSums);
-    if (arr) rc = what == kExtrema ? launch_plan<true, kExtrema>(A, st, p, thr)
-                : what == kCount ? launch_plan<true, kCount>(A, st, p, thr) : launch_plan<true, kSums>(A, st, p, thr);
-    else rc = what == kExtrema ? launch_plan<false, kExtrema>(A, st, p, thr)
-            : what == kCount ? launch_plan<false, kCount>(A, st, p, thr) : launch_plan<false, kSums>(A, st, p, thr);
-    if (rc) return rc;
-    if (A.nsplit > 1) {
-        const int64_t ncols = cube->ny * cube->nx;
-        dim3 grid((unsigned)((ncols + 255) / 256));
-        if (ext) hipLaunchKernelGGL(moments_combine_kernel<kExtrema>, grid, dim3(256), 0, st, A, p.vec);
-        else hipLaunchKernelGGL(moments_combine_kernel<kCount>, grid, dim3(256), 0, st, A, p.vec);
-        SPC_LAUNCH_CHECK();
-    }
+    ListArgs L{};
+    L.bits = (const uint8_t*)d_mask_bits; L.nz = cube->nz; L.zchunk = d.zchunk; L.nsub = d.nsub; L.total = total; L.zw = d.zw;
+    L.cube = cube->d_data; L.row_stride = cube->row_stride; L.plane_stride = cube->plane_stride;
+    L.groups_per_row = cube->nx / 4; L.ngroups = ngroups;
+    L.off = list->d_off; L.flen = list->d_len;
+    L.samples = (f32x4*)list->d_samples; L.meta = (uint32_t*)list->d_meta; L.rows = list->rows;
+    hipLaunchKernelGGL(list_fill_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
+                       (hipStream_t)stream, L);
+    SPC_LAUNCH_CHECK();
     return SPC_OK;
 }
 

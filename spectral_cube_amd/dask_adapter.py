@@ -142,6 +142,7 @@ def _stage(chunk, device):
     ptr = st.pinned(n * 4)
     view = np.frombuffer((C.c_byte * (n * 4)).from_address(ptr), dtype=np.float32, count=n).reshape(chunk.shape)
     dev = st.buffer("in", chunk.shape, np.float32)
+    dev.mark_written()                                       # the thread's buffer, refilled by raw copies below
     nz = chunk.shape[0] if chunk.ndim == 3 else 0
     plane = n // nz if nz else 0
     pieces = min(8, nz, (n * 4) >> 24) if nz else 0          # runs of >= 16 MiB

@@ -27,7 +27,17 @@ class MaskSpec:
     operator of this package that writes into a caller-given array advance it), so a mask rewritten that way is packed
     again after two more uses.  Bytes changed behind the library's back - through the raw pointer, by a kernel of the
     caller's - after a spec has been used twice need invalidate().  rows(), planes() and swap01() return specs of their
-    own, which pack for themselves on their second use."""
+    own, which pack for themselves on their second use.
+
+    A spec that is used again ON THE SAME CUBE goes one step further: the launch that finds the bits packed and the cube of
+    the launch before it (normally the third use) builds the list of the cube's 16-byte lane segments that the bits
+    include (spc_moments_list_*: include/spcube_hip.h) and later launches with the same launch plan read that list instead
+    of marching the cube - where the list is at most half of the bytes the march fetches; otherwise it is refused, once,
+    and the march goes on.  The list costs 1280 bytes of HBM per entry row (about 14 GB for a 4096 x 2048 x 2048 cube under
+    a 4 % mask) and lives as long as the spec.  It is keyed by the bits' key and the cube's root array BY IDENTITY, its
+    address, shape, strides and write generation: another cube, upload() into the cube or an operator of this package
+    writing into it (out=, scale_inplace) drop the list, and only the list.  SAMPLES changed behind the library's back
+    after a spec's second use on the cube need invalidate() just as mask bytes do.  SPC_MOMENTS_LIST=0 turns the list off."""
     flags: int = 0
     thr_lo: float = 0.0
     thr_hi: float = 0.0
@@ -37,10 +47,16 @@ class MaskSpec:
     _bits_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)
     _bits_uses: int = field(default=0, init=False, compare=False, repr=False)
     _bits_failed: bool = field(default=False, init=False, compare=False, repr=False)   # no form / no memory: stay with the bytes
+    # the list of the lane segments the bits include in ONE cube (moments(), _moments_list): beside the bits, under their lock
+    _list: Optional[object] = field(default=None, init=False, compare=False, repr=False)
+    _list_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)      # the cube of the launch before
+    _list_root: Optional[object] = field(default=None, init=False, compare=False, repr=False)    # weakref to that cube's root array
+    _list_failed: bool = field(default=False, init=False, compare=False, repr=False)   # refused / no form / no memory: the bits march
 
     def invalidate(self):
-        """forget the packed form of the array term and start counting uses again: after the array's bytes were changed by
-        something other than upload() or an operator of this package"""
+        """forget the packed form of the array term and the list made from it, and start counting uses again: after the
+        array's bytes - or the samples of the cube a list was made of - were changed by something other than upload() or an
+        operator of this package"""
         with _bits_lock:
             self._drop_bits()
 
@@ -49,6 +65,13 @@ class MaskSpec:
         self._bits_key = None
         self._bits_uses = 0
         self._bits_failed = False
+        self._drop_list()                    # the list holds what THESE bits include
+
+    def _drop_list(self):
+        self._list = None
+        self._list_key = None
+        self._list_root = None
+        self._list_failed = False
 
     def to_c(self, wide=False):
         """spc_mask_f32, or (*wide*) spc_mask_f64: the thresholds as they are (a float64 cube is compared in float64)"""
@@ -102,8 +125,9 @@ def _switch_on(name, dflt=1):
 
 
 def _written(a):
-    """the operator has queued a write into *a*, a 1-byte array the caller may have given (or None): a MaskSpec that has
-    packed its bytes packs them again (DeviceArray.mark_written; arrays that are no DeviceArray keep no count)"""
+    """the operator has queued a write into *a*, an array the caller may have given (or None): a MaskSpec that has packed
+    its bytes packs them again, and one that holds the list of a cube's included samples builds it again
+    (DeviceArray.mark_written; arrays that are no DeviceArray keep no count)"""
     mark = getattr(a, "mark_written", None)
     if mark is not None:
         mark()
@@ -143,6 +167,87 @@ def _mask_bits(mask, stream):
             return None
         mask._bits = bits
         return bits
+
+
+class _MomentsList:
+    """the device arrays of one list (spc_moments_list: include/spcube_hip.h) and the struct that names them"""
+
+    def __init__(self, desc, off, length, samples, meta, rows):
+        self.desc, self.off, self.len, self.samples, self.meta, self.rows = desc, off, length, samples, meta, int(rows)
+        c = self.c = _lib.SpcMomentsList()
+        c.desc = desc
+        c.d_samples, c.samples_bytes = samples.ptr, samples.nbytes
+        c.d_meta, c.meta_bytes = meta.ptr, meta.nbytes
+        c.d_off, c.d_len, c.nsublists = off.ptr, length.ptr, int(desc.nblocks * desc.nsub)
+        c.rows = self.rows
+
+    @property
+    def nbytes(self):
+        return self.rows * 1280
+
+
+def list_is_kept(rows, lines, nblocks, nz):
+    """the list is built only where it reads at most half of what the bits march fetches: 1280 bytes per entry row against
+    128 per fetched cube line and 32 of bits per block and plane.  A condition, not a tuning result: all-ones and dense
+    random masks stay with the march"""
+    return 2 * 1280 * int(rows) <= 128 * int(lines) + 32 * int(nblocks) * int(nz)
+
+
+def _cube_key(cube):
+    nz, ny, nx = cube.shape
+    return (cube.ptr, cube.shape, getattr(cube, "row_stride", nx), getattr(cube, "plane_stride", ny * nx), cube.write_generation)
+
+
+def _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws):
+    """the list of *cube*'s lane segments that *mask*'s bits include, or None.  Nothing changes for a spec's first two uses:
+    the list is built by the first launch that finds the bits already packed (*had_bits*) and the cube of the launch before
+    it - the same root array BY IDENTITY (a weak reference: a freed cube whose address a new array reuses never matches),
+    pointer, shape, strides and write generation - and then handed out until that key or the bits' changes.  The launch
+    that builds counts on *stream*, reads the counts back (one stream sync, as the bits pack has), forms the offsets on the
+    host, allocates, fills, and uses the list.  A refusal (list_is_kept), a launch that has no list and a failed
+    allocation are remembered on the spec and are silent: the bits march goes on."""
+    import weakref
+    if mask is None or mask.array is None:
+        return None
+    root = cube._root() if isinstance(cube, DeviceArray) else None
+    if root is None:
+        return None
+    key = (mask._bits_key,) + _cube_key(cube)
+    with _bits_lock:
+        same = mask._list_key == key and mask._list_root is not None and mask._list_root() is root
+        if not same:
+            mask._drop_list()
+            mask._list_key, mask._list_root = key, weakref.ref(root)
+            return None
+        if mask._list is not None or mask._list_failed:
+            return mask._list
+        if bits is None or not had_bits or not _switch_on("SPC_MOMENTS_LIST"):
+            return None
+        try:
+            desc = _lib.SpcMomentsListDesc()
+            wsp, wsn = C.c_void_p(ws.ptr if ws is not None else 0), ws.nbytes if ws is not None else 0
+            _lib.call("spc_moments_list_plan_f32", C.byref(c), C.byref(m), C.byref(o), wsp, wsn, C.byref(desc))
+            n = int(desc.nblocks * desc.nsub)
+            d_len, d_lines = DeviceArray((n,), np.uint32, cube.device), DeviceArray((n,), np.uint32, cube.device)
+            _lib.call("spc_moments_list_count_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.byref(o), wsp, wsn,
+                      C.c_void_p(bits.ptr), bits.nbytes, C.c_void_p(d_len.ptr), C.c_void_p(d_lines.ptr), n, C.byref(desc))
+            length = d_len.get(stream).astype(np.uint64)
+            lines = int(d_lines.get(stream).astype(np.uint64).sum())
+            rows = int(length.sum())
+            if not list_is_kept(rows, lines, desc.nblocks, cube.shape[0]):
+                mask._list_failed = True
+                return None
+            off = DeviceArray.from_numpy(np.cumsum(length) - length, cube.device, stream)
+            samples = DeviceArray((max(rows, 1) * 1024,), np.uint8, cube.device)
+            meta = DeviceArray((max(rows, 1) * 256,), np.uint8, cube.device)
+            lst = _MomentsList(desc, off, d_len, samples, meta, rows)
+            _lib.call("spc_moments_list_fill_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c))
+            _lib.call("spc_stream_sync", cube.device, _sh(stream))      # later launches on any stream may read the list
+        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
+            mask._list_failed = True         # never an error: the bits march goes on
+            return None
+        mask._list = lst
+        return lst
 
 
 def _cube_c(cube, dtype=None):
@@ -236,6 +341,7 @@ def _moment_outputs(shape2d, device, want, out=None):
             bufs[name] = out[name]
             if bufs[name].shape != tuple(shape2d) or bufs[name].dtype != np.dtype(types[name]):
                 raise ValueError("preallocated output %r has wrong shape/dtype" % name)
+            _written(bufs[name])
         else:
             bufs[name] = DeviceArray(shape2d, types[name], device)
         setattr(o, "d_" + name, bufs[name].ptr)
@@ -264,8 +370,14 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
     if need and (ws is None or ws.nbytes < need):
         ws = DeviceArray((need,), np.uint8, cube.device)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
+    had_bits = mask is not None and mask._bits is not None
     bits = _mask_bits(mask, stream) if cube.dtype == _F32 else None
-    if bits is not None:       # (whether the launch can read them is the library's decision)
+    lst = _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws) if cube.dtype == _F32 else None
+    if bits is not None and lst is not None:       # (whether the launch's plan is the list's is the library's decision)
+        _lib.call("spc_moments_list_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
+                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
+                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c))
+    elif bits is not None:     # (whether the launch can read them is the library's decision)
         _lib.call("spc_moments_bits_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
                   float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
                   ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes)
@@ -347,6 +459,7 @@ def _given(out, name, shape, dtype, device):
         return DeviceArray(shape, dtype, device)
     if tuple(a.shape) != tuple(shape) or a.dtype != np.dtype(dtype):
         raise ValueError("preallocated output %r must be %s %s" % (name, tuple(shape), np.dtype(dtype)))
+    _written(a)                  # the operator is about to write into the caller's array
     return a
 
 
@@ -451,6 +564,8 @@ def _downsample_outputs(cube, axis, factor, truncate, dtype, out, out_mask):
     shape = downsample_shape(cube.shape, axis, factor, truncate)
     if out is None:
         out = DeviceArray(shape, dtype, cube.device)
+    else:
+        _written(out)
     if out_mask is None:
         out_mask = DeviceArray(shape, np.uint8, cube.device)
     if tuple(out.shape) != shape or out.dtype != np.dtype(dtype) or tuple(out_mask.shape) != shape or out_mask.dtype != np.uint8:
@@ -483,6 +598,8 @@ def _rank_filter(base, cube, sizes, rank, mode, cval, fill, mask, out, stream, n
         raise ValueError("mode must be one of %s (got %r)" % (", ".join(sorted(_lib.RANK_MODES)), mode))
     if out is None:
         out = DeviceArray(cube.shape, dtype, cube.device)
+    else:
+        _written(out)
     if tuple(out.shape) != tuple(cube.shape) or out.dtype != dtype:
         raise ValueError("preallocated output must be %s %s" % (tuple(cube.shape), dtype))
     c, m = _cube_c(cube), _mask_c(mask, cube)
@@ -544,6 +661,8 @@ def stack_shift(cube, idx, shifts, pad=(0, 0), fill=np.nan, mask=None, out=None,
         out = DeviceArray(shape if shape[0] <= _lib.STACK_MAX_CHANNELS else (1, 1), np.float64, cube.device)
     elif tuple(out.shape) != shape or out.dtype != _F64:
         raise ValueError("preallocated output must be %s float64" % (shape,))
+    else:
+        _written(out)
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill),
               C.c_void_p(d_idx.ptr), C.c_void_p(d_shift.ptr), npos, pad_lo, pad_hi, C.c_void_p(out.ptr), C.c_void_p(ws.ptr), ws.nbytes)
     if stream is not None:                   # (the inputs and the workspace go back to the pool when this returns)
@@ -644,6 +763,8 @@ def mosaic(cubes, maps, masks, fills, order, weights=None, out=None, stream=None
         out = DeviceArray(shape, dtype, dev)
     elif tuple(out.shape) != shape or out.dtype != dtype or getattr(out, "_is_view", False):
         raise ValueError("preallocated output must be a contiguous %s %s" % (shape, dtype))
+    else:
+        _written(out)
     if weights is not None and (tuple(weights.shape) != shape_yx or weights.dtype != np.int32):
         raise ValueError("weights must be an int32 %s DeviceArray" % (shape_yx,))
     ws = DeviceArray((int(_lib.load().spc_mosaic_workspace_bytes(nsrc)),), np.uint8, dev)
@@ -675,6 +796,8 @@ def subcube(cube, start, step, shape, mask=None, out=None, out_mask=None, want_m
     shape = tuple(int(n) for n in shape)
     if out is None:
         out = DeviceArray(shape, dtype, cube.device)
+    else:
+        _written(out)
     if out_mask is None and want_mask:
         out_mask = DeviceArray(shape, np.uint8, cube.device)
     if tuple(out.shape) != shape or out.dtype != dtype:
@@ -890,6 +1013,8 @@ def arith(cube, steps, mask=None, fill=np.nan, out=None, stream=None, nan_exclud
         out = DeviceArray(cube.shape, dtype, cube.device)
     elif tuple(out.shape) != tuple(cube.shape) or out.dtype != dtype:
         raise ValueError("preallocated output must be %s %s" % (tuple(cube.shape), dtype))
+    else:
+        _written(out)
     ors, ops_ = _strides(out)
     _lib.call(name, cube.device, _sh(stream), C.byref(c), C.byref(m), 1 if nan_excluded else 0, float(fill), C.byref(prog),
               C.c_void_p(out.ptr), ors, ops_)
@@ -1182,6 +1307,8 @@ def resample_bilinear_lerp(cube, xs, ys, lo, t, inv_dx, fill=np.nan, mask=None, 
         out = DeviceArray((nz_out, ny_out, nx_out), np.float32, dev)
     elif out.shape != (nz_out, ny_out, nx_out) or out.dtype != np.float32 or getattr(out, "_is_view", False):
         raise ValueError("out must be a contiguous float32 (nz_out, ny_out, nx_out) DeviceArray")
+    else:
+        _written(out)
     foot = DeviceArray((ny_out, nx_out), np.uint8, dev) if want_footprint else None
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     ws, wsn = workspace(dev, stream, _lib.WS_RESAMPLE_BILINEAR_LERP, *cube.shape, ny_out, nx_out)
@@ -1347,6 +1474,8 @@ def stats_axis(cube, axis, mask=None, want=STAT_KEYS, stream=None, out=None):
             a = DeviceArray(shp, types[k], cube.device)
         elif tuple(a.shape) != shp or a.dtype != types[k]:
             raise ValueError("out[%r] must be %s %s" % (k, shp, types[k]))
+        else:
+            _written(a)
         res[k] = a
     o = _lib.SpcStatsOutputs()
     for k in want:
@@ -1382,6 +1511,8 @@ def map_conv2d(dmap, kernel2d, stream=None, out=None):
         raise ValueError("kernel must be 2-D")
     if out is None:
         out = DeviceArray(dmap.shape, np.float64, dmap.device)
+    else:
+        _written(out)
     ws, wsn = workspace(dmap.device, stream, _lib.WS_MAP_CONV2D, 1, dmap.shape[0], dmap.shape[1], k.shape[0], k.shape[1])
     _lib.call("spc_map_conv2d_f64", dmap.device, _sh(stream), C.c_void_p(dmap.ptr), dmap.shape[0], dmap.shape[1],
               k.ctypes.data_as(C.POINTER(C.c_double)), k.shape[0], k.shape[1], C.c_void_p(out.ptr), ws, wsn)
@@ -1396,6 +1527,8 @@ def map_arith(op, a, b, c=None, s=0.0, out=None, stream=None):
             raise TypeError("maps must be float64 DeviceArrays of one shape")
     if out is None:
         out = DeviceArray(a.shape, np.float64, a.device)
+    else:
+        _written(out)
     _lib.call("spc_map_arith_f64", a.device, _sh(stream), int(op), C.c_void_p(a.ptr), C.c_void_p(b.ptr),
               C.c_void_p(c.ptr) if c is not None else None, float(s), C.c_void_p(out.ptr), int(np.prod(a.shape, dtype=np.int64)))
     return out
@@ -1413,6 +1546,8 @@ def percentile_axis0(cube, q, mask=None, center=None, scale=1.0, stream=None, ou
     name, dtype = _entry("percentile_axis0", cube)
     if out is None:
         out = DeviceArray(cube.shape[1:], dtype, cube.device)
+    else:
+        _written(out)
     c, m = _cube_c(cube), _mask_c(mask, cube)
     if center is not None and (center.dtype != dtype or tuple(center.shape) != tuple(cube.shape[1:])):
         raise TypeError("center must be a %s (ny, nx) DeviceArray" % dtype)
@@ -1680,6 +1815,8 @@ def percentile_axis2(cube, q, mask=None, center=None, scale=1.0, stream=None, ou
     nz, ny, nx = cube.shape
     if out is None:
         out = DeviceArray((nz, ny), np.float32, cube.device)
+    else:
+        _written(out)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     if center is not None and (center.dtype != np.float32 or tuple(center.shape) != (nz, ny)):
         raise TypeError("center must be a float32 (nz, ny) DeviceArray")
@@ -1721,6 +1858,8 @@ def _percentile_groups(cube, q, mask, center, stream, keep, scale, out):
         out = DeviceArray((ngroups,), np.float32, cube.device)
     elif tuple(out.shape) != (ngroups,) or out.dtype != np.float32:
         raise ValueError("preallocated output must be (%d,) float32" % ngroups)
+    else:
+        _written(out)
     ws, wsn = _pooled_scratch(cube.device, stream, int(_lib.load().spc_percentile_groups_workspace_bytes(ngroups)))
     _lib.call("spc_percentile_groups_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), int(keep), float(q),
               C.c_void_p(center.ptr) if center is not None else None, float(scale), C.c_void_p(out.ptr), ws, wsn)
@@ -1826,6 +1965,7 @@ def scale_inplace(arr, factor, stream=None):
     """arr *= factor on the device (contiguous float32 or float64 DeviceArray)."""
     if arr.dtype not in (_F32, _F64) or getattr(arr, "_is_view", False):
         raise TypeError("scale_inplace needs a contiguous float32 or float64 DeviceArray")
+    _written(arr)
     _lib.call(_entry("scale", arr)[0], arr.device, _sh(stream), C.c_void_p(arr.ptr), int(np.prod(arr.shape, dtype=np.int64)), float(factor))
     return arr
 

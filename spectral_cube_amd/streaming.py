@@ -353,6 +353,7 @@ class StripPipeline:
                 b = self.pinned[i % self.nbuf]
                 # a short last strip is stored densely: (nz, rows, nx) at the head of the slot
                 dst = self.bufs[slot].ptr + (z0 - first_z) * rows * nx * isz
+                self.bufs[slot].mark_written()       # a raw copy refills the slot: nothing derived from its old samples holds
                 if src.decode is None:
                     _lib.call("spc_memcpy_h2d", dev, C.c_void_p(dst), C.c_void_p(b.ptr), C.c_size_t(n), self.copy.handle)
                 else:
