@@ -310,6 +310,46 @@ int spc_moments_list_f32(int device, void* stream, const spc_cube_f32* cube,
                          void* d_workspace, size_t workspace_bytes,
                          const void* d_mask_bits, size_t bits_bytes, const spc_moments_list* list);
 
+/* One tier above the list: the VOXEL list, one 8-byte entry per included voxel, made FROM a list (above) for the same
+ * launch plan and the same sublists (block, split * zw + w); it reuses the list's desc.  Where the mask keeps about one
+ * voxel of a lane segment, an entry row of the list carries 16 sample bytes of which four are needed; the voxel list
+ * carries those four.
+ * Layout: an entry is { float v; uint32_t meta; } with meta = z | col << 28 | 1u << 30: z < 2^28 the plane, col in 0..3 the
+ * voxel's place in the lane's 16-byte segment, bit 30 "an entry".  A lane's entries are the voxels whose bit is set in the
+ * nibbles of its list entries, in the list's order and in ascending col within a list entry, which keeps every column's
+ * samples in the order of the march.  An entry row is 64 lanes x 8 bytes = 512 bytes.  vlen[sub] (uint32, d_len) is the
+ * longest lane's count, voff[sub] (uint64, d_off) its exclusive prefix sum in rows.  Shorter and dead lanes are padded
+ * with written all-zero entries (bit 30 clear); every byte of rows [0, sum of vlen) is written.
+ *   spc_moments_vlist_count_f32  one wave per sublist reads ONLY the list's metas: d_vlen[sub] = the maximum over the
+ *       lanes of the sum of popcount(meta >> 28) over the sublist's rows.  nsublists = entries of d_vlen, at least
+ *       list->desc.nblocks * list->desc.nsub.
+ *   spc_moments_vlist_fill_f32   one wave per sublist walks the list's rows and stores every included voxel's entry at its
+ *       lane's own running row of vlist->d_entries, then pads.  It reads neither the cube nor the bits: the list is the
+ *       cube's snapshot already.  vlist->desc must equal list->desc.  Nothing is written past row vlist->rows or past a
+ *       sublist's vlen, and nothing is read past row list->rows, whatever the offsets and lengths hold.
+ *   spc_moments_vlist_f32        spc_moments_list_f32 plus the voxel list (NULL: exactly spc_moments_list_f32).  The voxel
+ *       list is read only if the call's final plan equals vlist->desc, the bits are read (as the list asks), the buffers
+ *       hold vlist->rows, neither SPC_MOMENTS_VLIST nor SPC_MOMENTS_LIST is 0; in every other case the call is
+ *       spc_moments_list_f32.  Where the voxel list is read, `list` is not looked at: it may be NULL or stale,
+ *       and the voxel list is read whatever it holds.  The maps are bit-identical either way: per column the included
+ *       samples are added in the order of the march, and everything else only adds +0.0.
+ * The caller answers for the voxel list being that of the list it was made from.  (Added within ABI 8: nothing existing
+ * moved.) */
+typedef struct {
+    spc_moments_list_desc desc;
+    void* d_entries; size_t entries_bytes;       /* rows * 512 bytes, 8-byte aligned */
+    const uint64_t* d_off; const uint32_t* d_len; size_t nsublists;   /* >= desc.nblocks * desc.nsub entries each */
+    uint64_t rows;               /* sum of vlen */
+} spc_moments_vlist;
+int spc_moments_vlist_count_f32(int device, void* stream, const spc_moments_list* list, uint32_t* d_vlen, size_t nsublists);
+int spc_moments_vlist_fill_f32(int device, void* stream, const spc_moments_list* list, const spc_moments_vlist* vlist);
+int spc_moments_vlist_f32(int device, void* stream, const spc_cube_f32* cube,
+                          const spc_mask* mask, const double* d_cen, double dv,
+                          double m1_add, const spc_moment_outputs* out,
+                          void* d_workspace, size_t workspace_bytes,
+                          const void* d_mask_bits, size_t bits_bytes, const spc_moments_list* list,
+                          const spc_moments_vlist* vlist);
+
 /* general order N >= 2 second pass:  out = sum v*(c - mu)^N / S0
  * (dask_spectral_cube.py:1094-1099; _moments.py:185-193).  d_mu, d_s0 come
  * from spc_moments_f32. */

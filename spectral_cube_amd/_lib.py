@@ -105,6 +105,12 @@ class SpcMomentsList(C.Structure):
                 ("nsublists", C.c_size_t), ("rows", C.c_uint64)]
 
 
+class SpcMomentsVlist(C.Structure):
+    """spc_moments_vlist: the 8-byte entries of the voxels a mask includes (spc_moments_vlist_fill_f32 / spc_moments_vlist_f32)"""
+    _fields_ = [("desc", SpcMomentsListDesc), ("d_entries", C.c_void_p), ("entries_bytes", C.c_size_t),
+                ("d_off", C.c_void_p), ("d_len", C.c_void_p), ("nsublists", C.c_size_t), ("rows", C.c_uint64)]
+
+
 class SpcMask64(C.Structure):
     """spc_mask_f64: the mask of a float64 cube (thresholds compared in float64)"""
     _fields_ = [("flags", C.c_uint32), ("thr_lo", C.c_double), ("thr_hi", C.c_double),
@@ -248,6 +254,10 @@ SIGNATURES = {
     "spc_moments_list_fill_f32": (_i, [_i, _vp, _P(SpcCube), _vp, _sz, _P(SpcMomentsList)]),
     "spc_moments_list_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
                                   _P(SpcMomentOutputs), _vp, _sz, _vp, _sz, _P(SpcMomentsList)]),
+    "spc_moments_vlist_count_f32": (_i, [_i, _vp, _P(SpcMomentsList), _vp, _sz]),
+    "spc_moments_vlist_fill_f32": (_i, [_i, _vp, _P(SpcMomentsList), _P(SpcMomentsVlist)]),
+    "spc_moments_vlist_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _d, _d,
+                                   _P(SpcMomentOutputs), _vp, _sz, _vp, _sz, _P(SpcMomentsList), _P(SpcMomentsVlist)]),
     "spc_moment_order_f32": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask), _vp, _i, _vp, _vp, _vp, _i64]),
     # (spc_cube_f64 has the layout of spc_cube_f32: a pointer and five int64)
     "spc_moments_f64": (_i, [_i, _vp, _P(SpcCube), _P(SpcMask64), _vp, _d, _d, _P(SpcMomentOutputs64)]),

@@ -60,6 +60,10 @@ struct SpcDeviceGuard {
     explicit SpcDeviceGuard(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
+        // the runtime keeps a thread's last error until it is read: one left by an earlier call - this hipSetDevice on a device
+        // the machine does not have, a refused allocation - would otherwise be reported by the NEXT entry's SPC_LAUNCH_CHECK as
+        // a failed launch of its own.  Every entry that launches switches the device first, so it starts from a clean state here.
+        (void)hipGetLastError();
     }
     ~SpcDeviceGuard() {
         int cur = -1;

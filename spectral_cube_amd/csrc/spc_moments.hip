@@ -58,7 +58,12 @@ struct MomArgs {
     const uint64_t* list_off;       // [nblocks * nsplit * ZW] first entry row of a sublist
     const uint32_t* list_len;       // [nblocks * nsplit * ZW] its entry rows
     uint64_t list_rows;             // rows the two arrays hold
+    // the VOXEL-LIST forms (LIST = 2, spc_moments_vlist_*) read the same fields, so that the arguments of every other form
+    // keep their layout: list_samples is the entry array ([rows][64] of 8 bytes), list_off / list_len / list_rows are
+    // voff / vlen / the voxel list's rows, list_meta is not read
 };
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));   // an entry of the voxel list: { bits of v, meta }
 
 // per-column running state
 struct Acc {
@@ -187,7 +192,19 @@ __device__ __forceinline__ unsigned vget(const unsigned char& v, int) { return v
 // never makes -0.0 of these additions) nor the count, the any-valid bit or the extrema; a lane's entries keep the order of the
 // march, and padding entries (meta 0, samples 0) are excluded planes.  So the maps are those of the march bit for bit.  The
 // channel coordinate is a per-lane load (the lanes of a row hold different planes); cen is nz doubles and stays in the caches.
-template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false, bool BITS = false, bool LIST = false>
+//
+// LIST = 2, the voxel list (layout: include/spcube_hip.h, spc_moments_vlist_*): again the loader alone differs.  An entry is ONE
+// included voxel of the lane - its sample, its plane and its place col in the lane's segment - and a row costs one 8-byte load
+// per lane, so U = 16 rows in flight hold 32 registers where the list form holds 40 at U = 8.  Every entry goes through acc_add
+// for all four columns with ok = mom_pred(v) && "an entry" && col == i.  Why the maps are the march's bit for bit: column i
+// receives its included voxels in the order of the march (a lane's entries follow the list's order, which is the march's, and
+// ascending col within a plane never reorders ONE column), each with the v, c, c2 and z the march passes; and every other call
+// of acc_add for column i has ok false, which is exactly the call the march makes for an excluded voxel: w = 0.f, so s0 += +0.0
+// and two fma(+0.0, c, s) with c the coordinate of a plane the march also adds at with ok false or true - they leave every sum as
+// it is (no sum is ever -0.0: they start at +0.0 and round-to-nearest makes -0.0 only of (-0.0) + (-0.0)), and with ok false
+// neither the count, the any-valid bit nor the extrema move.  Padding entries (all zero, bit 30 clear) are ok false in every
+// column.  The columns' additions the march makes and this form leaves out are +0.0 additions of the same kind.
+template <int VEC, int ZW, int U, bool ARR, int EXT, int PRED, bool MF = false, bool BITS = false, int LIST = 0>
 __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     static_assert(!MF || (ARR && VEC == 4), "mask-first is the 16-byte lane form with a mask array");
     static_assert(!BITS || MF, "the packed mask is read by the mask-first forms only");
@@ -228,7 +245,41 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
     if (live) {
         int64_t z = zb + w;
         // main loop: U planes (stride ZW) in flight per lane
-        if constexpr (LIST) {
+        if constexpr (LIST == 2) {
+            // one voxel of a lane into the column it belongs to; the other three columns add +0.0 (see above the kernel)
+            auto add_voxel = [&](const u32x2& e) {
+                const uint32_t mt = e.y;
+                const float val = __uint_as_float(e.x);
+                const int zz = (int)min((int64_t)(mt & 0x0fffffffu), A.nz - 1);
+                const double c = A.cen[zz];
+                const double c2 = c * c;
+                const bool in = mom_pred<PRED>(val, lim, lo, hi) && ((mt >> 30) & 1u) != 0;
+                const uint32_t col = (mt >> 28) & 3u;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc_add<EXT>(acc[i], val, in && col == (uint32_t)i, c, c2, zz);
+            };
+            // the sublist of this wave: wave-uniform indices, scalar loads
+            typedef const uint64_t __attribute__((address_space(4))) cu64;
+            typedef const uint32_t __attribute__((address_space(4))) cu32;
+            const int64_t sub = (blk * A.nsplit + split) * ZW + w;
+            const uint64_t row = ((cu64*)A.list_off)[sub];
+            uint32_t n = ((cu32*)A.list_len)[sub];
+            if (row > A.list_rows || n > A.list_rows - row) n = 0;   // never past the array, whatever voff and vlen hold
+            typedef const u32x2 __attribute__((address_space(1))) GE;
+            GE* pe = (GE*)A.list_samples + row * kLanes + lane;
+            uint32_t k = 0;
+            for (; k + U <= n; k += U, pe += U * kLanes) {
+                u32x2 e[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) e[u] = __builtin_nontemporal_load(pe + u * kLanes);
+#pragma unroll
+                for (int u = 0; u < U; ++u) add_voxel(e[u]);
+            }
+            for (; k < n; ++k, pe += kLanes) {
+                const u32x2 e = *pe;
+                add_voxel(e);
+            }
+        } else if constexpr (LIST) {
             // one entry of a lane: add_plane of the march below, with the lane's own plane number and coordinate (a plane number
             // past the cube, which no filled list holds, reads the last coordinate instead of memory that is not cen's)
             auto add_entry = [&](const F& v, uint32_t mt) {
@@ -566,11 +617,12 @@ __global__ __launch_bounds__(256) void moment_order_v4_kernel(const OrdArgs A) {
     }
 }
 
-// bits: the packed mask array, or nullptr; list_u: 0, or the rows in flight of the LIST form that reads A.list_* (4 or 8)
-struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; int list_u; };
+// bits: the packed mask array, or nullptr; list_u: 0, or the rows in flight of the LIST form that reads A.list_* (4 or 8);
+// vlist_u: 0, or the rows in flight of the voxel-list form (LIST = 2) that reads A.list_* as a voxel list (8 or 16)
+struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; int list_u; int vlist_u; };
 
 template <int VEC, int ZW, int U, bool ARR, int EXT>
-int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits, int list_u) {
+int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits, int list_u, int vlist_u) {
     dim3 block(kLanes, ZW);
     dim3 grid((unsigned)((A.ngroups + kLanes - 1) / kLanes), (unsigned)A.nsplit);
     if constexpr (ARR && VEC == 4) {
@@ -579,14 +631,26 @@ int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_fir
             // layout (and every other instantiation the instructions) they had
             MomArgs B = A;
             B.mask.arr = bits;
+            if (vlist_u) {
+                // the voxel-list forms: the plan's ZW and split, U rows of 8-byte entries in flight
+                if (vlist_u == 16) {
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 16, ARR, EXT, 1, true, true, 2>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 16, ARR, EXT, 0, true, true, 2>), grid, block, 0, st, B);
+                } else {
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, 2>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, 2>), grid, block, 0, st, B);
+                }
+                SPC_LAUNCH_CHECK();
+                return SPC_OK;
+            }
             if (list_u) {
                 // the LIST forms: the plan's ZW and split with a batch of their own (U counts planes in the march, rows here)
                 if (list_u == 8) {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, true>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, true>), grid, block, 0, st, B);
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, 1>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, 1>), grid, block, 0, st, B);
                 } else {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 1, true, true, true>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 0, true, true, true>), grid, block, 0, st, B);
+                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 1, true, true, 1>), grid, block, 0, st, B);
+                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 0, true, true, 1>), grid, block, 0, st, B);
                 }
                 SPC_LAUNCH_CHECK();
                 return SPC_OK;
@@ -625,25 +689,26 @@ template <bool ARR, int EXT>
 int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     if (p.vec == 4) {
         switch (p.zw * 16 + p.u) {
-            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
         }
     }
-    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
-    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u);
+    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
 }
 
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     Plan p;
     p.bits = nullptr;
     p.list_u = 0;
+    p.vlist_u = 0;
     auto aligned = [&](int v) {
         const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
         return (c->nx % v == 0) && (c->row_stride % v == 0) && (c->plane_stride % v == 0) &&
@@ -858,6 +923,124 @@ __global__ __launch_bounds__(kLanes * kListWaves) void list_fill_kernel(const Li
     }
 }
 
+// ---- the voxel list, made from a list (layout: include/spcube_hip.h, spc_moments_vlist_*) -------------------------
+// One wave per sublist of the list, the list's rows read coalesced; neither kernel reads the cube or the bits.
+struct VlistArgs {
+    const uint32_t* meta;              // the list: [rows][64] z | nibble << 28 ...
+    const f32x4* samples;              // ... and [rows][64] the lane's four samples (fill)
+    const uint64_t* off;
+    const uint32_t* len;
+    uint64_t rows;
+    int64_t total;                     // nblocks * nsub
+    uint32_t* vlen_out;                // count: the longest lane's included voxels
+    const uint64_t* voff;              // fill
+    const uint32_t* vlen;
+    u32x2* entries;
+    uint64_t vrows;
+};
+
+constexpr int kVlistBatch = 8;         // list rows in flight per lane of the count kernel
+constexpr int kVlistFillBatch = 4;     // ... and of the fill kernel (20 bytes a row)
+constexpr int kVlistLongSublist = 128; // mean rows per sublist from which the sums and count forms keep 16 rows in flight (moments_run)
+
+__global__ __launch_bounds__(kLanes * kListWaves) void vlist_count_kernel(const VlistArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (s >= A.total) return;                                        // wave-uniform
+    // the rows of this sublist, cut to what the list holds whatever off and len say
+    const uint64_t row0 = A.off[s];
+    uint32_t n = A.len[s];
+    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
+    if (n > room) n = (uint32_t)room;
+    const uint32_t* pq = A.meta + row0 * kLanes + lane;
+    uint32_t cnt = 0, k = 0;
+    for (; k + kVlistBatch <= n; k += kVlistBatch, pq += kVlistBatch * kLanes) {
+        uint32_t mt[kVlistBatch];
+#pragma unroll
+        for (int u = 0; u < kVlistBatch; ++u) mt[u] = __builtin_nontemporal_load(pq + u * kLanes);
+#pragma unroll
+        for (int u = 0; u < kVlistBatch; ++u) cnt += (uint32_t)__popc(mt[u] >> 28);
+    }
+    for (; k < n; ++k, pq += kLanes) cnt += (uint32_t)__popc(*pq >> 28);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt = max(cnt, (uint32_t)__shfl_xor((int)cnt, o));
+    if (lane == 0) A.vlen_out[s] = cnt;
+}
+
+__global__ __launch_bounds__(kLanes * kListWaves) void vlist_fill_kernel(const VlistArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (s >= A.total) return;                                        // wave-uniform
+    // the rows read and the rows written, each cut to what its arrays hold whatever the offsets and lengths say
+    const uint64_t row0 = A.off[s];
+    uint32_t n = A.len[s];
+    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
+    if (n > room) n = (uint32_t)room;
+    const uint64_t vrow0 = A.voff[s];
+    uint32_t vn = A.vlen[s];
+    const uint64_t vroom = vrow0 < A.vrows ? A.vrows - vrow0 : 0;
+    if (vn > vroom) vn = (uint32_t)vroom;
+    const uint32_t* pq = A.meta + row0 * kLanes + lane;
+    const f32x4* ps = A.samples + row0 * kLanes + lane;
+    u32x2* pe = A.entries + vrow0 * kLanes + lane;
+    uint32_t kv = 0;                                                 // the lane's own running row
+    auto put = [&](const f32x4& v, uint32_t mt) {
+        const uint32_t z = mt & 0x0fffffffu;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (((mt >> (28 + i)) & 1u) != 0 && kv < vn) {
+                u32x2 e;
+                e.x = __float_as_uint(v[i]);
+                e.y = z | ((uint32_t)i << 28) | (1u << 30);
+                pe[(uint64_t)kv * kLanes] = e;
+                ++kv;
+            }
+        }
+    };
+    uint32_t k = 0;
+    for (; k + kVlistFillBatch <= n; k += kVlistFillBatch, pq += kVlistFillBatch * kLanes, ps += kVlistFillBatch * kLanes) {
+        uint32_t mt[kVlistFillBatch];
+        f32x4 v[kVlistFillBatch];
+#pragma unroll
+        for (int u = 0; u < kVlistFillBatch; ++u) mt[u] = __builtin_nontemporal_load(pq + u * kLanes);
+#pragma unroll
+        for (int u = 0; u < kVlistFillBatch; ++u) v[u] = __builtin_nontemporal_load(ps + u * kLanes);
+#pragma unroll
+        for (int u = 0; u < kVlistFillBatch; ++u) put(v[u], mt[u]);
+    }
+    for (; k < n; ++k, pq += kLanes, ps += kLanes) {
+        const uint32_t mt = *pq;
+        const f32x4 v = *ps;
+        put(v, mt);
+    }
+    // padding: all zero, bit 30 clear - not an entry
+    for (; kv < vn; ++kv) pe[(uint64_t)kv * kLanes] = u32x2{0u, 0u};
+}
+
+// the list a voxel list is counted and filled from: its desc a plan, its arrays holding the rows it names (with_samples: fill)
+int vlist_source_check(const spc_moments_list* list, bool with_samples, int64_t* total) {
+    SPC_REQUIRE(list != nullptr, "list is NULL");
+    const spc_moments_list_desc& d = list->desc;
+    SPC_REQUIRE((d.zw == 1 || d.zw == 4 || d.zw == 8) && d.nsplit >= 1 && d.zchunk >= 1 && d.nsub == (int64_t)d.nsplit * d.zw &&
+                d.nblocks >= 1 && d.nblocks < (1LL << 31), "the list's desc is not a launch plan");
+    *total = d.nblocks * d.nsub;
+    SPC_REQUIRE((*total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
+    SPC_REQUIRE(list->d_off != nullptr && list->d_len != nullptr && list->nsublists >= (size_t)*total,
+                "the list's d_off and d_len: %zu entries given, %lld sublists", list->nsublists, (long long)*total);
+    SPC_REQUIRE(list->rows == 0 || (list->d_meta != nullptr && (!with_samples || list->d_samples != nullptr)),
+                "the list's d_samples or d_meta is NULL");
+    SPC_REQUIRE(list->meta_bytes / 256 >= list->rows && (!with_samples || list->samples_bytes / 1024 >= list->rows),
+                "the list's d_samples / d_meta too small for %llu rows (1024 and 256 bytes each)", (unsigned long long)list->rows);
+    SPC_REQUIRE(spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4) &&
+                (!with_samples || spc_aligned(list->d_samples, 16)),
+                "the list's d_samples must be 16-byte, d_off 8-byte, d_meta and d_len 4-byte aligned");
+    return SPC_OK;
+}
+
+bool same_desc(const spc_moments_list_desc& d, const spc_moments_list_desc& l) {
+    return d.zw == l.zw && d.nsplit == l.nsplit && d.zchunk == l.zchunk && d.nblocks == l.nblocks && d.nsub == l.nsub;
+}
+
 constexpr int64_t kListMaxNz = 1LL << 28;      // z shares its meta word with the nibble
 
 // what every moments entry works out before it launches: the checks, the kernel arguments, the plan after the workspace
@@ -928,7 +1111,7 @@ int list_exists(const MomArgs& A, const Plan& p, bool have_bits, const char* who
 
 int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask, const double* d_cen, double dv, double m1_add,
                 const spc_moment_outputs* out, void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
-                const spc_moments_list* list) {
+                const spc_moments_list* list, const spc_moments_vlist* vlist) {
     MomArgs A{};
     Plan p;
     int rc = moments_setup(cube, mask, d_cen, true, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
@@ -952,6 +1135,25 @@ int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_ma
             A.list_rows = list->rows;
             // rows in flight per lane (profiles/moments_list_bench.txt)
             p.list_u = spc_switch("SPC_MOMENTS_LIST_U", ext ? 4 : 8) == 4 ? 4 : 8;
+        }
+    }
+    // the voxel list under the same conditions, for exactly this plan; otherwise what the call was without it
+    if (vlist && p.bits && A.nz < kListMaxNz && spc_switch("SPC_MOMENTS_LIST", 1) != 0 && spc_switch("SPC_MOMENTS_VLIST", 1) != 0) {
+        const spc_moments_list_desc d = list_desc(A, p);
+        if (same_desc(d, vlist->desc) && vlist->d_entries && vlist->d_off && vlist->d_len && vlist->nsublists >= (size_t)(d.nblocks * d.nsub) &&
+            vlist->entries_bytes / 512 >= vlist->rows && spc_aligned(vlist->d_entries, 8) && spc_aligned(vlist->d_off, 8) &&
+            spc_aligned(vlist->d_len, 4)) {
+            A.list_samples = (const f32x4*)vlist->d_entries;     // (MomArgs: the voxel-list forms read the list's fields)
+            A.list_meta = nullptr;
+            A.list_off = vlist->d_off;
+            A.list_len = vlist->d_len;
+            A.list_rows = vlist->rows;
+            // rows in flight per lane (profiles/moments_vlist_bench.txt): the U = 16 forms hold 142 - 148 VGPRs, three waves per SIMD
+            // against five, and pay only where a sublist is many batches long - 180 rows on average at the north star (5 % faster
+            // than U = 8), not at 38 or 70 rows (27 % and 20 % slower); with extrema U = 8 wins at every shape measured
+            const uint64_t nsublists = (uint64_t)(d.nblocks * d.nsub);
+            const bool long_sublists = vlist->rows / nsublists >= (uint64_t)kVlistLongSublist;
+            p.vlist_u = spc_switch("SPC_MOMENTS_VLIST_U", !ext && long_sublists ? 16 : 8) == 16 ? 16 : 8;
         }
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1027,14 +1229,14 @@ int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const sp
 int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                          const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                          void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes) {
-    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, nullptr);
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, nullptr, nullptr);
 }
 
 int spc_moments_list_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                          const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                          void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
                          const spc_moments_list* list) {
-    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list);
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list, nullptr);
 }
 
 int spc_moments_list_plan_f32(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out,
@@ -1118,6 +1320,54 @@ int spc_moments_list_fill_f32(int device, void* stream, const spc_cube_f32* cube
     L.samples = (f32x4*)list->d_samples; L.meta = (uint32_t*)list->d_meta; L.rows = list->rows;
     hipLaunchKernelGGL(list_fill_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
                        (hipStream_t)stream, L);
+    SPC_LAUNCH_CHECK();
+    return SPC_OK;
+}
+
+int spc_moments_vlist_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
+                          const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
+                          void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
+                          const spc_moments_list* list, const spc_moments_vlist* vlist) {
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list, vlist);
+}
+
+int spc_moments_vlist_count_f32(int device, void* stream, const spc_moments_list* list, uint32_t* d_vlen, size_t nsublists) {
+    int64_t total = 0;
+    int rc = vlist_source_check(list, false, &total);
+    if (rc) return rc;
+    SPC_REQUIRE(d_vlen != nullptr, "d_vlen is NULL");
+    SPC_REQUIRE(nsublists >= (size_t)total, "d_vlen too small: %zu entries given, %lld sublists", nsublists, (long long)total);
+    SPC_REQUIRE(spc_aligned(d_vlen, 4), "d_vlen must be 4-byte aligned");
+    SPC_DEVICE(device);
+    VlistArgs V{};
+    V.meta = (const uint32_t*)list->d_meta; V.off = list->d_off; V.len = list->d_len; V.rows = list->rows; V.total = total;
+    V.vlen_out = d_vlen;
+    hipLaunchKernelGGL(vlist_count_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
+                       (hipStream_t)stream, V);
+    SPC_LAUNCH_CHECK();
+    return SPC_OK;
+}
+
+int spc_moments_vlist_fill_f32(int device, void* stream, const spc_moments_list* list, const spc_moments_vlist* vlist) {
+    int64_t total = 0;
+    int rc = vlist_source_check(list, true, &total);
+    if (rc) return rc;
+    SPC_REQUIRE(vlist != nullptr, "vlist is NULL");
+    SPC_REQUIRE(same_desc(list->desc, vlist->desc), "the voxel list's desc is not the list's");
+    SPC_REQUIRE(vlist->d_off != nullptr && vlist->d_len != nullptr && vlist->nsublists >= (size_t)total,
+                "d_off and d_len: %zu entries given, %lld sublists", vlist->nsublists, (long long)total);
+    SPC_REQUIRE(vlist->rows == 0 || vlist->d_entries != nullptr, "d_entries is NULL");
+    SPC_REQUIRE(vlist->entries_bytes / 512 >= vlist->rows, "d_entries too small for %llu rows (512 bytes each)",
+                (unsigned long long)vlist->rows);
+    SPC_REQUIRE(spc_aligned(vlist->d_entries, 8) && spc_aligned(vlist->d_off, 8) && spc_aligned(vlist->d_len, 4),
+                "d_entries and d_off must be 8-byte, d_len 4-byte aligned");
+    SPC_DEVICE(device);
+    VlistArgs V{};
+    V.meta = (const uint32_t*)list->d_meta; V.samples = (const f32x4*)list->d_samples;
+    V.off = list->d_off; V.len = list->d_len; V.rows = list->rows; V.total = total;
+    V.voff = vlist->d_off; V.vlen = vlist->d_len; V.entries = (u32x2*)vlist->d_entries; V.vrows = vlist->rows;
+    hipLaunchKernelGGL(vlist_fill_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
+                       (hipStream_t)stream, V);
     SPC_LAUNCH_CHECK();
     return SPC_OK;
 }

@@ -34,10 +34,15 @@ class MaskSpec:
     include (spc_moments_list_*: include/spcube_hip.h) and later launches with the same launch plan read that list instead
     of marching the cube - where the list is at most half of the bytes the march fetches; otherwise it is refused, once,
     and the march goes on.  The list costs 1280 bytes of HBM per entry row (about 14 GB for a 4096 x 2048 x 2048 cube under
-    a 4 % mask) and lives as long as the spec.  It is keyed by the bits' key and the cube's root array BY IDENTITY, its
-    address, shape, strides and write generation: another cube, upload() into the cube or an operator of this package
-    writing into it (out=, scale_inplace) drop the list, and only the list.  SAMPLES changed behind the library's back
-    after a spec's second use on the cube need invalidate() just as mask bytes do.  SPC_MOMENTS_LIST=0 turns the list off."""
+    a 4 % mask) and lives as long as the spec.  The launch after that (normally the fourth use) compacts a kept, non-empty
+    list into the VOXEL list (spc_moments_vlist_*): one 8-byte entry per included voxel instead of a 20-byte entry per
+    included lane segment, kept only where it reads at most half of what the list does (vlist_is_kept: masks that keep about
+    one voxel of a segment; connected masks are refused, once, and stay on the list).  The list's arrays stay allocated
+    beside it (6 GB of voxel list beside 14 GB of list for that cube).  SPC_MOMENTS_VLIST=0 turns the voxel list off.
+    The list is keyed by the bits' key and the cube's root array BY IDENTITY, its address, shape, strides and write
+    generation: another cube, upload() into the cube or an operator of this package writing into it (out=, scale_inplace)
+    drop the list - the voxel list with it - and only them.  SAMPLES changed behind the library's back after a spec's second
+    use on the cube need invalidate() just as mask bytes do.  SPC_MOMENTS_LIST=0 turns the list off."""
     flags: int = 0
     thr_lo: float = 0.0
     thr_hi: float = 0.0
@@ -52,6 +57,9 @@ class MaskSpec:
     _list_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)      # the cube of the launch before
     _list_root: Optional[object] = field(default=None, init=False, compare=False, repr=False)    # weakref to that cube's root array
     _list_failed: bool = field(default=False, init=False, compare=False, repr=False)   # refused / no form / no memory: the bits march
+    # the voxel list made from _list (_moments_vlist): dropped wherever the list is, under the same lock
+    _vlist: Optional[object] = field(default=None, init=False, compare=False, repr=False)
+    _vlist_failed: bool = field(default=False, init=False, compare=False, repr=False)  # refused / switched off / no memory: the list
 
     def invalidate(self):
         """forget the packed form of the array term and the list made from it, and start counting uses again: after the
@@ -72,6 +80,8 @@ class MaskSpec:
         self._list_key = None
         self._list_root = None
         self._list_failed = False
+        self._vlist = None                   # the voxel list holds what THIS list holds
+        self._vlist_failed = False
 
     def to_c(self, wide=False):
         """spc_mask_f32, or (*wide*) spc_mask_f64: the thresholds as they are (a float64 cube is compared in float64)"""
@@ -250,6 +260,69 @@ def _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws):
         return lst
 
 
+class _MomentsVlist:
+    """the device arrays of one voxel list (spc_moments_vlist: include/spcube_hip.h) and the struct that names them"""
+
+    def __init__(self, desc, off, length, entries, rows):
+        self.desc, self.off, self.len, self.entries, self.rows = desc, off, length, entries, int(rows)
+        c = self.c = _lib.SpcMomentsVlist()
+        c.desc = desc
+        c.d_entries, c.entries_bytes = entries.ptr, entries.nbytes
+        c.d_off, c.d_len, c.nsublists = off.ptr, length.ptr, int(desc.nblocks * desc.nsub)
+        c.rows = self.rows
+
+    @property
+    def nbytes(self):
+        return self.rows * 512
+
+
+def vlist_is_kept(vrows, rows):
+    """the voxel list is kept only where it reads at most half of what the list it is made from does: 512 bytes per entry row
+    against 1280.  A condition, not a tuning result: masks that keep three or four voxels of a lane segment (connected
+    signal masks) stay on the list"""
+    return 2 * 512 * int(vrows) <= 1280 * int(rows)
+
+
+def _moments_vlist(mask, lst, prev, device, stream):
+    """the voxel list made from *lst*, the list this launch reads, or None.  It is built by the first launch that finds the
+    list ALREADY BUILT BY AN EARLIER CALL (*prev*, the spec's list before this launch, is *lst*) and holding at least one
+    row - normally the spec's fourth use; an empty list is never compacted.  The launch that builds counts on *stream*,
+    reads the counts back (one stream sync), forms the offsets on the host, allocates, fills, and uses the voxel list.  A
+    refusal (vlist_is_kept), SPC_MOMENTS_VLIST=0 and a failed allocation are remembered on the spec and are silent: the
+    list goes on being read.  The voxel list is dropped with the list (MaskSpec._drop_list)."""
+    if lst is None:
+        return None
+    with _bits_lock:
+        if mask._list is not lst:            # another thread dropped it meanwhile
+            return None
+        if mask._vlist is not None or mask._vlist_failed:
+            return mask._vlist
+        if prev is not lst or lst.rows == 0:
+            return None
+        if not _switch_on("SPC_MOMENTS_VLIST"):
+            mask._vlist_failed = True
+            return None
+        try:
+            n = int(lst.desc.nblocks * lst.desc.nsub)
+            d_vlen = DeviceArray((n,), np.uint32, device)
+            _lib.call("spc_moments_vlist_count_f32", device, _sh(stream), C.byref(lst.c), C.c_void_p(d_vlen.ptr), n)
+            vlen = d_vlen.get(stream).astype(np.uint64)
+            vrows = int(vlen.sum())
+            if not vlist_is_kept(vrows, lst.rows):
+                mask._vlist_failed = True
+                return None
+            voff = DeviceArray.from_numpy(np.cumsum(vlen) - vlen, device, stream)
+            entries = DeviceArray((max(vrows, 1) * 512,), np.uint8, device)
+            vl = _MomentsVlist(lst.desc, voff, d_vlen, entries, vrows)
+            _lib.call("spc_moments_vlist_fill_f32", device, _sh(stream), C.byref(lst.c), C.byref(vl.c))
+            _lib.call("spc_stream_sync", device, _sh(stream))      # later launches on any stream may read the voxel list
+        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
+            mask._vlist_failed = True        # never an error: the list goes on being read
+            return None
+        mask._vlist = vl
+        return vl
+
+
 def _cube_c(cube, dtype=None):
     """spc_cube_f32 / spc_cube_f64 (one layout) of a float32 or float64 cube; *dtype*: the one sample type an operator
     without the other form takes"""
@@ -372,8 +445,14 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
     had_bits = mask is not None and mask._bits is not None
     bits = _mask_bits(mask, stream) if cube.dtype == _F32 else None
+    prev = mask._list if mask is not None else None
     lst = _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws) if cube.dtype == _F32 else None
-    if bits is not None and lst is not None:       # (whether the launch's plan is the list's is the library's decision)
+    vl = _moments_vlist(mask, lst, prev, cube.device, stream) if bits is not None and lst is not None else None
+    if vl is not None:                             # (whether the launch's plan is the voxel list's is the library's decision)
+        _lib.call("spc_moments_vlist_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
+                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
+                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c), C.byref(vl.c))
+    elif bits is not None and lst is not None:       # (whether the launch's plan is the list's is the library's decision)
         _lib.call("spc_moments_list_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
                   float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
                   ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c))
