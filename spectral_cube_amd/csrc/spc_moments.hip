@@ -28,14 +28,13 @@
 // arithmetic at all (tools/micro/mask_patterns.hip), which is what is left of the 8 TB/s in this access pattern
 // (profiles/r04_moments_issue.log).  SPC_MOMENTS_XCD=1 hands the blocks of one XCD neighbouring column groups
 // (+3 % on the bare read, nothing on the kernel: off).
-#include "spc_common.h"
+// This unit: the march and its combine, the order-N second pass, the launch plan and the spc_moments*_f32 entries.  The forms a
+// reused mask and cube are read in are BUILT in spc_moments_forms.hip; spc_moments_forms.h has what the two units share.
+#include "spc_moments_forms.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-constexpr int kLanes = 64;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct MomArgs {
     const float* cube;
@@ -62,8 +61,6 @@ struct MomArgs {
     // keep their layout: list_samples is the entry array ([rows][64] of 8 bytes), list_off / list_len / list_rows are
     // voff / vlen / the voxel list's rows, list_meta is not read
 };
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));   // an entry of the voxel list: { bits of v, meta }
 
 // per-column running state
 struct Acc {
@@ -346,7 +343,7 @@ __global__ __launch_bounds__(kLanes * ZW) void moments_kernel(const MomArgs A) {
             typedef const F __attribute__((address_space(1))) GF;
             typedef const M __attribute__((address_space(1))) GM;
             gfloat* pz = (gfloat*)(p + z * A.plane_stride);      // the samples of plane z ...
-            // (BITS: A.mask.arr is the packed form - launch_main - and this the byte that holds the lane's nibble)
+            // (BITS: A.mask.arr is the packed form - launch_vec4 - and this the byte that holds the lane's nibble)
             gbyte* qz = BITS ? (gbyte*)(A.mask.arr + (blk * A.nz + z) * 32 + (lane >> 1))
                              : (gbyte*)(pm + z * A.mask.plane_stride);  // ... and the first mask that has not been asked for yet
             // the odd lanes own the high nibble of their byte.  The shift runs under the lane mask (scalar registers) and in place:
@@ -617,64 +614,25 @@ __global__ __launch_bounds__(256) void moment_order_v4_kernel(const OrdArgs A) {
     }
 }
 
-// bits: the packed mask array, or nullptr; list_u: 0, or the rows in flight of the LIST form that reads A.list_* (4 or 8);
-// vlist_u: 0, or the rows in flight of the voxel-list form (LIST = 2) that reads A.list_* as a voxel list (8 or 16)
-struct Plan { int vec, zw, u, nsplit; int64_t zchunk; bool mask_first; const uint8_t* bits; int list_u; int vlist_u; };
+// ---- the launch plan: what a launch reads, each form a loader of moments_kernel - every sample and mask byte; the mask bytes
+// first (MF); the packed mask (BITS); the list of included lane segments (LIST = 1); the voxel list (LIST = 2).  Everything past
+// kEverything exists for 16-byte lanes with a mask array only.  u: what the form keeps in flight per lane - planes of the march
+// (2, 4, 8), entry rows of the list (4, 8) or of the voxel list (8, 16); bits: the packed mask from kBits on; ext: with extrema
+enum Form { kEverything, kMaskFirst, kBits, kList, kVlist };
+struct Plan { int vec, zw, u, nsplit; int64_t zchunk; Form form; const uint8_t* bits; bool ext; };
 
-template <int VEC, int ZW, int U, bool ARR, int EXT>
-int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_first, const uint8_t* bits, int list_u, int vlist_u) {
+template <int VEC, int ZW, int U, bool ARR, int EXT, bool MF = false, bool BITS = false, int LIST = 0>
+int launch_form(const MomArgs& A, hipStream_t st, bool thresholds) {
     dim3 block(kLanes, ZW);
     dim3 grid((unsigned)((A.ngroups + kLanes - 1) / kLanes), (unsigned)A.nsplit);
-    if constexpr (ARR && VEC == 4) {
-        if (mask_first && bits) {
-            // the BITS forms never read the byte array: its pointer carries the packed form, so that the arguments keep the
-            // layout (and every other instantiation the instructions) they had
-            MomArgs B = A;
-            B.mask.arr = bits;
-            if (vlist_u) {
-                // the voxel-list forms: the plan's ZW and split, U rows of 8-byte entries in flight
-                if (vlist_u == 16) {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 16, ARR, EXT, 1, true, true, 2>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 16, ARR, EXT, 0, true, true, 2>), grid, block, 0, st, B);
-                } else {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, 2>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, 2>), grid, block, 0, st, B);
-                }
-                SPC_LAUNCH_CHECK();
-                return SPC_OK;
-            }
-            if (list_u) {
-                // the LIST forms: the plan's ZW and split with a batch of their own (U counts planes in the march, rows here)
-                if (list_u == 8) {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 1, true, true, 1>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 8, ARR, EXT, 0, true, true, 1>), grid, block, 0, st, B);
-                } else {
-                    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 1, true, true, 1>), grid, block, 0, st, B);
-                    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, 4, ARR, EXT, 0, true, true, 1>), grid, block, 0, st, B);
-                }
-                SPC_LAUNCH_CHECK();
-                return SPC_OK;
-            }
-            if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true, true>), grid, block, 0, st, B);
-            else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true, true>), grid, block, 0, st, B);
-            SPC_LAUNCH_CHECK();
-            return SPC_OK;
-        }
-        if (mask_first) {
-            if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, true>), grid, block, 0, st, A);
-            else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, true>), grid, block, 0, st, A);
-            SPC_LAUNCH_CHECK();
-            return SPC_OK;
-        }
-    }
-    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0>), grid, block, 0, st, A);
+    if (thresholds) hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 1, MF, BITS, LIST>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((moments_kernel<VEC, ZW, U, ARR, EXT, 0, MF, BITS, LIST>), grid, block, 0, st, A);
     SPC_LAUNCH_CHECK();
     return SPC_OK;
 }
 
-// 16-byte lanes: ZW in {1, 4, 8}, U in {2, 4, 8}; the narrower lanes (odd nx, unaligned views): ZW in {1, 4}, U = 4
-// Mask-first forms (launch_main): their register counts rest on three things that a compiler change can undo - the empty asm
+// 16-byte lanes: ZW in {1, 4, 8}, U in {2, 4, 8}, one line per (form, u) below; the narrower lanes (odd nx, unaligned views): ZW in {1, 4}, U = 4
+// Mask-first forms (launch_vec4): their register counts rest on three things that a compiler change can undo - the empty asm
 // statements on the carried pointers and on the lane number, and the global address space of the pointers (see the kernel) -
 // so check -Rpass-analysis=kernel-resource-usage after one (profiles/moments_mask_first_bench.txt has the table: <4,4,8,sums,0>
 // 79 VGPRs, six waves per SIMD).  Two groups of mask-first forms hold a wave per SIMD fewer than the loop that loads everything
@@ -685,32 +643,49 @@ int launch_main(const MomArgs& A, hipStream_t st, bool thresholds, bool mask_fir
 // each; they rest on the nibble being shifted and masked IN PLACE (the asm statements in the kernel): with a shift amount in
 // a vector register <4,8,8,sums> held 82 and five waves and a nearly empty mask ran 8 % slower than on its bytes.
 // <4,4,8,count,0> holds 81 against the byte form's 80: five waves against six (and still gains what the sums form gains).
+template <int ZW, bool ARR, int EXT>
+int launch_vec4(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
+    if constexpr (ARR) {
+        // the BITS forms never read the byte array: its pointer carries the packed form, so that the arguments keep the layout
+        // (and every other instantiation the instructions) they had.  Made only where a BITS form is launched
+        auto B = [&] {
+            MomArgs b = A;
+            b.mask.arr = p.bits;
+            return b;
+        };
+        switch (p.form * 32 + p.u) {
+            case kVlist * 32 + 16: return launch_form<4, ZW, 16, ARR, EXT, true, true, 2>(B(), st, thr);
+            case kVlist * 32 + 8: return launch_form<4, ZW, 8, ARR, EXT, true, true, 2>(B(), st, thr);
+            case kList * 32 + 8: return launch_form<4, ZW, 8, ARR, EXT, true, true, 1>(B(), st, thr);
+            case kList * 32 + 4: return launch_form<4, ZW, 4, ARR, EXT, true, true, 1>(B(), st, thr);
+            case kBits * 32 + 2: return launch_form<4, ZW, 2, ARR, EXT, true, true>(B(), st, thr);
+            case kBits * 32 + 4: return launch_form<4, ZW, 4, ARR, EXT, true, true>(B(), st, thr);
+            case kBits * 32 + 8: return launch_form<4, ZW, 8, ARR, EXT, true, true>(B(), st, thr);
+            case kMaskFirst * 32 + 2: return launch_form<4, ZW, 2, ARR, EXT, true>(A, st, thr);
+            case kMaskFirst * 32 + 4: return launch_form<4, ZW, 4, ARR, EXT, true>(A, st, thr);
+            case kMaskFirst * 32 + 8: return launch_form<4, ZW, 8, ARR, EXT, true>(A, st, thr);
+        }
+    }
+    if (p.u == 2) return launch_form<4, ZW, 2, ARR, EXT>(A, st, thr);
+    return p.u == 4 ? launch_form<4, ZW, 4, ARR, EXT>(A, st, thr) : launch_form<4, ZW, 8, ARR, EXT>(A, st, thr);
+}
+
 template <bool ARR, int EXT>
 int launch_plan(const MomArgs& A, hipStream_t st, const Plan& p, bool thr) {
     if (p.vec == 4) {
-        switch (p.zw * 16 + p.u) {
-            case 1 * 16 + 2: return launch_main<4, 1, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 1 * 16 + 4: return launch_main<4, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 1 * 16 + 8: return launch_main<4, 1, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 4 * 16 + 2: return launch_main<4, 4, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 4 * 16 + 4: return launch_main<4, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 4 * 16 + 8: return launch_main<4, 4, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 8 * 16 + 2: return launch_main<4, 8, 2, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            case 8 * 16 + 4: return launch_main<4, 8, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-            default: return launch_main<4, 8, 8, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-        }
+        if (p.zw == 1) return launch_vec4<1, ARR, EXT>(A, st, p, thr);
+        return p.zw == 4 ? launch_vec4<4, ARR, EXT>(A, st, p, thr) : launch_vec4<8, ARR, EXT>(A, st, p, thr);
     }
-    if (p.vec == 2) return p.zw > 1 ? launch_main<2, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u) : launch_main<2, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
-    return p.zw > 1 ? launch_main<1, 4, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u) : launch_main<1, 1, 4, ARR, EXT>(A, st, thr, p.mask_first, p.bits, p.list_u, p.vlist_u);
+    if (p.vec == 2) return p.zw > 1 ? launch_form<2, 4, 4, ARR, EXT>(A, st, thr) : launch_form<2, 1, 4, ARR, EXT>(A, st, thr);
+    return p.zw > 1 ? launch_form<1, 4, 4, ARR, EXT>(A, st, thr) : launch_form<1, 1, 4, ARR, EXT>(A, st, thr);
 }
 
 Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     Plan p;
     p.bits = nullptr;
-    p.list_u = 0;
-    p.vlist_u = 0;
+    p.ext = ext;
+    const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
     auto aligned = [&](int v) {
-        const bool arr = (m.flags & SPC_MASK_ARRAY) != 0;
         return (c->nx % v == 0) && (c->row_stride % v == 0) && (c->plane_stride % v == 0) &&
                (((uintptr_t)c->d_data) % (4 * v) == 0) &&
                (!arr || ((m.row_stride % v == 0) && (m.plane_stride % v == 0) && (((uintptr_t)m.arr) % v == 0)));
@@ -721,9 +696,8 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     while (vec > 1 && !aligned(vec)) vec >>= 1;
     p.vec = vec;
     // MI355X sweeps at 1024^3 (tools/tune_moments.py; profiles/r01_tune_moments.log, r04_moments_issue.log)
-    const bool arr_ = (m.flags & SPC_MASK_ARRAY) != 0;
-    (void)arr_;
-    p.mask_first = spc_switch("SPC_MOMENTS_MASK_FIRST", 1) != 0;   // 0: the loop that loads every sample (16-byte lanes with a mask array)
+    // SPC_MOMENTS_MASK_FIRST=0: the loop that loads every sample, also where the mask could be read first
+    p.form = arr && vec == 4 && spc_switch("SPC_MOMENTS_MASK_FIRST", 1) != 0 ? kMaskFirst : kEverything;
     p.u = spc_switch("SPC_MOMENTS_U", ext ? 2 : 8);
     if (p.u != 2 && p.u != 4 && p.u != 8) p.u = 4;
     const int64_t ngroups = c->ny * (c->nx / p.vec);
@@ -744,305 +718,6 @@ Plan make_plan(const spc_cube_f32* c, const MaskDev& m, bool ext) {
     return p;
 }
 
-// ---- the mask array as bits (layout: include/spcube_hip.h) ---------------------------------------------------
-// Lane group g = y * (nx / 4) + x / 4 as in moments_kernel<4, ...>; block b = g / 64, lane l = g % 64; the 32 bytes of plane z
-// of block b at (b * nz + z) * 32, lane l in nibble (l & 1) of byte l >> 1.  Nothing of a launch plan enters.
-struct PackArgs {
-    const uint8_t* arr;
-    int64_t nz, row_stride, plane_stride;
-    int64_t groups_per_row, ngroups;
-    uint8_t* bits;
-};
-
-constexpr int kPackPlanes = 8;   // planes per wave and step: 8 x 32 = 256 contiguous bytes of bits, one dword per lane
-
-// One wave = one block of 64 lane groups, eight planes per step.  A lane reads its mask dword of each plane and makes the
-// nibble; the eight lanes that share a dword of the bits (lanes 8 j .. 8 j + 7 -> bytes 4 j .. 4 j + 3) OR their shifted nibbles
-// together by three neighbour exchanges, after which each of them holds the dword of every plane; lane 8 j + p stores plane p's.
-// A wave's store covers the 256 bytes of its eight planes.  Dead lanes (g >= ngroups) contribute zero bits; planes past nz
-// are neither read nor stored.
-__global__ __launch_bounds__(256) void mask_pack_bits_kernel(const PackArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t blk = blockIdx.x;
-    const int64_t g = blk * kLanes + lane;
-    const bool live = g < A.ngroups;
-    const int64_t gg = live ? g : 0;
-    const int64_t y = gg / A.groups_per_row;
-    const int64_t x = (gg - y * A.groups_per_row) * 4;
-    const uint8_t* pm = A.arr + y * A.row_stride + x;
-    const int64_t nsteps = (A.nz + kPackPlanes - 1) / kPackPlanes;
-    const int p_mine = lane & 7;
-    for (int64_t s = (int64_t)blockIdx.y * 4 + w; s < nsteps; s += (int64_t)gridDim.y * 4) {
-        const int64_t z0 = s * kPackPlanes;
-        uint32_t m[kPackPlanes];
-#pragma unroll
-        for (int p = 0; p < kPackPlanes; ++p) {
-            m[p] = 0;
-            if (live && z0 + p < A.nz)                               // z0 + p < nz: wave-uniform
-                m[p] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(pm + (z0 + p) * A.plane_stride));
-        }
-        uint32_t mine = 0;
-#pragma unroll
-        for (int p = 0; p < kPackPlanes; ++p) {
-            uint32_t n = ((m[p] & 0xffu) != 0 ? 1u : 0u) | ((m[p] & 0xff00u) != 0 ? 2u : 0u) |
-                         ((m[p] & 0xff0000u) != 0 ? 4u : 0u) | ((m[p] & 0xff000000u) != 0 ? 8u : 0u);
-            n <<= 4 * (lane & 7);
-            n |= __shfl_xor(n, 1);
-            n |= __shfl_xor(n, 2);
-            n |= __shfl_xor(n, 4);
-            if (p == p_mine) mine = n;
-        }
-        if (z0 + p_mine < A.nz)
-            *reinterpret_cast<uint32_t*>(A.bits + (blk * A.nz + z0 + p_mine) * 32 + (lane >> 3) * 4) = mine;
-    }
-}
-
-size_t mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx) {
-    if (nz <= 0 || ny <= 0 || nx <= 0 || nx % 4 != 0) return 0;
-    const int64_t ngroups = ny * (nx / 4);
-    return (size_t)((ngroups + kLanes - 1) / kLanes) * (size_t)nz * 32;
-}
-
-// ---- the list of included lane segments (layout: include/spcube_hip.h) -----------------------------------------
-// One wave per sublist s = b * nsub + j, j = split * zw + w: it marches the planes wave w of split `split` of block b marches
-// in moments_kernel, reading the lane's nibble of the bits as the BITS form does.
-struct ListArgs {
-    const uint8_t* bits;
-    int64_t nz, zchunk, nsub, total;   // total = nblocks * nsub
-    int zw;
-    uint32_t* len;                     // count: the longest lane's included planes ...
-    uint32_t* lines;                   // ... and the non-zero 32-bit words of the sublist's bits rows
-    const float* cube;                 // fill
-    int64_t row_stride, plane_stride, groups_per_row, ngroups;
-    const uint64_t* off;
-    const uint32_t* flen;
-    f32x4* samples;
-    uint32_t* meta;
-    uint64_t rows;
-};
-
-constexpr int kListWaves = 4;          // sublists per block of the count and fill kernels
-constexpr int kListBatch = 8;          // planes in flight per lane
-
-__global__ __launch_bounds__(kLanes * kListWaves) void list_count_kernel(const ListArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (s >= A.total) return;                                        // wave-uniform
-    const int64_t b = s / A.nsub;
-    const int j = (int)(s - b * A.nsub);
-    const int split = j / A.zw, w = j - split * A.zw;
-    const int64_t zb = (int64_t)split * A.zchunk;
-    const int64_t ze = min(A.nz, zb + A.zchunk);
-    const uint8_t* q = A.bits + b * A.nz * 32 + (lane >> 1);
-    const int sh = (lane & 1) * 4;
-    uint32_t cnt = 0, lines = 0;
-    auto take = [&](uint32_t byte) {
-        const bool inc = ((byte >> sh) & 0xfu) != 0;
-        cnt += inc ? 1u : 0u;
-        // eight lanes share a 32-bit word of the bits and a 128-byte line of the cube: bit 0 of every byte of the ballot after the folds
-        unsigned long long any = __ballot(inc);
-        any |= any >> 1;
-        any |= any >> 2;
-        any |= any >> 4;
-        lines += (uint32_t)__popcll(any & 0x0101010101010101ULL);
-    };
-    int64_t z = zb + w;
-    for (; z + (int64_t)(kListBatch - 1) * A.zw < ze; z += (int64_t)kListBatch * A.zw) {
-        uint32_t byte[kListBatch];
-#pragma unroll
-        for (int u = 0; u < kListBatch; ++u) byte[u] = q[(z + (int64_t)u * A.zw) * 32];
-#pragma unroll
-        for (int u = 0; u < kListBatch; ++u) take(byte[u]);
-    }
-    for (; z < ze; z += A.zw) take(q[z * 32]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt = max(cnt, (uint32_t)__shfl_xor((int)cnt, o));
-    if (lane == 0) {
-        A.len[s] = cnt;
-        A.lines[s] = lines;
-    }
-}
-
-__global__ __launch_bounds__(kLanes * kListWaves) void list_fill_kernel(const ListArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (s >= A.total) return;                                        // wave-uniform
-    const int64_t b = s / A.nsub;
-    const int j = (int)(s - b * A.nsub);
-    const int split = j / A.zw, w = j - split * A.zw;
-    const int64_t zb = (int64_t)split * A.zchunk;
-    const int64_t ze = min(A.nz, zb + A.zchunk);
-    const int64_t g = b * kLanes + lane;
-    const bool live = g < A.ngroups;                                 // dead lanes load nothing and hold only padding
-    const int64_t gg = live ? g : 0;
-    const int64_t y = gg / A.groups_per_row;
-    const int64_t x = (gg - y * A.groups_per_row) * 4;
-    const float* p = A.cube + y * A.row_stride + x;
-    const uint8_t* q = A.bits + b * A.nz * 32 + (lane >> 1);
-    const int sh = (lane & 1) * 4;
-    // the rows of this sublist, cut to what the arrays hold whatever off and len say
-    const uint64_t row0 = A.off[s];
-    uint32_t n = A.flen[s];
-    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
-    if (n > room) n = (uint32_t)room;
-    f32x4* ps = A.samples + row0 * kLanes + lane;
-    uint32_t* pq = A.meta + row0 * kLanes + lane;
-    uint32_t k = 0;                                                  // the lane's own running index
-    auto put = [&](const f32x4& v, uint32_t nib, int64_t z) {
-        if (nib != 0 && k < n) {
-            ps[(uint64_t)k * kLanes] = v;
-            pq[(uint64_t)k * kLanes] = (uint32_t)z | (nib << 28);
-            ++k;
-        }
-    };
-    int64_t z = zb + w;
-    for (; z + (int64_t)(kListBatch - 1) * A.zw < ze; z += (int64_t)kListBatch * A.zw) {
-        uint32_t nib[kListBatch];
-        f32x4 v[kListBatch];
-#pragma unroll
-        for (int u = 0; u < kListBatch; ++u) nib[u] = live ? (uint32_t)(q[(z + (int64_t)u * A.zw) * 32] >> sh) & 0xfu : 0u;
-#pragma unroll
-        for (int u = 0; u < kListBatch; ++u) {
-            v[u] = f32x4{};
-            if (nib[u] != 0) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + (z + (int64_t)u * A.zw) * A.plane_stride));
-        }
-#pragma unroll
-        for (int u = 0; u < kListBatch; ++u) put(v[u], nib[u], z + (int64_t)u * A.zw);
-    }
-    for (; z < ze; z += A.zw) {
-        const uint32_t nib = live ? (uint32_t)(q[z * 32] >> sh) & 0xfu : 0u;
-        f32x4 v{};
-        if (nib != 0) v = *reinterpret_cast<const f32x4*>(p + z * A.plane_stride);
-        put(v, nib, z);
-    }
-    // padding: samples 0, meta 0 - a plane the mask excludes
-    for (; k < n; ++k) {
-        ps[(uint64_t)k * kLanes] = f32x4{};
-        pq[(uint64_t)k * kLanes] = 0u;
-    }
-}
-
-// ---- the voxel list, made from a list (layout: include/spcube_hip.h, spc_moments_vlist_*) -------------------------
-// One wave per sublist of the list, the list's rows read coalesced; neither kernel reads the cube or the bits.
-struct VlistArgs {
-    const uint32_t* meta;              // the list: [rows][64] z | nibble << 28 ...
-    const f32x4* samples;              // ... and [rows][64] the lane's four samples (fill)
-    const uint64_t* off;
-    const uint32_t* len;
-    uint64_t rows;
-    int64_t total;                     // nblocks * nsub
-    uint32_t* vlen_out;                // count: the longest lane's included voxels
-    const uint64_t* voff;              // fill
-    const uint32_t* vlen;
-    u32x2* entries;
-    uint64_t vrows;
-};
-
-constexpr int kVlistBatch = 8;         // list rows in flight per lane of the count kernel
-constexpr int kVlistFillBatch = 4;     // ... and of the fill kernel (20 bytes a row)
-constexpr int kVlistLongSublist = 128; // mean rows per sublist from which the sums and count forms keep 16 rows in flight (moments_run)
-
-__global__ __launch_bounds__(kLanes * kListWaves) void vlist_count_kernel(const VlistArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (s >= A.total) return;                                        // wave-uniform
-    // the rows of this sublist, cut to what the list holds whatever off and len say
-    const uint64_t row0 = A.off[s];
-    uint32_t n = A.len[s];
-    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
-    if (n > room) n = (uint32_t)room;
-    const uint32_t* pq = A.meta + row0 * kLanes + lane;
-    uint32_t cnt = 0, k = 0;
-    for (; k + kVlistBatch <= n; k += kVlistBatch, pq += kVlistBatch * kLanes) {
-        uint32_t mt[kVlistBatch];
-#pragma unroll
-        for (int u = 0; u < kVlistBatch; ++u) mt[u] = __builtin_nontemporal_load(pq + u * kLanes);
-#pragma unroll
-        for (int u = 0; u < kVlistBatch; ++u) cnt += (uint32_t)__popc(mt[u] >> 28);
-    }
-    for (; k < n; ++k, pq += kLanes) cnt += (uint32_t)__popc(*pq >> 28);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt = max(cnt, (uint32_t)__shfl_xor((int)cnt, o));
-    if (lane == 0) A.vlen_out[s] = cnt;
-}
-
-__global__ __launch_bounds__(kLanes * kListWaves) void vlist_fill_kernel(const VlistArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * kListWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (s >= A.total) return;                                        // wave-uniform
-    // the rows read and the rows written, each cut to what its arrays hold whatever the offsets and lengths say
-    const uint64_t row0 = A.off[s];
-    uint32_t n = A.len[s];
-    const uint64_t room = row0 < A.rows ? A.rows - row0 : 0;
-    if (n > room) n = (uint32_t)room;
-    const uint64_t vrow0 = A.voff[s];
-    uint32_t vn = A.vlen[s];
-    const uint64_t vroom = vrow0 < A.vrows ? A.vrows - vrow0 : 0;
-    if (vn > vroom) vn = (uint32_t)vroom;
-    const uint32_t* pq = A.meta + row0 * kLanes + lane;
-    const f32x4* ps = A.samples + row0 * kLanes + lane;
-    u32x2* pe = A.entries + vrow0 * kLanes + lane;
-    uint32_t kv = 0;                                                 // the lane's own running row
-    auto put = [&](const f32x4& v, uint32_t mt) {
-        const uint32_t z = mt & 0x0fffffffu;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (((mt >> (28 + i)) & 1u) != 0 && kv < vn) {
-                u32x2 e;
-                e.x = __float_as_uint(v[i]);
-                e.y = z | ((uint32_t)i << 28) | (1u << 30);
-                pe[(uint64_t)kv * kLanes] = e;
-                ++kv;
-            }
-        }
-    };
-    uint32_t k = 0;
-    for (; k + kVlistFillBatch <= n; k += kVlistFillBatch, pq += kVlistFillBatch * kLanes, ps += kVlistFillBatch * kLanes) {
-        uint32_t mt[kVlistFillBatch];
-        f32x4 v[kVlistFillBatch];
-#pragma unroll
-        for (int u = 0; u < kVlistFillBatch; ++u) mt[u] = __builtin_nontemporal_load(pq + u * kLanes);
-#pragma unroll
-        for (int u = 0; u < kVlistFillBatch; ++u) v[u] = __builtin_nontemporal_load(ps + u * kLanes);
-#pragma unroll
-        for (int u = 0; u < kVlistFillBatch; ++u) put(v[u], mt[u]);
-    }
-    for (; k < n; ++k, pq += kLanes, ps += kLanes) {
-        const uint32_t mt = *pq;
-        const f32x4 v = *ps;
-        put(v, mt);
-    }
-    // padding: all zero, bit 30 clear - not an entry
-    for (; kv < vn; ++kv) pe[(uint64_t)kv * kLanes] = u32x2{0u, 0u};
-}
-
-// the list a voxel list is counted and filled from: its desc a plan, its arrays holding the rows it names (with_samples: fill)
-int vlist_source_check(const spc_moments_list* list, bool with_samples, int64_t* total) {
-    SPC_REQUIRE(list != nullptr, "list is NULL");
-    const spc_moments_list_desc& d = list->desc;
-    SPC_REQUIRE((d.zw == 1 || d.zw == 4 || d.zw == 8) && d.nsplit >= 1 && d.zchunk >= 1 && d.nsub == (int64_t)d.nsplit * d.zw &&
-                d.nblocks >= 1 && d.nblocks < (1LL << 31), "the list's desc is not a launch plan");
-    *total = d.nblocks * d.nsub;
-    SPC_REQUIRE((*total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
-    SPC_REQUIRE(list->d_off != nullptr && list->d_len != nullptr && list->nsublists >= (size_t)*total,
-                "the list's d_off and d_len: %zu entries given, %lld sublists", list->nsublists, (long long)*total);
-    SPC_REQUIRE(list->rows == 0 || (list->d_meta != nullptr && (!with_samples || list->d_samples != nullptr)),
-                "the list's d_samples or d_meta is NULL");
-    SPC_REQUIRE(list->meta_bytes / 256 >= list->rows && (!with_samples || list->samples_bytes / 1024 >= list->rows),
-                "the list's d_samples / d_meta too small for %llu rows (1024 and 256 bytes each)", (unsigned long long)list->rows);
-    SPC_REQUIRE(spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4) &&
-                (!with_samples || spc_aligned(list->d_samples, 16)),
-                "the list's d_samples must be 16-byte, d_off 8-byte, d_meta and d_len 4-byte aligned");
-    return SPC_OK;
-}
-
-bool same_desc(const spc_moments_list_desc& d, const spc_moments_list_desc& l) {
-    return d.zw == l.zw && d.nsplit == l.nsplit && d.zchunk == l.zchunk && d.nblocks == l.nblocks && d.nsub == l.nsub;
-}
-
-constexpr int64_t kListMaxNz = 1LL << 28;      // z shares its meta word with the nibble
-
 // what every moments entry works out before it launches: the checks, the kernel arguments, the plan after the workspace
 // fallback and whether the launch reads the packed mask
 int moments_setup(const spc_cube_f32* cube, const spc_mask* mask, const double* d_cen, bool need_cen, double dv, double m1_add,
@@ -1061,28 +736,25 @@ int moments_setup(const spc_cube_f32* cube, const spc_mask* mask, const double* 
     A.cen = d_cen; A.dv = dv; A.m1_add = m1_add;
     A.out = *out;
     A.out_row_stride = out->out_row_stride ? out->out_row_stride : cube->nx;
-    const bool ext = out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin;
-    p = make_plan(cube, A.mask, ext);
+    p = make_plan(cube, A.mask, out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin);
     spc_canonical_pred(A.mask.flags, A.mask.thr_lo, A.mask.thr_hi, &A.lim, &A.lo, &A.hi);
     A.xcd_group = spc_switch("SPC_MOMENTS_XCD", 0);    // measured: +- 1 % either way on the real kernel (profiles/r04_moments_issue.log)
     A.groups_per_row = cube->nx / p.vec;
     A.ngroups = cube->ny * A.groups_per_row;
-    A.nsplit = p.nsplit;
-    A.zchunk = p.zchunk;
     A.ws = (double*)d_workspace;
     if (p.nsplit > 1) {
         const size_t need = (size_t)p.nsplit * kWsFields * sizeof(double) * (size_t)(cube->ny * cube->nx);
         if (!d_workspace || workspace_bytes < need) {
             // not enough workspace: fall back to a single z range (still correct)
-            A.nsplit = 1; A.zchunk = cube->nz; p.nsplit = 1; p.zchunk = cube->nz;
+            p.nsplit = 1; p.zchunk = cube->nz;
         }
     }
-    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
+    A.nsplit = p.nsplit;
+    A.zchunk = p.zchunk;
     // the packed mask only where the launch is the mask-first march of 16-byte lanes; everything else reads the bytes as before
-    p.bits = nullptr;
-    if (d_mask_bits && arr && p.vec == 4 && p.mask_first && spc_switch("SPC_MOMENTS_MASK_BITS", 1) != 0) {
+    if (d_mask_bits && p.form == kMaskFirst && spc_switch("SPC_MOMENTS_MASK_BITS", 1) != 0) {
         const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
-        if (need && bits_bytes >= need) p.bits = (const uint8_t*)d_mask_bits;
+        if (need && bits_bytes >= need) { p.form = kBits; p.bits = (const uint8_t*)d_mask_bits; }
     }
     return SPC_OK;
 }
@@ -1090,17 +762,16 @@ int moments_setup(const spc_cube_f32* cube, const spc_mask* mask, const double* 
 // the plan of a launch as a list is made for it
 spc_moments_list_desc list_desc(const MomArgs& A, const Plan& p) {
     spc_moments_list_desc d;
-    d.zw = p.zw; d.nsplit = A.nsplit; d.zchunk = A.zchunk;
+    d.zw = p.zw; d.nsplit = p.nsplit; d.zchunk = p.zchunk;
     d.nblocks = (A.ngroups + kLanes - 1) / kLanes;
-    d.nsub = (int64_t)A.nsplit * p.zw;
+    d.nsub = (int64_t)p.nsplit * p.zw;
     return d;
 }
 
 // there is a list for this launch: the march of 16-byte lanes over the packed mask (have_bits: the bits were given and are
 // read; without them the same conditions on the plan alone), short enough for z to share a word with the nibble
 int list_exists(const MomArgs& A, const Plan& p, bool have_bits, const char* who) {
-    const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
-    if (!arr || p.vec != 4 || !p.mask_first || A.nz >= kListMaxNz || (have_bits && !p.bits) ||
+    if (p.form == kEverything || A.nz >= kListMaxNz || (have_bits && p.form != kBits) ||
         spc_switch("SPC_MOMENTS_MASK_BITS", 1) == 0 || spc_switch("SPC_MOMENTS_LIST", 1) == 0) {
         spc_set_error("%s: no list for this launch (it needs a mask array read as bits by the mask-first march of 16-byte lanes, "
                       "nz < 2^28 and SPC_MOMENTS_LIST not 0)", who);
@@ -1117,32 +788,26 @@ int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_ma
     int rc = moments_setup(cube, mask, d_cen, true, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
     if (rc) return rc;
     SPC_DEVICE(device);
-    const bool ext = out->d_argmax || out->d_argmin || out->d_vmax || out->d_vmin;
     const bool thr = (A.mask.flags & (SPC_MASK_GT | SPC_MASK_GE | SPC_MASK_LT | SPC_MASK_LE)) != 0;
     const bool arr = (A.mask.flags & SPC_MASK_ARRAY) != 0;
-    // the list only where it was made for exactly this plan and its arrays hold the rows it names; otherwise the bits march
-    if (list && p.bits && A.nz < kListMaxNz && spc_switch("SPC_MOMENTS_LIST", 1) != 0) {
+    // a list or a voxel list only where the launch reads the bits, it was made for exactly this plan and all its arrays are there
+    // and hold the rows it names (otherwise what the call was without it); a voxel list that passes goes before the list
+    if (p.form == kBits && A.nz < kListMaxNz && spc_switch("SPC_MOMENTS_LIST", 1) != 0) {
         const spc_moments_list_desc d = list_desc(A, p);
-        const spc_moments_list_desc& l = list->desc;
-        const bool same = d.zw == l.zw && d.nsplit == l.nsplit && d.zchunk == l.zchunk && d.nblocks == l.nblocks && d.nsub == l.nsub;
-        if (same && list->d_samples && list->d_meta && list->d_off && list->d_len && list->nsublists >= (size_t)(d.nblocks * d.nsub) &&
-            list->samples_bytes / 1024 >= list->rows && list->meta_bytes / 256 >= list->rows &&
-            spc_aligned(list->d_samples, 16) && spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4)) {
+        const int64_t total = d.nblocks * d.nsub;
+        if (list && same_desc(d, list->desc) && list->d_samples && list->d_meta && !list_arrays_bad(*list, total, true)) {
+            p.form = kList;
             A.list_samples = (const f32x4*)list->d_samples;
             A.list_meta = (const uint32_t*)list->d_meta;
             A.list_off = list->d_off;
             A.list_len = list->d_len;
             A.list_rows = list->rows;
             // rows in flight per lane (profiles/moments_list_bench.txt)
-            p.list_u = spc_switch("SPC_MOMENTS_LIST_U", ext ? 4 : 8) == 4 ? 4 : 8;
+            p.u = spc_switch("SPC_MOMENTS_LIST_U", p.ext ? 4 : 8) == 4 ? 4 : 8;
         }
-    }
-    // the voxel list under the same conditions, for exactly this plan; otherwise what the call was without it
-    if (vlist && p.bits && A.nz < kListMaxNz && spc_switch("SPC_MOMENTS_LIST", 1) != 0 && spc_switch("SPC_MOMENTS_VLIST", 1) != 0) {
-        const spc_moments_list_desc d = list_desc(A, p);
-        if (same_desc(d, vlist->desc) && vlist->d_entries && vlist->d_off && vlist->d_len && vlist->nsublists >= (size_t)(d.nblocks * d.nsub) &&
-            vlist->entries_bytes / 512 >= vlist->rows && spc_aligned(vlist->d_entries, 8) && spc_aligned(vlist->d_off, 8) &&
-            spc_aligned(vlist->d_len, 4)) {
+        if (vlist && spc_switch("SPC_MOMENTS_VLIST", 1) != 0 && same_desc(d, vlist->desc) && vlist->d_entries &&
+            !vlist_arrays_bad(*vlist, total)) {
+            p.form = kVlist;
             A.list_samples = (const f32x4*)vlist->d_entries;     // (MomArgs: the voxel-list forms read the list's fields)
             A.list_meta = nullptr;
             A.list_off = vlist->d_off;
@@ -1151,13 +816,12 @@ int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_ma
             // rows in flight per lane (profiles/moments_vlist_bench.txt): the U = 16 forms hold 142 - 148 VGPRs, three waves per SIMD
             // against five, and pay only where a sublist is many batches long - 180 rows on average at the north star (5 % faster
             // than U = 8), not at 38 or 70 rows (27 % and 20 % slower); with extrema U = 8 wins at every shape measured
-            const uint64_t nsublists = (uint64_t)(d.nblocks * d.nsub);
-            const bool long_sublists = vlist->rows / nsublists >= (uint64_t)kVlistLongSublist;
-            p.vlist_u = spc_switch("SPC_MOMENTS_VLIST_U", !ext && long_sublists ? 16 : 8) == 16 ? 16 : 8;
+            const bool long_sublists = vlist->rows / (uint64_t)total >= (uint64_t)kVlistLongSublist;
+            p.u = spc_switch("SPC_MOMENTS_VLIST_U", !p.ext && long_sublists ? 16 : 8) == 16 ? 16 : 8;
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    const int what = ext ? kExtrema : (out->d_nvalid ? kCount : kSums);
+    const int what = p.ext ? kExtrema : (out->d_nvalid ? kCount : kSums);
     if (arr) rc = what == kExtrema ? launch_plan<true, kExtrema>(A, st, p, thr)
                 : what == kCount ? launch_plan<true, kCount>(A, st, p, thr) : launch_plan<true, kSums>(A, st, p, thr);
     else rc = what == kExtrema ? launch_plan<false, kExtrema>(A, st, p, thr)
@@ -1166,7 +830,7 @@ int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_ma
     if (A.nsplit > 1) {
         const int64_t ncols = cube->ny * cube->nx;
         dim3 grid((unsigned)((ncols + 255) / 256));
-        if (ext) hipLaunchKernelGGL(moments_combine_kernel<kExtrema>, grid, dim3(256), 0, st, A, p.vec);
+        if (p.ext) hipLaunchKernelGGL(moments_combine_kernel<kExtrema>, grid, dim3(256), 0, st, A, p.vec);
         else hipLaunchKernelGGL(moments_combine_kernel<kCount>, grid, dim3(256), 0, st, A, p.vec);
         SPC_LAUNCH_CHECK();
     }
@@ -1175,38 +839,22 @@ int moments_run(int device, void* stream, const spc_cube_f32* cube, const spc_ma
 
 }  // namespace
 
-extern "C" {
-
-size_t spc_mask_bits_bytes(int64_t nz, int64_t ny, int64_t nx) { return mask_bits_bytes(nz, ny, nx); }
-
-int spc_mask_pack_bits(int device, void* stream, int64_t nz, int64_t ny, int64_t nx, const spc_mask* mask,
-                       void* d_bits, size_t bits_bytes) {
-    SPC_REQUIRE(nz > 0 && ny > 0 && nx > 0, "mask shape must be positive (got %lld,%lld,%lld)", (long long)nz, (long long)ny, (long long)nx);
-    SPC_REQUIRE(mask != nullptr && (mask->flags & SPC_MASK_ARRAY) && mask->d_array != nullptr, "no mask array to pack");
-    SPC_REQUIRE(d_bits != nullptr, "d_bits is NULL");
-    const size_t need = mask_bits_bytes(nz, ny, nx);
-    const int64_t rs = mask->row_stride ? mask->row_stride : nx, ps = mask->plane_stride ? mask->plane_stride : ny * nx;
-    SPC_REQUIRE(rs >= nx && ps >= rs * (ny - 1) + nx, "mask strides smaller than the shape");
-    // the lanes read dwords: the conditions of make_plan's aligned(4) for the mask
-    if (need == 0 || rs % 4 != 0 || ps % 4 != 0 || !spc_aligned(mask->d_array, 4) || !spc_aligned(d_bits, 4)) {
-        spc_set_error("spc_mask_pack_bits: nx, the mask's strides and its address must be multiples of 4");
-        return SPC_ERR_UNSUPPORTED;
-    }
-    SPC_REQUIRE(bits_bytes >= need, "d_bits too small: %zu bytes given, %zu needed (spc_mask_bits_bytes)", bits_bytes, need);
-    SPC_DEVICE(device);
-    PackArgs A{};
-    A.arr = mask->d_array; A.nz = nz; A.row_stride = rs; A.plane_stride = ps;
-    A.groups_per_row = nx / 4; A.ngroups = ny * A.groups_per_row;
-    A.bits = (uint8_t*)d_bits;
-    const int64_t nblocks = (A.ngroups + kLanes - 1) / kLanes;
-    SPC_REQUIRE(nblocks < (1LL << 31), "mask too large");
-    // enough blocks to fill the chip when the map alone is small; four waves of a block take interleaved steps
-    const int64_t nsteps = (nz + kPackPlanes - 1) / kPackPlanes;
-    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nsteps + 3) / 4, (4096 + nblocks - 1) / nblocks), 65535));
-    hipLaunchKernelGGL(mask_pack_bits_kernel, dim3((unsigned)nblocks, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, A);
-    SPC_LAUNCH_CHECK();
+// (spc_moments_forms.h) for spc_moments_list_plan_f32 below and spc_moments_list_count_f32 in spc_moments_forms.hip
+int spc_moments_list_launch(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out, const void* d_workspace,
+                            size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes, const char* who,
+                            spc_moments_list_desc* desc, const uint8_t** bits) {
+    MomArgs A{};
+    Plan p;
+    int rc = moments_setup(cube, mask, nullptr, false, 0.0, 0.0, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
+    if (rc) return rc;
+    rc = list_exists(A, p, d_mask_bits != nullptr, who);
+    if (rc) return rc;
+    *desc = list_desc(A, p);
+    if (bits) *bits = p.bits;
     return SPC_OK;
 }
+
+extern "C" {
 
 size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
     if (nz <= 0 || ny <= 0 || nx <= 0) return 0;
@@ -1223,7 +871,7 @@ size_t spc_moments_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
 int spc_moments_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                     const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                     void* d_workspace, size_t workspace_bytes) {
-    return spc_moments_bits_f32(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, nullptr, 0);
+    return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, nullptr, 0, nullptr, nullptr);
 }
 
 int spc_moments_bits_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
@@ -1239,91 +887,6 @@ int spc_moments_list_f32(int device, void* stream, const spc_cube_f32* cube, con
     return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list, nullptr);
 }
 
-int spc_moments_list_plan_f32(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out,
-                              const void* d_workspace, size_t workspace_bytes, spc_moments_list_desc* desc) {
-    SPC_REQUIRE(desc != nullptr, "desc is NULL");
-    MomArgs A{};
-    Plan p;
-    int rc = moments_setup(cube, mask, nullptr, false, 0.0, 0.0, out, d_workspace, workspace_bytes, nullptr, 0, A, p);
-    if (rc) return rc;
-    rc = list_exists(A, p, false, "spc_moments_list_plan_f32");
-    if (rc) return rc;
-    *desc = list_desc(A, p);
-    return SPC_OK;
-}
-
-int spc_moments_list_count_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
-                               const spc_moment_outputs* out, const void* d_workspace, size_t workspace_bytes,
-                               const void* d_mask_bits, size_t bits_bytes, uint32_t* d_len, uint32_t* d_lines,
-                               size_t nsublists, spc_moments_list_desc* desc) {
-    SPC_REQUIRE(desc != nullptr, "desc is NULL");
-    SPC_REQUIRE(d_mask_bits != nullptr, "d_mask_bits is NULL");
-    SPC_REQUIRE(d_len != nullptr && d_lines != nullptr, "d_len or d_lines is NULL");
-    MomArgs A{};
-    Plan p;
-    int rc = moments_setup(cube, mask, nullptr, false, 0.0, 0.0, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, A, p);
-    if (rc) return rc;
-    rc = list_exists(A, p, true, "spc_moments_list_count_f32");
-    if (rc) return rc;
-    const spc_moments_list_desc d = list_desc(A, p);
-    const int64_t total = d.nblocks * d.nsub;
-    SPC_REQUIRE(nsublists >= (size_t)total, "d_len and d_lines too small: %zu entries given, %lld sublists", nsublists, (long long)total);
-    SPC_REQUIRE(spc_aligned(d_len, 4) && spc_aligned(d_lines, 4), "d_len and d_lines must be 4-byte aligned");
-    SPC_REQUIRE((total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
-    *desc = d;
-    SPC_DEVICE(device);
-    ListArgs L{};
-    L.bits = p.bits; L.nz = A.nz; L.zchunk = d.zchunk; L.nsub = d.nsub; L.total = total; L.zw = d.zw;
-    L.len = d_len; L.lines = d_lines;
-    hipLaunchKernelGGL(list_count_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
-                       (hipStream_t)stream, L);
-    SPC_LAUNCH_CHECK();
-    return SPC_OK;
-}
-
-int spc_moments_list_fill_f32(int device, void* stream, const spc_cube_f32* cube, const void* d_mask_bits, size_t bits_bytes,
-                              const spc_moments_list* list) {
-    int rc = spc_check_cube(cube);
-    if (rc) return rc;
-    SPC_REQUIRE(list != nullptr, "list is NULL");
-    SPC_REQUIRE(d_mask_bits != nullptr, "d_mask_bits is NULL");
-    SPC_REQUIRE(cube->nz < kListMaxNz, "nz too large for a list (%lld)", (long long)cube->nz);
-    // 16-byte lanes: make_plan's aligned(4) for the cube
-    if (cube->nx % 4 != 0 || cube->row_stride % 4 != 0 || cube->plane_stride % 4 != 0 || !spc_aligned(cube->d_data, 16)) {
-        spc_set_error("spc_moments_list_fill_f32: nx, the cube's strides and its address must be multiples of 4 elements");
-        return SPC_ERR_UNSUPPORTED;
-    }
-    const size_t need = mask_bits_bytes(cube->nz, cube->ny, cube->nx);
-    SPC_REQUIRE(need && bits_bytes >= need, "d_mask_bits too small: %zu bytes given, %zu needed (spc_mask_bits_bytes)", bits_bytes, need);
-    const spc_moments_list_desc& d = list->desc;
-    const int64_t ngroups = cube->ny * (cube->nx / 4);
-    SPC_REQUIRE((d.zw == 1 || d.zw == 4 || d.zw == 8) && d.nsplit >= 1 && d.zchunk >= 1 && d.nsub == (int64_t)d.nsplit * d.zw &&
-                d.nblocks == (ngroups + kLanes - 1) / kLanes, "desc is not a launch plan of this cube");
-    // the splits cover [0, nz) and none of them is empty
-    SPC_REQUIRE(d.zchunk <= cube->nz && (int64_t)(d.nsplit - 1) * d.zchunk < cube->nz && (int64_t)d.nsplit * d.zchunk >= cube->nz,
-                "desc: %d splits of %lld planes do not cover %lld planes", d.nsplit, (long long)d.zchunk, (long long)cube->nz);
-    const int64_t total = d.nblocks * d.nsub;
-    SPC_REQUIRE(list->d_off != nullptr && list->d_len != nullptr && list->nsublists >= (size_t)total,
-                "d_off and d_len: %zu entries given, %lld sublists", list->nsublists, (long long)total);
-    SPC_REQUIRE(list->rows == 0 || (list->d_samples != nullptr && list->d_meta != nullptr), "d_samples or d_meta is NULL");
-    SPC_REQUIRE(list->samples_bytes / 1024 >= list->rows && list->meta_bytes / 256 >= list->rows,
-                "d_samples / d_meta too small for %llu rows (1024 and 256 bytes each)", (unsigned long long)list->rows);
-    SPC_REQUIRE(spc_aligned(list->d_samples, 16) && spc_aligned(list->d_meta, 4) && spc_aligned(list->d_off, 8) && spc_aligned(list->d_len, 4),
-                "d_samples must be 16-byte, d_off 8-byte, d_meta and d_len 4-byte aligned");
-    SPC_REQUIRE((total + kListWaves - 1) / kListWaves < (1LL << 31), "too many sublists");
-    SPC_DEVICE(device);
-    ListArgs L{};
-    L.bits = (const uint8_t*)d_mask_bits; L.nz = cube->nz; L.zchunk = d.zchunk; L.nsub = d.nsub; L.total = total; L.zw = d.zw;
-    L.cube = cube->d_data; L.row_stride = cube->row_stride; L.plane_stride = cube->plane_stride;
-    L.groups_per_row = cube->nx / 4; L.ngroups = ngroups;
-    L.off = list->d_off; L.flen = list->d_len;
-    L.samples = (f32x4*)list->d_samples; L.meta = (uint32_t*)list->d_meta; L.rows = list->rows;
-    hipLaunchKernelGGL(list_fill_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
-                       (hipStream_t)stream, L);
-    SPC_LAUNCH_CHECK();
-    return SPC_OK;
-}
-
 int spc_moments_vlist_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,
                           const double* d_cen, double dv, double m1_add, const spc_moment_outputs* out,
                           void* d_workspace, size_t workspace_bytes, const void* d_mask_bits, size_t bits_bytes,
@@ -1331,45 +894,10 @@ int spc_moments_vlist_f32(int device, void* stream, const spc_cube_f32* cube, co
     return moments_run(device, stream, cube, mask, d_cen, dv, m1_add, out, d_workspace, workspace_bytes, d_mask_bits, bits_bytes, list, vlist);
 }
 
-int spc_moments_vlist_count_f32(int device, void* stream, const spc_moments_list* list, uint32_t* d_vlen, size_t nsublists) {
-    int64_t total = 0;
-    int rc = vlist_source_check(list, false, &total);
-    if (rc) return rc;
-    SPC_REQUIRE(d_vlen != nullptr, "d_vlen is NULL");
-    SPC_REQUIRE(nsublists >= (size_t)total, "d_vlen too small: %zu entries given, %lld sublists", nsublists, (long long)total);
-    SPC_REQUIRE(spc_aligned(d_vlen, 4), "d_vlen must be 4-byte aligned");
-    SPC_DEVICE(device);
-    VlistArgs V{};
-    V.meta = (const uint32_t*)list->d_meta; V.off = list->d_off; V.len = list->d_len; V.rows = list->rows; V.total = total;
-    V.vlen_out = d_vlen;
-    hipLaunchKernelGGL(vlist_count_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
-                       (hipStream_t)stream, V);
-    SPC_LAUNCH_CHECK();
-    return SPC_OK;
-}
-
-int spc_moments_vlist_fill_f32(int device, void* stream, const spc_moments_list* list, const spc_moments_vlist* vlist) {
-    int64_t total = 0;
-    int rc = vlist_source_check(list, true, &total);
-    if (rc) return rc;
-    SPC_REQUIRE(vlist != nullptr, "vlist is NULL");
-    SPC_REQUIRE(same_desc(list->desc, vlist->desc), "the voxel list's desc is not the list's");
-    SPC_REQUIRE(vlist->d_off != nullptr && vlist->d_len != nullptr && vlist->nsublists >= (size_t)total,
-                "d_off and d_len: %zu entries given, %lld sublists", vlist->nsublists, (long long)total);
-    SPC_REQUIRE(vlist->rows == 0 || vlist->d_entries != nullptr, "d_entries is NULL");
-    SPC_REQUIRE(vlist->entries_bytes / 512 >= vlist->rows, "d_entries too small for %llu rows (512 bytes each)",
-                (unsigned long long)vlist->rows);
-    SPC_REQUIRE(spc_aligned(vlist->d_entries, 8) && spc_aligned(vlist->d_off, 8) && spc_aligned(vlist->d_len, 4),
-                "d_entries and d_off must be 8-byte, d_len 4-byte aligned");
-    SPC_DEVICE(device);
-    VlistArgs V{};
-    V.meta = (const uint32_t*)list->d_meta; V.samples = (const f32x4*)list->d_samples;
-    V.off = list->d_off; V.len = list->d_len; V.rows = list->rows; V.total = total;
-    V.voff = vlist->d_off; V.vlen = vlist->d_len; V.entries = (u32x2*)vlist->d_entries; V.vrows = vlist->rows;
-    hipLaunchKernelGGL(vlist_fill_kernel, dim3((unsigned)((total + kListWaves - 1) / kListWaves)), dim3(kLanes * kListWaves), 0,
-                       (hipStream_t)stream, V);
-    SPC_LAUNCH_CHECK();
-    return SPC_OK;
+int spc_moments_list_plan_f32(const spc_cube_f32* cube, const spc_mask* mask, const spc_moment_outputs* out,
+                              const void* d_workspace, size_t workspace_bytes, spc_moments_list_desc* desc) {
+    SPC_REQUIRE(desc != nullptr, "desc is NULL");
+    return spc_moments_list_launch(cube, mask, out, d_workspace, workspace_bytes, nullptr, 0, "spc_moments_list_plan_f32", desc, nullptr);
 }
 
 int spc_moment_order_f32(int device, void* stream, const spc_cube_f32* cube, const spc_mask* mask,

@@ -12,8 +12,9 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, moments_forms
 from .device import DeviceArray, _sh
+from .moments_forms import _MomentsList, _MomentsVlist, _bits_lock, _cube_key, _switch_on, list_is_kept, vlist_is_kept
 
 
 @dataclass
@@ -21,28 +22,11 @@ class MaskSpec:
     """Device-evaluable mask (AND of the enabled terms); see SPC_MASK_* in
     include/spcube_hip.h and spectral_cube/masks.py:105-116, 425-435.
 
-    A spec that is used again is taken to describe the same mask: from its second use on, moments() reads the array term
-    as bits (spc_mask_pack_bits: an eighth of the bytes per launch), packed once and kept with the spec.  The bits are
-    keyed by the array's address, shape, strides and WRITE GENERATION (DeviceArray.mark_written: upload() and every
-    operator of this package that writes into a caller-given array advance it), so a mask rewritten that way is packed
-    again after two more uses.  Bytes changed behind the library's back - through the raw pointer, by a kernel of the
-    caller's - after a spec has been used twice need invalidate().  rows(), planes() and swap01() return specs of their
-    own, which pack for themselves on their second use.
-
-    A spec that is used again ON THE SAME CUBE goes one step further: the launch that finds the bits packed and the cube of
-    the launch before it (normally the third use) builds the list of the cube's 16-byte lane segments that the bits
-    include (spc_moments_list_*: include/spcube_hip.h) and later launches with the same launch plan read that list instead
-    of marching the cube - where the list is at most half of the bytes the march fetches; otherwise it is refused, once,
-    and the march goes on.  The list costs 1280 bytes of HBM per entry row (about 14 GB for a 4096 x 2048 x 2048 cube under
-    a 4 % mask) and lives as long as the spec.  The launch after that (normally the fourth use) compacts a kept, non-empty
-    list into the VOXEL list (spc_moments_vlist_*): one 8-byte entry per included voxel instead of a 20-byte entry per
-    included lane segment, kept only where it reads at most half of what the list does (vlist_is_kept: masks that keep about
-    one voxel of a segment; connected masks are refused, once, and stay on the list).  The list's arrays stay allocated
-    beside it (6 GB of voxel list beside 14 GB of list for that cube).  SPC_MOMENTS_VLIST=0 turns the voxel list off.
-    The list is keyed by the bits' key and the cube's root array BY IDENTITY, its address, shape, strides and write
-    generation: another cube, upload() into the cube or an operator of this package writing into it (out=, scale_inplace)
-    drop the list - the voxel list with it - and only them.  SAMPLES changed behind the library's back after a spec's second
-    use on the cube need invalidate() just as mask bytes do.  SPC_MOMENTS_LIST=0 turns the list off."""
+    A spec that is used again is taken to describe the same mask, and one used again on the same cube the same samples:
+    moments() then reads the array term as bits, as a list of the included lane segments, as a list of the included voxels
+    (moments_forms has the rules, the keys and the costs; the slots below are its state, changed under its lock).  Bytes or
+    samples changed behind the library's back - through the raw pointer, by a kernel of the caller's - after a spec's second
+    use need invalidate()."""
     flags: int = 0
     thr_lo: float = 0.0
     thr_hi: float = 0.0
@@ -52,12 +36,12 @@ class MaskSpec:
     _bits_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)
     _bits_uses: int = field(default=0, init=False, compare=False, repr=False)
     _bits_failed: bool = field(default=False, init=False, compare=False, repr=False)   # no form / no memory: stay with the bytes
-    # the list of the lane segments the bits include in ONE cube (moments(), _moments_list): beside the bits, under their lock
+    # the list of the lane segments the bits include in ONE cube (moments_forms.select): beside the bits, under their lock
     _list: Optional[object] = field(default=None, init=False, compare=False, repr=False)
     _list_key: Optional[tuple] = field(default=None, init=False, compare=False, repr=False)      # the cube of the launch before
     _list_root: Optional[object] = field(default=None, init=False, compare=False, repr=False)    # weakref to that cube's root array
     _list_failed: bool = field(default=False, init=False, compare=False, repr=False)   # refused / no form / no memory: the bits march
-    # the voxel list made from _list (_moments_vlist): dropped wherever the list is, under the same lock
+    # the voxel list made from _list (moments_forms.select): dropped wherever the list is, under the same lock
     _vlist: Optional[object] = field(default=None, init=False, compare=False, repr=False)
     _vlist_failed: bool = field(default=False, init=False, compare=False, repr=False)  # refused / switched off / no memory: the list
 
@@ -116,23 +100,6 @@ class MaskSpec:
 
 _F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
 
-_bits_lock = threading.Lock()        # dask `threads` workers share a spec: one of them packs
-
-
-def _switch_on(name, dflt=1):
-    """a library switch as spc_switch reads it: atoi of the value when set ("" and text that is no number: 0)"""
-    e = os.environ.get(name)
-    if e is None:
-        return dflt != 0
-    e = e.strip()
-    n = 0
-    while n < len(e) and (e[n].isdigit() or (n == 0 and e[n] in "+-")):
-        n += 1
-    try:
-        return int(e[:n]) != 0
-    except ValueError:
-        return False
-
 
 def _written(a):
     """the operator has queued a write into *a*, an array the caller may have given (or None): a MaskSpec that has packed
@@ -141,186 +108,6 @@ def _written(a):
     mark = getattr(a, "mark_written", None)
     if mark is not None:
         mark()
-
-
-def _mask_bits(mask, stream):
-    """the packed form of *mask*'s array term, or None: nothing on a spec's first use (a mask used once costs what it always
-    did), packed on *stream* on the second - the stream is waited for once, so that later launches on any stream may read
-    the bits - and handed out from then on, until the array's key or write generation changes"""
-    if mask is None or mask.array is None or not (mask.flags & _lib.MASK_ARRAY) or len(mask.array.shape) != 3:
-        return None
-    if not _switch_on("SPC_MOMENTS_MASK_BITS"):
-        return None
-    a = mask.array
-    nz, ny, nx = a.shape
-    key = (a.ptr, a.shape, getattr(a, "row_stride", nx), getattr(a, "plane_stride", ny * nx), a.write_generation)
-    with _bits_lock:
-        if mask._bits_key != key:
-            mask._drop_bits()
-            mask._bits_key = key
-        if mask._bits is not None or mask._bits_failed:
-            return mask._bits
-        mask._bits_uses += 1
-        if mask._bits_uses < 2:
-            return None
-        need = int(_lib.load().spc_mask_bits_bytes(nz, ny, nx))
-        if not need:
-            mask._bits_failed = True
-            return None
-        try:
-            bits = DeviceArray((need,), np.uint8, a.device)
-            m = mask.to_c()
-            _lib.call("spc_mask_pack_bits", a.device, _sh(stream), nz, ny, nx, C.byref(m), C.c_void_p(bits.ptr), need)
-            _lib.call("spc_stream_sync", a.device, _sh(stream))
-        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
-            mask._bits_failed = True         # never an error: the byte path goes on
-            return None
-        mask._bits = bits
-        return bits
-
-
-class _MomentsList:
-    """the device arrays of one list (spc_moments_list: include/spcube_hip.h) and the struct that names them"""
-
-    def __init__(self, desc, off, length, samples, meta, rows):
-        self.desc, self.off, self.len, self.samples, self.meta, self.rows = desc, off, length, samples, meta, int(rows)
-        c = self.c = _lib.SpcMomentsList()
-        c.desc = desc
-        c.d_samples, c.samples_bytes = samples.ptr, samples.nbytes
-        c.d_meta, c.meta_bytes = meta.ptr, meta.nbytes
-        c.d_off, c.d_len, c.nsublists = off.ptr, length.ptr, int(desc.nblocks * desc.nsub)
-        c.rows = self.rows
-
-    @property
-    def nbytes(self):
-        return self.rows * 1280
-
-
-def list_is_kept(rows, lines, nblocks, nz):
-    """the list is built only where it reads at most half of what the bits march fetches: 1280 bytes per entry row against
-    128 per fetched cube line and 32 of bits per block and plane.  A condition, not a tuning result: all-ones and dense
-    random masks stay with the march"""
-    return 2 * 1280 * int(rows) <= 128 * int(lines) + 32 * int(nblocks) * int(nz)
-
-
-def _cube_key(cube):
-    nz, ny, nx = cube.shape
-    return (cube.ptr, cube.shape, getattr(cube, "row_stride", nx), getattr(cube, "plane_stride", ny * nx), cube.write_generation)
-
-
-def _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws):
-    """the list of *cube*'s lane segments that *mask*'s bits include, or None.  Nothing changes for a spec's first two uses:
-    the list is built by the first launch that finds the bits already packed (*had_bits*) and the cube of the launch before
-    it - the same root array BY IDENTITY (a weak reference: a freed cube whose address a new array reuses never matches),
-    pointer, shape, strides and write generation - and then handed out until that key or the bits' changes.  The launch
-    that builds counts on *stream*, reads the counts back (one stream sync, as the bits pack has), forms the offsets on the
-    host, allocates, fills, and uses the list.  A refusal (list_is_kept), a launch that has no list and a failed
-    allocation are remembered on the spec and are silent: the bits march goes on."""
-    import weakref
-    if mask is None or mask.array is None:
-        return None
-    root = cube._root() if isinstance(cube, DeviceArray) else None
-    if root is None:
-        return None
-    key = (mask._bits_key,) + _cube_key(cube)
-    with _bits_lock:
-        same = mask._list_key == key and mask._list_root is not None and mask._list_root() is root
-        if not same:
-            mask._drop_list()
-            mask._list_key, mask._list_root = key, weakref.ref(root)
-            return None
-        if mask._list is not None or mask._list_failed:
-            return mask._list
-        if bits is None or not had_bits or not _switch_on("SPC_MOMENTS_LIST"):
-            return None
-        try:
-            desc = _lib.SpcMomentsListDesc()
-            wsp, wsn = C.c_void_p(ws.ptr if ws is not None else 0), ws.nbytes if ws is not None else 0
-            _lib.call("spc_moments_list_plan_f32", C.byref(c), C.byref(m), C.byref(o), wsp, wsn, C.byref(desc))
-            n = int(desc.nblocks * desc.nsub)
-            d_len, d_lines = DeviceArray((n,), np.uint32, cube.device), DeviceArray((n,), np.uint32, cube.device)
-            _lib.call("spc_moments_list_count_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.byref(o), wsp, wsn,
-                      C.c_void_p(bits.ptr), bits.nbytes, C.c_void_p(d_len.ptr), C.c_void_p(d_lines.ptr), n, C.byref(desc))
-            length = d_len.get(stream).astype(np.uint64)
-            lines = int(d_lines.get(stream).astype(np.uint64).sum())
-            rows = int(length.sum())
-            if not list_is_kept(rows, lines, desc.nblocks, cube.shape[0]):
-                mask._list_failed = True
-                return None
-            off = DeviceArray.from_numpy(np.cumsum(length) - length, cube.device, stream)
-            samples = DeviceArray((max(rows, 1) * 1024,), np.uint8, cube.device)
-            meta = DeviceArray((max(rows, 1) * 256,), np.uint8, cube.device)
-            lst = _MomentsList(desc, off, d_len, samples, meta, rows)
-            _lib.call("spc_moments_list_fill_f32", cube.device, _sh(stream), C.byref(c), C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c))
-            _lib.call("spc_stream_sync", cube.device, _sh(stream))      # later launches on any stream may read the list
-        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
-            mask._list_failed = True         # never an error: the bits march goes on
-            return None
-        mask._list = lst
-        return lst
-
-
-class _MomentsVlist:
-    """the device arrays of one voxel list (spc_moments_vlist: include/spcube_hip.h) and the struct that names them"""
-
-    def __init__(self, desc, off, length, entries, rows):
-        self.desc, self.off, self.len, self.entries, self.rows = desc, off, length, entries, int(rows)
-        c = self.c = _lib.SpcMomentsVlist()
-        c.desc = desc
-        c.d_entries, c.entries_bytes = entries.ptr, entries.nbytes
-        c.d_off, c.d_len, c.nsublists = off.ptr, length.ptr, int(desc.nblocks * desc.nsub)
-        c.rows = self.rows
-
-    @property
-    def nbytes(self):
-        return self.rows * 512
-
-
-def vlist_is_kept(vrows, rows):
-    """the voxel list is kept only where it reads at most half of what the list it is made from does: 512 bytes per entry row
-    against 1280.  A condition, not a tuning result: masks that keep three or four voxels of a lane segment (connected
-    signal masks) stay on the list"""
-    return 2 * 512 * int(vrows) <= 1280 * int(rows)
-
-
-def _moments_vlist(mask, lst, prev, device, stream):
-    """the voxel list made from *lst*, the list this launch reads, or None.  It is built by the first launch that finds the
-    list ALREADY BUILT BY AN EARLIER CALL (*prev*, the spec's list before this launch, is *lst*) and holding at least one
-    row - normally the spec's fourth use; an empty list is never compacted.  The launch that builds counts on *stream*,
-    reads the counts back (one stream sync), forms the offsets on the host, allocates, fills, and uses the voxel list.  A
-    refusal (vlist_is_kept), SPC_MOMENTS_VLIST=0 and a failed allocation are remembered on the spec and are silent: the
-    list goes on being read.  The voxel list is dropped with the list (MaskSpec._drop_list)."""
-    if lst is None:
-        return None
-    with _bits_lock:
-        if mask._list is not lst:            # another thread dropped it meanwhile
-            return None
-        if mask._vlist is not None or mask._vlist_failed:
-            return mask._vlist
-        if prev is not lst or lst.rows == 0:
-            return None
-        if not _switch_on("SPC_MOMENTS_VLIST"):
-            mask._vlist_failed = True
-            return None
-        try:
-            n = int(lst.desc.nblocks * lst.desc.nsub)
-            d_vlen = DeviceArray((n,), np.uint32, device)
-            _lib.call("spc_moments_vlist_count_f32", device, _sh(stream), C.byref(lst.c), C.c_void_p(d_vlen.ptr), n)
-            vlen = d_vlen.get(stream).astype(np.uint64)
-            vrows = int(vlen.sum())
-            if not vlist_is_kept(vrows, lst.rows):
-                mask._vlist_failed = True
-                return None
-            voff = DeviceArray.from_numpy(np.cumsum(vlen) - vlen, device, stream)
-            entries = DeviceArray((max(vrows, 1) * 512,), np.uint8, device)
-            vl = _MomentsVlist(lst.desc, voff, d_vlen, entries, vrows)
-            _lib.call("spc_moments_vlist_fill_f32", device, _sh(stream), C.byref(lst.c), C.byref(vl.c))
-            _lib.call("spc_stream_sync", device, _sh(stream))      # later launches on any stream may read the voxel list
-        except (_lib.HipLibraryError, _lib.HipUnsupported, MemoryError):
-            mask._vlist_failed = True        # never an error: the list goes on being read
-            return None
-        mask._vlist = vl
-        return vl
 
 
 def _cube_c(cube, dtype=None):
@@ -443,27 +230,13 @@ def moments(cube, cen, dv=1.0, m1_add=0.0, mask=None, want=_WANT_ALL, stream=Non
     if need and (ws is None or ws.nbytes < need):
         ws = DeviceArray((need,), np.uint8, cube.device)
     c, m = _cube_c(cube, _F32), _mask_c(mask, cube)
-    had_bits = mask is not None and mask._bits is not None
-    bits = _mask_bits(mask, stream) if cube.dtype == _F32 else None
-    prev = mask._list if mask is not None else None
-    lst = _moments_list(mask, cube, bits, had_bits, stream, c, m, o, ws) if cube.dtype == _F32 else None
-    vl = _moments_vlist(mask, lst, prev, cube.device, stream) if bits is not None and lst is not None else None
-    if vl is not None:                             # (whether the launch's plan is the voxel list's is the library's decision)
-        _lib.call("spc_moments_vlist_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
-                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
-                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c), C.byref(vl.c))
-    elif bits is not None and lst is not None:       # (whether the launch's plan is the list's is the library's decision)
-        _lib.call("spc_moments_list_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
-                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
-                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes, C.byref(lst.c))
-    elif bits is not None:     # (whether the launch can read them is the library's decision)
-        _lib.call("spc_moments_bits_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
-                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
-                  ws.nbytes if ws is not None else 0, C.c_void_p(bits.ptr), bits.nbytes)
-    else:
-        _lib.call("spc_moments_f32", cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr),
-                  float(dv), float(m1_add), C.byref(o), C.c_void_p(ws.ptr if ws is not None else 0),
-                  ws.nbytes if ws is not None else 0)
+    wsp = (C.c_void_p(ws.ptr if ws is not None else 0), ws.nbytes if ws is not None else 0)
+    common = (cube.device, _sh(stream), C.byref(c), C.byref(m), C.c_void_p(cen.ptr), float(dv), float(m1_add), C.byref(o)) + wsp
+    # the form a reused mask and cube are read in; *held* keeps its buffers from being freed by a drop in another thread
+    # until the launch that reads them has been queued (spc_free then waits for that launch)
+    entry, extra, held = moments_forms.select(mask, cube, stream, c, m, o, wsp)
+    _lib.call(entry, *common, *extra)
+    del held
     bufs["_workspace"] = ws
     return bufs
 

@@ -36,11 +36,11 @@ GENERAL = ("xwin_off1", "xwin_oddstride", "xwin_tail")
 # (operator, entry points, dispatch line, kind, tolerance and where it comes from).  Fast form: ALIGNED (with mask_same /
 # mask_contig); general form: GENERAL, and ALIGNED with mask_phase where the line tests the mask - unless noted.
 TABLE = [
-    ("moments", "spc_moments_f32", "spc_moments.hip:534 (aligned(v), v = 4, 2, 1; mask base and strides too)", "summing",
+    ("moments", "spc_moments_f32", "spc_moments.hip make_plan (aligned(v), v = 4, 2, 1; mask base and strides too)", "summing",
      "m0 1e-5 max, m1 1e-5 span, m2 1e-5 scale on rays with signal; extrema, counts exact: test_gpu_ops.py:56-72"),
     ("moments_f64", "spc_moments_f64 + spc_moment_order_f64", "spc_moments_f64.hip:186 (spc_pairs_ok_f64, spc_wide.h:39)", "summing",
      "1e-13: mask_edges.py:301 (test_moments_f64, test_gpu_round4.py)"),
-    ("moment_order", "spc_moment_order_f32 / _f64", "spc_moments.hip:654 (v4); spc_moments_f64.hip:186", "summing",
+    ("moment_order", "spc_moment_order_f32 / _f64", "spc_moments.hip spc_moment_order_f32 (v4); spc_moments_f64.hip:186", "summing",
      "rtol 1e-9, atol 1e-9 max: test_gpu_ops.py:116; float64 1e-12: mask_edges.py:317"),
     ("stats_axis", "spc_stats_axis_f32 / _f64, axes 0 1 2", "spc_stats.hip:855-856 (v4)", "summing",
      "count, min, max exact; sum, sumsq rtol 1e-12: test_gpu_ops.py:460-465"),

@@ -1,13 +1,14 @@
-// Stand-alone host check of spc_moments_list_plan_f32 / _count_f32 / _fill_f32 and spc_moments_list_f32 (csrc/spc_moments.hip)
-// for a CPU build under sanitizers: the argument checks, the desc a plan gives and the size and offset arithmetic held
+// Stand-alone host check of spc_moments_list_plan_f32 / _count_f32 / _fill_f32 and spc_moments_list_f32 (csrc/spc_moments.hip,
+// csrc/spc_moments_forms.hip) for a CPU build under sanitizers: the argument checks, the desc a plan gives and the size and offset arithmetic held
 // against it - the long-axis and the empty-mask cases among them - everything up to the device switch.  Every call that
 // would launch names device 2^20, which no machine has, so no kernel is ever launched and no pointer is dereferenced (the
 // buffers are host memory); the kernels need a device and are covered by tests/test_gpu_moments_list.py.  From the
 // repository root:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -c spectral_cube_amd/csrc/spc_moments.hip -o moments.o
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -c spectral_cube_amd/csrc/spc_moments_forms.hip -o forms.o
 //   /opt/rocm/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -c tools/host_check_moments_list.cpp -o main.o
-//   /opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined main.o moments.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o host_check && ./host_check
+//   /opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined main.o moments.o forms.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o host_check && ./host_check
 //
 // (its own main: nothing is preloaded, nothing is loaded into an interpreter)
 #include <cstdarg>
